@@ -340,6 +340,34 @@ def emit(full, args):
         print(json.dumps(compact), flush=True)
 
 
+DUMP_LIMIT = 64 << 20        # bytes: --dump-outputs writes at most this much; a larger output is sampled (fixed seed, whole frames)
+
+
+def dump_outputs(dirname, arrays, suffix="", shards=1):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one DIR/<name><suffix>.npy per array (float32 where that
+    holds every value exactly, else float64), arrays indexed by frame along axis 0. Past DUMP_LIMIT bytes the same seeded sample of frames is
+    kept from every array (each of `shards` ranks / devices gets its share of the limit) and their indices go to frame_index<suffix>.npy, so
+    that two builds run with the same arguments compare file for file."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    F = len(next(iter(arrays.values())))
+    per_frame = sum(v[:1].nbytes for v in arrays.values()) + 8
+    room = DUMP_LIMIT // shards - 128 * (len(arrays) + 1)       # the shard's part of the limit less each .npy file's header
+    if F * per_frame > room:
+        keep = np.sort(np.random.default_rng(SEED).choice(F, room // per_frame, replace=False))
+        arrays = dict({k: v[keep] for k, v in arrays.items()}, frame_index=keep.astype(np.float64))
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), v)
+
+
+def stats_arrays(payload, stats):
+    """payload uint8 [F, payload_stride] and stats STATS_DTYPE [F] (mgpu_frame_stats) as the arrays dump_outputs() writes."""
+    out = {"payload": payload.astype(np.float32)}
+    for name in STATS_DTYPE.names:
+        out[name] = stats[name].astype(np.float32 if stats[name].dtype == np.float32 else np.float64)
+    return out
+
+
 def cpu_baseline(cfg, max_iters, bb_sample, flags, gpu_payload, gpu_stats):
     """Time the CPU checker on a bounded sample of the same frames; also cross-check the GPU output."""
     import oraclelib
@@ -602,6 +630,14 @@ def run_pool(args):
                            "ldpc_kernel_ms": dec_g, "frontend_kernel_ms": fe_g, "wall_ms": float(dev_ms[g])})
     pool.enable_timing(False)
     hard_total = pool.decoder_hard_frames() - hard0        # frames decided without iterating: reported with max + 1 iterations, none executed
+    if args.dump_outputs:                                  # the last timed step's outputs: every device's shard
+        for g in range(N):
+            sfx = "_dev%d" % g if N > 1 else ""
+            if args.ldpc_only:
+                dump_outputs(args.dump_outputs, {"iterations_done": pool.copy_to_host(g, np.zeros(F, np.int32), d_it[g]).astype(np.float64)}, sfx, N)
+            else:
+                dump_outputs(args.dump_outputs, stats_arrays(pool.copy_to_host(g, np.zeros((F, ps), np.uint8), d_pay[g]),
+                                                             pool.copy_to_host(g, np.zeros(F, STATS_DTYPE), d_st[g])), sfx, N)
     iters_total -= hard_total * args.iters
     frames_total = F * N * args.steps
     iters_per_launch = iters_total / (args.steps * N)
@@ -693,7 +729,12 @@ def main():
     ap.add_argument("--pool", action="store_true",
                     help="one process drives the --gpus devices through the C-ABI pool (include/mercury_pool.h: one context + one host "
                          "thread per device), device-resident shards; also what `python bench.py --gpus N` does when not under torchrun")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (payload bytes and per-frame stats) as DIR/<name>.npy, float32 / "
+                         "float64, at most %d MB (a seeded sample of frames beyond that); same arguments, same inputs" % (DUMP_LIMIT >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dry_run:
         return dry_run(args)
     if args.pool or (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus > 1):
@@ -792,6 +833,9 @@ def main():
     # as the reference's loop would after changing nothing) count with the iterations they EXECUTED: none
     hard_frames = rx.decoder_hard_frames() - hard0
     iters_acc.sub_(hard_frames * args.iters)
+    if args.dump_outputs:                   # the last timed step's outputs, before anything else reuses the buffers
+        dump_outputs(args.dump_outputs, stats_arrays(payload.cpu().numpy(), stats.cpu().numpy().view(STATS_DTYPE).reshape(F)),
+                     "_rank%d" % rank if world > 1 else "", world)
 
     tmax = torch.tensor([dt], dtype=torch.float64, device=rdev)
     sums = torch.stack([iters_acc, decoded_acc]).to(torch.float64).to(rdev)

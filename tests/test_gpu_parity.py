@@ -784,6 +784,34 @@ def test_bench_pool_two_contexts_on_one_gpu():
     assert j["cpu_baseline"]["gpu_vs_cpu_mismatches"] == 0 and j["n_gpus"] == 1 and j["cpu_baseline"]["kind"] == "port"
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: the payload and stats of the LAST timed step. With two input batches cycled, 1 and 3 timed steps end on
+    the same batch and must dump identical files (same arguments, same inputs, deterministic decoder), 2 steps end on the other batch; the
+    contract line reports the steps it timed and ms_per_step."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps, lines = {}, {}
+    for steps in (1, 2, 3):
+        d = tmp_path / ("s%d" % steps)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--frames", "256",
+               "--esn0", "2.5", "--nbuf", "2", "--no-extras", "--no-cpu-baseline", "--line", "compact", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[steps] = json.loads(r.stdout.strip().splitlines()[-1])
+        dumps[steps] = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    for steps, c in lines.items():
+        assert c["steps"] == steps and c["ms_per_step"] > 0
+    one = dumps[1]
+    assert set(one) == {"payload", "iterations_done", "crc", "all_zeros", "message_decoded", "variance", "snr_db"}
+    assert all(v.dtype in (np.float32, np.float64) and len(v) == 256 for v in one.values())
+    assert one["payload"].shape[1] >= Oracle(8, 50).payload_bytes and np.array_equal(one["payload"], one["payload"].astype(np.uint8))
+    assert abs(one["message_decoded"].mean() - lines[1]["decoded_fraction"]) < 1e-5 and lines[1]["decoded_fraction"] > 0.97
+    assert all(np.array_equal(one[k], dumps[3][k], equal_nan=True) for k in one)
+    assert not np.array_equal(one["payload"], dumps[2]["payload"])
+
+
 @pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5, 6, 12])
 def test_decoder_only_all_eight_rates_bpsk_llrs(cfg):
     """every LDPC rate with BPSK LLRs llr = 2y/sigma^2 around the waterfall, so that the

@@ -117,6 +117,36 @@ def test_bench_contract_line_is_compact_whatever_the_full_record_holds(capsys):
     assert len(out) == 2 and json.loads(out[0])["bench_full_record"] and json.loads(out[1]) == bench.compact_line(full) and len(out[1]) <= 4096
 
 
+def test_bench_dump_outputs_writes_exact_floats_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: payload bytes and every mgpu_frame_stats field as float32 / float64 .npy files holding the values exactly;
+    an output past the size limit is cut to the same seeded sample of frames in every array (frame_index says which), within the limit."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    F, stride = 3000, 200
+    payload = rng.integers(0, 256, (F, stride), dtype=np.uint8)
+    stats = np.zeros(F, bench.STATS_DTYPE)
+    for name in stats.dtype.names:
+        stats[name] = rng.integers(-2 ** 31, 2 ** 31 - 1, F) if stats[name].dtype == np.int32 else rng.standard_normal(F)
+    bench.dump_outputs(str(tmp_path / "all"), bench.stats_arrays(payload, stats))
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert set(got) == {"payload"} | set(bench.STATS_DTYPE.names)
+    assert all(v.dtype in (np.float32, np.float64) and len(v) == F for v in got.values())
+    assert np.array_equal(got["payload"], payload) and all(np.array_equal(got[n], stats[n]) for n in bench.STATS_DTYPE.names)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 20)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), bench.stats_arrays(payload, stats))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "frame_index.npy" in files
+    assert 0 < sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1 << 20
+    keep = np.load(tmp_path / "a" / "frame_index.npy").astype(np.int64)
+    assert 0 < len(keep) < F and np.all(np.diff(keep) > 0)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    assert np.array_equal(np.load(tmp_path / "a" / "payload.npy"), payload[keep])
+    assert np.array_equal(np.load(tmp_path / "a" / "crc.npy"), stats["crc"][keep])
+
+
 def test_table_blob_is_wellformed():
     import struct
     blob = open(os.path.join(ROOT, "mercury_amd", "data", "mercury_ldpc_tables.bin"), "rb").read()

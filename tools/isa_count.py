@@ -19,10 +19,11 @@ from mercury_amd.build import HIPCC_FLAGS, _hipcc  # noqa: E402
 
 
 def assembly(unit):
-    out = os.path.join(tempfile.gettempdir(), "isa_" + unit + ".s")
-    subprocess.run([_hipcc()] + HIPCC_FLAGS + ["-I", os.path.join(ROOT, "mercury_amd", "csrc"), "--cuda-device-only", "-S", "-o", out,
-                    os.path.join(ROOT, "mercury_amd", "csrc", unit)], check=True, stderr=subprocess.DEVNULL)
-    return open(out).read().split("\n")
+    with tempfile.TemporaryDirectory(prefix="isa_") as tmp:            # a private directory: no clash with another user's or run's file
+        out = os.path.join(tmp, unit + ".s")
+        subprocess.run([_hipcc()] + HIPCC_FLAGS + ["-I", os.path.join(ROOT, "mercury_amd", "csrc"), "--cuda-device-only", "-S", "-o", out,
+                        os.path.join(ROOT, "mercury_amd", "csrc", unit)], check=True, stderr=subprocess.DEVNULL)
+        return open(out).read().split("\n")
 
 
 def classify(op, c):
