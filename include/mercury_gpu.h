@@ -46,7 +46,7 @@ extern "C" {
 #define MGPU_OK 0
 #define MGPU_ERR_ARG 1        /* bad argument (cfg out of range, null pointer, F > max_batch ...) */
 #define MGPU_ERR_DEVICE 2     /* HIP runtime error; text in mgpu_last_error() */
-#define MGPU_ERR_TABLES 3     /* LDPC table blob missing / corrupt */
+#define MGPU_ERR_TABLES 3     /* refused before any device work: LDPC table blob missing / corrupt, a geometry the kernels do not cover */
 #define MGPU_ERR_UNSUPPORTED 4
 
 /* decoder selection — reference: cl_ldpc::decoding_algorithm (physical_defines.h:44-45) */
@@ -146,9 +146,10 @@ int mgpu_create(const mgpu_config* cfg, mgpu_ctx** out);
  * honoured for the OFDM modes as load_configuration copies them (telecom_system.cc:2775-2778): the pilot lattice
  * (cl_pilot_configurator::configure, ofdm.cc:976-1064), every size derived from it (data_container.cc:90-99) and the whole RX / TX /
  * generator path follow. With Dy != 3 the LS estimator takes the kernel's general window walk (slower than the lattice-specialised
- * one; same sums in the same order). Refused (MGPU_ERR_TABLES): a geometry whose data cells hold more bits than a codeword or fewer than
- * its parity plus one payload byte, one with a column of fewer than two pilots, one that does not fit the front-end's LDS carve, the
- * MFSK modes.
+ * one; same sums in the same order). Refused (MGPU_ERR_TABLES), on any machine and before any device work: a geometry whose data
+ * cells hold more bits than a codeword or fewer than its parity plus one payload byte, one with a column of fewer than two pilots,
+ * one outside the front-end's interpolation table (Nsymb * Nc >= 4096, or 1024 pilots or more), one whose front-end, decoder or
+ * generator LDS carve exceeds a compute unit's 160 KiB, a code the selected decoder instance does not cover, the MFSK modes.
  * FIXED, not parameters: Nc = 50, Nfft = 256 (Ngi = 16, Nofdm = 272) and the pilot lattice's column step Dx = 1 — physical_config.cc:35-65
  * gives all 17 modes these values and the kernels are specialised for them. The three fields exist only so that a caller holding the
  * reference's configuration can have it confirmed: 0 or exactly 50 / 256 / 1 is accepted, anything else returns MGPU_ERR_UNSUPPORTED

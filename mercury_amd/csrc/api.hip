@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -23,39 +24,30 @@ thread_local std::string g_create_error;
 
 namespace mgpu_detail {
 
-void ctx_alloc(mgpu_ctx* c) {
+constexpr size_t kLdsBytes = size_t(160) * 1024;     // LDS of a compute unit: every kernel's dynamic carve must fit it
+
+struct Plan { std::vector<uint16_t> pilot_cell, crc_tab; std::vector<uint32_t> cell_lerp; std::vector<double> cons, tw; };
+
+// The part of mgpu_create that needs no device: the scalars of dev / ldev, the launch shapes, LDS sizes and decoder instance go into the
+// context, the derived tables into the plan. Everything it refuses is refused before any device work (MGPU_ERR_TABLES).
+Plan ctx_plan(mgpu_ctx* c) {
     const auto& t = c->tab;
     MgpuDev& d = c->dev;
-    std::vector<uint16_t> pilot_cell;
-    for (int i = 0; i < t.Nsymb * t.Nc; ++i) if (t.cell_type[i]) pilot_cell.push_back(uint16_t(i));
-    std::vector<double> cons, tw;
-    for (auto& z : t.constellation) { cons.push_back(z.re); cons.push_back(z.im); }
-    for (auto& z : t.twiddle) { tw.push_back(z.re); tw.push_back(z.im); }
-    d.cell_type = c->keep(upload(t.cell_type));
-    d.pilot_val = c->keep(upload(t.pilot_val));
-    d.pilot_cell = c->keep(upload(pilot_cell));
-    d.constellation = c->keep(upload(cons));
-    d.twiddle = c->keep(upload(tw));
-    d.sym_src = c->keep(upload(t.sym_src));
-    d.llr_src = c->keep(upload(t.llr_src));
-    d.ls_weight = c->keep(upload(t.ls_weight));
-    d.scrambler = c->keep(upload(t.scrambler));
-    d.llr_dst = c->keep(upload(t.llr_dst));
-    d.bit_il = c->keep(upload(t.bit_il));
-    c->d_fir[0] = c->keep(upload(t.fir_time_sync));
-    c->d_fir[1] = c->keep(upload(t.fir_data));
-    d.tf_inv = c->keep(upload(t.tf_inv));
-    d.data_cell = c->keep(upload(t.data_cell));
-    d.cell_lerp = nullptr;
+    Plan p;
+    for (int i = 0; i < t.Nsymb * t.Nc; ++i) if (t.cell_type[i]) p.pilot_cell.push_back(uint16_t(i));
+    for (auto& z : t.constellation) { p.cons.push_back(z.re); p.cons.push_back(z.im); }
+    for (auto& z : t.twiddle) { p.tw.push_back(z.re); p.tw.push_back(z.im); }
     if (t.mfsk_M == 0) {
         // The two pilot rows a data cell (i, j) interpolates between and their pilots' indices, tabulated from the lattice itself the way
         // interpolate_linear_col walks a column (interpolator.cc:163-254): between two measured rows the nearest one above and the nearest
         // one below; above the column's first measured row the first two, below its last one the last two (extrapolation). Every column
         // needs two pilots (a column with fewer is refused: the reference's walk degenerates there). The kernel used to derive all of this
         // per cell from divisions by 50 and 3.
+        const std::vector<uint16_t>& pilot_cell = p.pilot_cell;
         std::vector<int> pilot_of_cell(size_t(t.Nsymb) * t.Nc, -1);
-        for (size_t p = 0; p < pilot_cell.size(); ++p) pilot_of_cell[pilot_cell[p]] = int(p);
-        std::vector<uint32_t> tab(size_t(t.nData) * 2, 0u);
+        for (size_t q = 0; q < pilot_cell.size(); ++q) pilot_of_cell[pilot_cell[q]] = int(q);
+        std::vector<uint32_t>& tab = p.cell_lerp;
+        tab.assign(size_t(t.nData) * 2, 0u);
         bool ok = t.Nsymb >= 2 && t.Nsymb * t.Nc < 4096 && pilot_cell.size() < 1024 && t.Nsymb < 256;
         std::vector<std::vector<int>> col_rows(size_t(t.Nc));
         for (int i = 0; i < t.Nsymb; ++i)
@@ -75,10 +67,7 @@ void ctx_alloc(mgpu_ctx* c) {
             tab[2 * size_t(k) + 1] = uint32_t(a) | uint32_t(b) << 8 | uint32_t(i) << 16;
         }
         if (!ok) throw std::runtime_error("pilot lattice / frame geometry outside what the front-end kernel's interpolation table covers");
-        d.cell_lerp = c->keep(upload(tab));
     }
-    d.cptr = c->keep(upload(t.graph.cptr));
-    d.cvar = c->keep(upload(t.graph.cvar));
     d.S = t.graph.S;
     d.M = t.M; d.bps = t.bps; d.K = t.K; d.P = t.P; d.N = t.N; d.E = t.graph.E;
     d.Nsymb = t.Nsymb; d.G = t.Nsymb * t.Nc; d.nData = t.nData; d.nBits = t.nBits; d.nPilots = t.nPilots;
@@ -110,34 +99,23 @@ void ctx_alloc(mgpu_ctx* c) {
     d.active_nsymb = t.active_nsymb; d.active_nbits = t.active_nbits; d.mfsk_amp = t.mfsk_amp;
     d.puncture_from = (c->cfg.test_puncture_nBits > 0 && c->cfg.test_puncture_nBits < t.active_nbits) ? c->cfg.test_puncture_nBits : t.active_nbits;
     LdpcDev& l = c->ldev;
-    l.scrambler = d.scrambler;
-    l.cptr = d.cptr; l.cvar = d.cvar;
     {   // the CRC as a sum of per-bit constants (crc16_modbus_rtu.cc:25-45 is linear over GF(2) up to the register's initial value)
         const int full = d.nReal / 8;
         std::vector<uint8_t> msg(size_t(full > 0 ? full : 1), 0);
         const uint16_t zero = mgpu::crc16_modbus(msg.data(), full);
-        std::vector<uint16_t> tab(size_t(full > 0 ? full : 1) * 8, 0);
+        p.crc_tab.assign(size_t(full > 0 ? full : 1) * 8, 0);
         for (int b = 0; b < full; ++b)
             for (int j = 0; j < 8; ++j) {
                 msg[b] = uint8_t(1u << j);
-                tab[size_t(b) * 8 + j] = uint16_t(mgpu::crc16_modbus(msg.data(), full) ^ zero);
+                p.crc_tab[size_t(b) * 8 + j] = uint16_t(mgpu::crc16_modbus(msg.data(), full) ^ zero);
                 msg[b] = 0;
             }
-        l.crc_tab = c->keep(upload(tab));
         l.crc_init = zero;
     }
-    l.gdesc = c->keep(upload(t.graph.gdesc));
-    l.gkpack = c->keep(upload(t.graph.gkpack));
-    l.vinfo_g = c->keep(upload(t.graph.vinfo_g));
     l.Sg = t.graph.Sg;
-    l.sadr = c->keep(upload(t.graph.sadr));
-    l.bhead = c->keep(upload(t.graph.bhead));
-    l.bmask = c->keep(upload(t.graph.bmask));
-    l.vinfo2 = c->keep(upload(t.graph.vinfo2));
     l.DM = t.graph.DM;
     l.S = d.S; l.N = d.N; l.P = d.P; l.K = d.K; l.E = d.E; l.nReal = d.nReal; l.payload_stride = d.payload_stride;
     l.max_iters = d.max_iters; l.minsum_alpha = d.minsum_alpha;
-    l.hard_frames = reinterpret_cast<unsigned long long*>(c->keep(upload(std::vector<uint64_t>(64, 0))));
     {   // fp64 decoder, a frame's first iterations (ldpc.hip "adaptive"): from how many odd checks on - estimated from the 16 bins a judged look
         // samples - the next iteration's posteriors (the next two iterations') are looked at inside the following check pass instead of by a
         // pass of their own. Two pairs of weights: for the look at the channel's hard decisions (the first iteration removes far more errors
@@ -158,67 +136,92 @@ void ctx_alloc(mgpu_ctx* c) {
         auto byte = [&](int weight) { const int m = sample_min(weight); return unsigned(m > 255 ? 255 : m); };      // (a wavefront's first bin holds at most 64 checks, 16 wavefronts: "never" is any value above 1024 - 255 stands for it, see ldpc.hip)
         l.spec_sample_pack = byte(w[0]) | byte(w[1]) << 8 | byte(w[2]) << 16 | byte(w[3]) << 24;
     }
-    HIPCK(hipStreamCreate(&c->stream));
-    for (auto& q : c->ev) for (auto& e : q) HIPCK(hipEventCreate(&e));
-    for (auto& e : c->sync_ev) HIPCK(hipEventCreate(&e));
 
     const bool mfsk = t.mfsk_M > 0;      // the MFSK front-end keeps no frame grid in LDS (csrc/mfsk.hip)
     {
         const char* e = getenv("MERCURY_FE_THREADS");
         const size_t lds512 = mfsk ? 0 : mgpu_frontend_lds_bytes(d.G, d.nPilots, d.nBits, 512);
-        c->fe_threads = e ? atoi(e) : (lds512 > size_t(160) * 1024 / 2 ? 1024 : 512);
+        c->fe_threads = e ? atoi(e) : (lds512 > kLdsBytes / 2 ? 1024 : 512);
         if (c->fe_threads != 512 && c->fe_threads != 1024) throw std::invalid_argument("MERCURY_FE_THREADS must be 512 or 1024");
         c->lds_fe = mfsk ? 0 : mgpu_frontend_lds_bytes(d.G, d.nPilots, d.nBits, c->fe_threads);
     }
     c->lds_tx = mgpu_txgen_lds_bytes(mfsk ? 0 : d.G);
-    if (!mfsk) HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_fe)));
-    HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(mgpu_txgen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_tx)));
-    {
-        int geo[6];
-        mgpu_tsync_fine_geometry(geo);
-        HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(mgpu_tsync_metric_fine_kernel_r4), hipFuncAttributeMaxDynamicSharedMemorySize, geo[2]));
-        HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(mgpu_tsync_metric_fine_kernel_r8), hipFuncAttributeMaxDynamicSharedMemorySize, geo[5]));
-    }
     switch (c->cfg.decoder) {
-        case MGPU_DEC_SPA:
+        case MGPU_DEC_SPA: {
             if (!t.graph.fp64_limit.empty()) throw std::runtime_error(t.graph.fp64_limit);
             c->lds_dec = mgpu_spa_lds_bytes(d.S, d.N);
-            {
-                const int ne = std::max(4, (d.S + 1023) / 1024);      // rounds of 16 bins; the smallest instance runs 4 (tables sized to match)
-                if (ne > 8) throw std::runtime_error("graph too large for the sum-product kernel");
-                if (t.graph.maxdeg > mgpu_spa_max_degree(ne)) throw std::runtime_error("check degree exceeds the sum-product kernel's unrolled product walk");
-                switch (ne) {
-                    case 4: c->spa_kernel = mgpu_ldpc_spa_kernel_ne4; break;
-                    case 5: c->spa_kernel = mgpu_ldpc_spa_kernel_ne5; break;
-                    case 6: c->spa_kernel = mgpu_ldpc_spa_kernel_ne6; break;
-                    case 7: c->spa_kernel = mgpu_ldpc_spa_kernel_ne7; break;
-                    default: c->spa_kernel = mgpu_ldpc_spa_kernel_ne8; break;
-                }
-            }
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(c->spa_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_dec)));
+            const int ne = std::max(4, (d.S + 1023) / 1024);      // rounds of 16 bins; the smallest instance runs 4 (tables sized to match)
+            if (ne > 8) throw std::runtime_error("graph too large for the sum-product kernel");
+            if (t.graph.maxdeg > mgpu_spa_max_degree(ne)) throw std::runtime_error("check degree exceeds the sum-product kernel's unrolled product walk");
+            const DecoderKernel by_ne[5] = {mgpu_ldpc_spa_kernel_ne4, mgpu_ldpc_spa_kernel_ne5, mgpu_ldpc_spa_kernel_ne6, mgpu_ldpc_spa_kernel_ne7, mgpu_ldpc_spa_kernel_ne8};
+            c->spa_kernel = by_ne[ne - 4];
             break;
+        }
         case MGPU_DEC_GBF:
             c->lds_dec = mgpu_gbf_lds_bytes(d.N);
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(mgpu_ldpc_gbf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_dec)));
             break;
-        case MGPU_DEC_MINSUM: {
+        case MGPU_DEC_MINSUM:
+        case MGPU_DEC_SPA_FAST:
             if (!t.graph.fp32_limit.empty()) throw std::runtime_error(t.graph.fp32_limit);
-            c->lds_dec = mgpu_spa_fast_lds_bytes(c->ldev.Sg, d.N);
-            c->dec_threads = 512;
-            c->spa_kernel = mgpu_ldpc_minsum_kernel_t512;
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(c->spa_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_dec)));
+            c->lds_dec = mgpu_spa_fast_lds_bytes(l.Sg, d.N);
+            c->dec_threads = 512;            // SPA_FAST: 8 wavefronts per barrier domain, the kernel is bound by waits, not by issue (1024 threads: 1.4x slower)
+            c->spa_kernel = c->cfg.decoder == MGPU_DEC_MINSUM ? mgpu_ldpc_minsum_kernel_t512 : mgpu_ldpc_spa_fast_kernel_t512;
             break;
-        }
-        case MGPU_DEC_SPA_FAST: {
-            if (!t.graph.fp32_limit.empty()) throw std::runtime_error(t.graph.fp32_limit);
-            c->lds_dec = mgpu_spa_fast_lds_bytes(c->ldev.Sg, d.N);
-            c->dec_threads = 512;            // 8 wavefronts per barrier domain: the kernel is bound by waits, not by issue (1024 threads: 1.4x slower)
-            c->spa_kernel = mgpu_ldpc_spa_fast_kernel_t512;
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(c->spa_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_dec)));
-            break;
-        }
         default: throw std::runtime_error("unknown decoder");
     }
+    if (c->lds_fe > kLdsBytes) throw std::runtime_error("frame geometry too large for the front-end kernel's LDS carve");
+    if (c->lds_dec > kLdsBytes) throw std::runtime_error("code too large for the decoder kernel's LDS");
+    if (c->lds_tx > kLdsBytes) throw std::runtime_error("frame geometry too large for the generator kernel's LDS");
+    return p;
+}
+
+// The rest of mgpu_create, on the device: the plan's and the mode's tables, the context's stream and events, the kernels' LDS limits.
+void ctx_upload(mgpu_ctx* c, const Plan& p) {
+    const auto& t = c->tab;
+    MgpuDev& d = c->dev;
+    LdpcDev& l = c->ldev;
+    d.cell_type = c->keep(t.cell_type);
+    d.pilot_val = c->keep(t.pilot_val);
+    d.pilot_cell = c->keep(p.pilot_cell);
+    d.constellation = c->keep(p.cons);
+    d.twiddle = c->keep(p.tw);
+    d.sym_src = c->keep(t.sym_src);
+    d.llr_src = c->keep(t.llr_src);
+    d.ls_weight = c->keep(t.ls_weight);
+    d.scrambler = c->keep(t.scrambler);
+    d.llr_dst = c->keep(t.llr_dst);
+    d.bit_il = c->keep(t.bit_il);
+    c->d_fir[0] = c->keep(t.fir_time_sync);
+    c->d_fir[1] = c->keep(t.fir_data);
+    d.tf_inv = c->keep(t.tf_inv);
+    d.data_cell = c->keep(t.data_cell);
+    d.cell_lerp = t.mfsk_M == 0 ? c->keep(p.cell_lerp) : nullptr;
+    d.cptr = c->keep(t.graph.cptr);
+    d.cvar = c->keep(t.graph.cvar);
+    l.scrambler = d.scrambler;
+    l.cptr = d.cptr; l.cvar = d.cvar;
+    l.crc_tab = c->keep(p.crc_tab);
+    l.gdesc = c->keep(t.graph.gdesc);
+    l.gkpack = c->keep(t.graph.gkpack);
+    l.vinfo_g = c->keep(t.graph.vinfo_g);
+    l.sadr = c->keep(t.graph.sadr);
+    l.bhead = c->keep(t.graph.bhead);
+    l.bmask = c->keep(t.graph.bmask);
+    l.vinfo2 = c->keep(t.graph.vinfo2);
+    l.hard_frames = reinterpret_cast<unsigned long long*>(c->keep(std::vector<uint64_t>(64, 0)));
+    HIPCK(hipStreamCreate(&c->stream.h));
+    for (auto& q : c->ev) for (auto& e : q) HIPCK(hipEventCreate(&e.h));
+    for (auto& e : c->sync_ev) HIPCK(hipEventCreate(&e.h));
+    auto lds_limit = [](auto kernel, size_t bytes) {
+        HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
+    };
+    if (t.mfsk_M == 0) lds_limit(fe_kernel(c->fe_threads), c->lds_fe);
+    lds_limit(mgpu_txgen_kernel, c->lds_tx);
+    int geo[6];
+    mgpu_tsync_fine_geometry(geo);
+    lds_limit(mgpu_tsync_metric_fine_kernel_r4, geo[2]);
+    lds_limit(mgpu_tsync_metric_fine_kernel_r8, geo[5]);
+    lds_limit(c->cfg.decoder == MGPU_DEC_GBF ? mgpu_ldpc_gbf_kernel : c->spa_kernel, c->lds_dec);
 }
 
 // Workspaces sized by max_batch are created on first use, so a context that only ever runs e.g. the
@@ -227,18 +230,18 @@ void ensure_workspaces(mgpu_ctx* c, unsigned what) {
     const auto& t = c->tab;
     const size_t B = size_t(c->max_batch);
     if ((what & WS_FRONTEND) && !c->d_variance) {
-        HIPCK(hipMalloc(&c->d_variance, B * sizeof(float)));
-        HIPCK(hipMalloc(&c->d_snrvar, B * sizeof(float)));
-        if (t.estimator == MGPU_EST_ZF) HIPCK(hipMalloc(&c->d_eqdata, B * t.nData * 16));
+        c->d_variance.grow(B * sizeof(float));
+        c->d_snrvar.grow(B * sizeof(float));
+        if (t.estimator == MGPU_EST_ZF) c->d_eqdata.grow(B * t.nData * 16);
     }
-    if ((what & WS_LLR) && !c->d_llr) HIPCK(hipMalloc(&c->d_llr, B * t.N * sizeof(float)));
+    if ((what & WS_LLR) && !c->d_llr) c->d_llr.grow(B * t.N * sizeof(float));
     if ((what & WS_OUT) && !c->d_payload) {
-        HIPCK(hipMalloc(&c->d_payload, B * t.payload_stride));
-        HIPCK(hipMalloc(&c->d_stats, B * sizeof(MgpuStatsDev)));
+        c->d_payload.grow(B * t.payload_stride);
+        c->d_stats.grow(B * sizeof(MgpuStatsDev));
     }
     if ((what & WS_BITS) && !c->d_bits) {
-        HIPCK(hipMalloc(&c->d_bits, B * t.K));
-        HIPCK(hipMalloc(&c->d_iters, B * sizeof(int)));
+        c->d_bits.grow(B * t.K);
+        c->d_iters.grow(B * sizeof(int));
     }
 }
 
@@ -274,7 +277,7 @@ void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float
         if (off && (taps.grid || taps.H || taps.eq || taps.syms || taps.llr_demod || taps.variance || taps.agc_gain || taps.mean_H))
             throw std::invalid_argument("stage taps are limited to 2^21 frames per call");
         hipLaunchKernelGGL(fe_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, d_bb + size_t(off) * stride * 2, n,
-                           d_llr + size_t(off) * t.N, d_var + off, at(d_snrvar, off), at(c->d_eqdata, (size_t(frame0) + off) * t.nData * 2), taps);
+                           d_llr + size_t(off) * t.N, d_var + off, at(d_snrvar, off), at<double>(c->d_eqdata, (size_t(frame0) + off) * t.nData * 2), taps);
         HIPCK(hipGetLastError());
     }
     if (c->timing) HIPCK(hipEventRecord(c->ev[slot][1], s));
@@ -313,12 +316,8 @@ const double* mixer_table(mgpu_ctx* c, double carrier_hz, size_t count, hipStrea
     // sincos is not bit-for-bit its cos + sin, so the same call is made here
     for (size_t i = 0; i < count; ++i) ::sincos(2 * M_PI * carrier_hz * double(int(i)) * Ts, &cs[2 * i + 1], &cs[2 * i]);
     HIPCK(hipStreamSynchronize(s));
-    if (c->mix_cap < cs.size()) {
-        (void)hipFree(c->d_mix_cs);
-        c->d_mix_cs = nullptr; c->mix_cap = 0;
-        HIPCK(hipMalloc(reinterpret_cast<void**>(&c->d_mix_cs), cs.size() * 8));
-        c->mix_cap = cs.size();
-    }
+    c->mix_count = 0;                    // no table until the new one is in place
+    c->d_mix_cs.grow(cs.size() * 8);
     HIPCK(hipMemcpy(c->d_mix_cs, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
     c->mix_carrier = carrier_hz; c->mix_count = count;
     return c->d_mix_cs;
@@ -524,9 +523,10 @@ int mgpu_create_explicit(const mgpu_config* cfg, const mgpu_explicit_params* xp_
     if (cfg->decoder < 0 || cfg->decoder > MGPU_DEC_SPA_FAST) { g_create_error = "unknown decoder"; return MGPU_ERR_ARG; }
     if (cfg->max_batch < 1) { g_create_error = "max_batch must be >= 1"; return MGPU_ERR_ARG; }
     if (cfg->test_puncture_nBits < 0) { g_create_error = "test_puncture_nBits must be >= 0"; return MGPU_ERR_ARG; }
-    mgpu_ctx* c = new mgpu_ctx();
+    std::unique_ptr<mgpu_ctx> c(new mgpu_ctx());
     c->cfg = *cfg;
     c->max_batch = cfg->max_batch;
+    mgpu_detail::Plan plan;
     try {
         std::vector<uint8_t> file_blob;
         const uint8_t* blob = mgpu_ldpc_blob;
@@ -538,59 +538,36 @@ int mgpu_create_explicit(const mgpu_config* cfg, const mgpu_explicit_params* xp_
             blob = file_blob.data();
             blob_size = file_blob.size();
         }
-        try {
-            c->tab = mgpu::build_mode_tables(cfg->cfg, cfg->mfsk_ctrl_mode, blob, blob_size, xp);
-        } catch (const std::exception& e) {
-            g_create_error = e.what();
-            delete c;
-            return MGPU_ERR_TABLES;
-        }
+        c->tab = mgpu::build_mode_tables(cfg->cfg, cfg->mfsk_ctrl_mode, blob, blob_size, xp);
+        plan = mgpu_detail::ctx_plan(c.get());
+    } catch (const std::exception& e) {
+        g_create_error = e.what();
+        return MGPU_ERR_TABLES;
+    }
+    try {
         int ndev = 0;
         HIPCK(hipGetDeviceCount(&ndev));
         if (ndev < 1) throw HipError("no HIP device visible (the MI355X path has no CPU fallback)");
         HIPCK(hipSetDevice(cfg->device));
         c->numa_node = mgpu_detail::device_numa_node(cfg->device);      // where the context's page-locked staging lives (-1: anywhere)
-        mgpu_detail::ctx_alloc(c);
+        mgpu_detail::ctx_upload(c.get(), plan);
     } catch (const std::exception& e) {
         g_create_error = e.what();
-        mgpu_destroy(c);
         return MGPU_ERR_DEVICE;
     }
-    *out = c;
+    *out = c.release();
     return MGPU_OK;
 }
 
 void mgpu_destroy(mgpu_ctx* c) {
     if (!c) return;
+    const int device = c->cfg.device;
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != c->cfg.device && hipSetDevice(c->cfg.device) != hipSuccess) prev = -1;   // no device: nothing below was allocated
-    for (void* p : c->owned) (void)hipFree(p);
-    (void)hipFree(c->d_baseband); (void)hipFree(c->d_llr); (void)hipFree(c->d_variance); (void)hipFree(c->d_snrvar);
-    (void)hipFree(c->d_payload); (void)hipFree(c->d_stats); (void)hipFree(c->d_bits); (void)hipFree(c->d_iters); (void)hipFree(c->d_eqdata);
-    if (c->rxloop_ws && c->rxloop_ws_free) c->rxloop_ws_free(c->rxloop_ws);
-    (void)hipFree(c->rb_stage);
-    (void)hipFree(c->rb_compact);
-    if (c->rb_stream) (void)hipStreamDestroy(c->rb_stream);
-    if (c->tx_state && c->tx_state_free) c->tx_state_free(c->tx_state);
-    (void)hipFree(c->d_mix_cs);
-    if (c->one_frame_graph) (void)hipGraphExecDestroy(c->one_frame_graph);
-    if (c->h_one_in) (void)hipHostFree(c->h_one_in);
-    if (c->h_one_out) (void)hipHostFree(c->h_one_out);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    for (auto& q : c->ev) for (auto& e : q) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->sync_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->hp_ev) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(c->d_one_in);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    for (auto& p : c->pipe) {
-        (void)hipFree(p.d_in);
-        if (p.stream) (void)hipStreamDestroy(p.stream);
-        if (p.done) (void)hipEventDestroy(p.done);
-        if (p.copied) (void)hipEventDestroy(p.copied);
-    }
-    if (prev >= 0 && prev != c->cfg.device) (void)hipSetDevice(prev);
+    if (prev != device && hipSetDevice(device) != hipSuccess) prev = -1;   // no device: nothing was allocated
+    (void)hipDeviceSynchronize();         // nothing queued on the context's streams still runs while its members are released (ctx.hpp)
     delete c;
+    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
 }
 
 void* mgpu_alloc_host(size_t bytes) {
@@ -1206,15 +1183,13 @@ int mgpu_debug_spa_math(mgpu_ctx* c, const double* in, int n, double* tanh_out, 
     if (!c) return MGPU_ERR_ARG;
     return guard(c, [&] {
         need(in && tanh_out && atanh_out && n > 0, "bad argument");
-        double *d_in = nullptr, *d_t = nullptr, *d_a = nullptr;
-        HIPCK(hipMalloc(&d_in, size_t(n) * 8)); HIPCK(hipMalloc(&d_t, size_t(n) * 8)); HIPCK(hipMalloc(&d_a, size_t(n) * 8));
+        DevArray<double> d_in(size_t(n) * 8), d_t(size_t(n) * 8), d_a(size_t(n) * 8);
         HIPCK(hipMemcpy(d_in, in, size_t(n) * 8, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(mgpu_spa_math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_in, d_t, d_a, n);
         HIPCK(hipGetLastError());
         HIPCK(hipStreamSynchronize(c->stream));
         HIPCK(hipMemcpy(tanh_out, d_t, size_t(n) * 8, hipMemcpyDeviceToHost));
         HIPCK(hipMemcpy(atanh_out, d_a, size_t(n) * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_in); (void)hipFree(d_t); (void)hipFree(d_a);
     });
 }
 
@@ -1242,18 +1217,13 @@ int mgpu_rx_batch_taps(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, m
         const auto& t = c->tab;
         const size_t in_bytes = size_t(F) * t.frame_samples * 16;
         ensure_workspaces(c, WS_FRONTEND | WS_LLR | WS_OUT);
-        if (c->baseband_cap < in_bytes) {
-            (void)hipFree(c->d_baseband);
-            c->d_baseband = nullptr; c->baseband_cap = 0;
-            HIPCK(hipMalloc(&c->d_baseband, in_bytes));
-            c->baseband_cap = in_bytes;
-        }
+        c->d_baseband.grow(in_bytes);
         hipStream_t s = c->stream;
         HIPCK(hipMemcpyAsync(c->d_baseband, bb, in_bytes, hipMemcpyHostToDevice, s));
         MgpuTapsDev dt{};
-        std::vector<void*> tmp;
         const size_t G = size_t(t.Nsymb) * t.Nc;
-        auto dalloc = [&](size_t bytes) { void* p = nullptr; HIPCK(hipMalloc(&p, bytes)); tmp.push_back(p); return p; };
+        std::vector<DevBuf> tmp;             // the taps' device buffers, for this call
+        auto dalloc = [&](size_t bytes) { tmp.emplace_back(bytes); return tmp.back().p; };
         if (taps) {
             if (taps->grid) { dt.grid = static_cast<double*>(dalloc(F * G * 16)); if (t.mfsk_M > 0) HIPCK(hipMemsetAsync(dt.grid, 0, F * G * 16, s)); }
             need(t.mfsk_M == 0 || !(taps->H || taps->eq || taps->syms), "the MFSK modes have no channel estimate / equalised grid to tap");
@@ -1279,7 +1249,6 @@ int mgpu_rx_batch_taps(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, m
             back(taps->cycles, dt.cycles, 16 * 8);
         }
         HIPCK(hipStreamSynchronize(s));
-        for (void* p : tmp) (void)hipFree(p);
     });
 }
 
@@ -1296,9 +1265,9 @@ static int rx_one_frame(mgpu_ctx* c, const double* bb, uint8_t* payload, mgpu_fr
             // The graph bakes in every address it touches, so it reads from a device buffer and staging buffers of its own
             // that live as long as the context (d_baseband may be reallocated by a larger batch later; the max_batch-sized
             // workspaces never are). Nothing is published in the context until the whole graph exists.
-            if (!c->d_one_in) HIPCK(hipMalloc(&c->d_one_in, in_bytes));
-            if (!c->h_one_in) HIPCK(host_alloc_on_node(&c->h_one_in, in_bytes, c->numa_node));
-            if (!c->h_one_out) HIPCK(host_alloc_on_node(&c->h_one_out, out_bytes, c->numa_node));
+            c->d_one_in.grow(in_bytes);
+            if (!c->h_one_in) HIPCK(host_alloc_on_node(&c->h_one_in.h, in_bytes, c->numa_node));
+            if (!c->h_one_out) HIPCK(host_alloc_on_node(&c->h_one_out.h, out_bytes, c->numa_node));
             hipGraph_t graph = nullptr;
             HIPCK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             try {
@@ -1308,7 +1277,7 @@ static int rx_one_frame(mgpu_ctx* c, const double* bb, uint8_t* payload, mgpu_fr
                 launch_decoder(c, c->d_llr, 1, nullptr, nullptr, c->d_payload, c->d_stats, c->d_variance, c->d_snrvar, s);
                 launch_zf_snr(c, 1, c->d_payload, c->d_stats, s);
                 HIPCK(hipMemcpyAsync(c->h_one_out, c->d_payload, t.payload_stride, hipMemcpyDeviceToHost, s));
-                HIPCK(hipMemcpyAsync(static_cast<char*>(c->h_one_out) + t.payload_stride, c->d_stats, sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, s));
+                HIPCK(hipMemcpyAsync(static_cast<char*>(c->h_one_out.h) + t.payload_stride, c->d_stats, sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, s));
             } catch (...) {
                 (void)hipStreamEndCapture(s, &graph);
                 if (graph) (void)hipGraphDestroy(graph);
@@ -1319,13 +1288,13 @@ static int rx_one_frame(mgpu_ctx* c, const double* bb, uint8_t* payload, mgpu_fr
             const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
             HIPCK(e);
-            c->one_frame_graph = exec;
+            c->one_frame_graph.h = exec;
         }
         std::memcpy(c->h_one_in, bb, in_bytes);
         HIPCK(hipGraphLaunch(c->one_frame_graph, s));
         HIPCK(hipStreamSynchronize(s));
         if (payload) std::memcpy(payload, c->h_one_out, t.payload_stride);
-        if (stats) std::memcpy(stats, static_cast<char*>(c->h_one_out) + t.payload_stride, sizeof(MgpuStatsDev));
+        if (stats) std::memcpy(stats, static_cast<char*>(c->h_one_out.h) + t.payload_stride, sizeof(MgpuStatsDev));
     });
 }
 
@@ -1353,23 +1322,20 @@ static void rx_batch_pipelined(mgpu_ctx* c, const double* bb, int F, uint8_t* pa
     if (const char* e = std::getenv("MERCURY_RX_CHUNK")) chunk = std::max(1, std::atoi(e));
     chunk = std::min(chunk, F);
     for (auto& p : c->pipe) {
-        if (!p.stream) HIPCK(hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking));
-        if (!p.done) HIPCK(hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
-        if (!p.copied) HIPCK(hipEventCreateWithFlags(&p.copied, hipEventDisableTiming));
-        if (p.cap < size_t(chunk) * frame_bytes) {
+        if (!p.stream) HIPCK(hipStreamCreateWithFlags(&p.stream.h, hipStreamNonBlocking));
+        if (!p.done) HIPCK(hipEventCreateWithFlags(&p.done.h, hipEventDisableTiming));
+        if (!p.copied) HIPCK(hipEventCreateWithFlags(&p.copied.h, hipEventDisableTiming));
+        if (p.d_in.capacity() < size_t(chunk) * frame_bytes) {
             HIPCK(hipStreamSynchronize(p.stream));
-            (void)hipFree(p.d_in);
-            p.d_in = nullptr; p.cap = 0;
-            HIPCK(hipMalloc(&p.d_in, size_t(chunk) * frame_bytes));
-            p.cap = size_t(chunk) * frame_bytes;
+            p.d_in.grow(size_t(chunk) * frame_bytes);
         }
     }
     // Results come back through page-locked staging owned by the context: a device-to-host copy into the caller's pageable
     // arrays would block the host until the chunk's kernels have finished, i.e. before the next chunk's input copy could even
     // be queued, and nothing would overlap.
     const size_t out_bytes = size_t(c->max_batch) * (t.payload_stride + sizeof(MgpuStatsDev));
-    if (!c->h_out) HIPCK(host_alloc_on_node(&c->h_out, out_bytes + 16, c->numa_node));
-    uint8_t* h_payload = static_cast<uint8_t*>(c->h_out);
+    if (!c->h_out) HIPCK(host_alloc_on_node(&c->h_out.h, out_bytes + 16, c->numa_node));
+    uint8_t* h_payload = static_cast<uint8_t*>(c->h_out.h);
     MgpuStatsDev* h_stats = reinterpret_cast<MgpuStatsDev*>(h_payload + ((size_t(c->max_batch) * t.payload_stride + 15) & ~size_t(15)));
     MgpuTapsDev none{};
     // Two ways to overlap, chosen by the kind of host memory (measured on MI355X / PCIe Gen5, tools/bench_host_path.py):
@@ -1382,7 +1348,7 @@ static void rx_batch_pipelined(mgpu_ctx* c, const double* bb, int F, uint8_t* pa
     hipPointerAttribute_t attr{};
     const bool pinned = hipPointerGetAttributes(&attr, bb) == hipSuccess && attr.type == hipMemoryTypeHost;
     if (!pinned) (void)hipGetLastError();
-    for (auto& e : c->hp_ev) if (!e) HIPCK(hipEventCreate(&e));
+    for (auto& e : c->hp_ev) if (!e) HIPCK(hipEventCreate(&e.h));
     const int nchunks = (F + chunk - 1) / chunk;
     int k = 0;
     for (int off = 0; off < F; off += chunk, ++k) {

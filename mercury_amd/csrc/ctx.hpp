@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <cmath>
@@ -82,16 +84,58 @@ struct HipError : std::runtime_error { using std::runtime_error::runtime_error; 
         if (e_ != hipSuccess) throw HipError(std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+hipError_t host_alloc_on_node(void** p, size_t bytes, int node);   // api.hip
+int device_numa_node(int device);
+
+// Owning handles: move-only, released by the destructor (errors ignored), so that a throw on any path frees what was made before it.
+struct DevBuf {
+    void* p = nullptr;
+    void* view = nullptr;       // when set: page-locked host memory holding the buffer's current content, which kernels read in place
+    DevBuf() = default;
+    explicit DevBuf(size_t bytes) : cap(bytes ? bytes : 16) { HIPCK(hipMalloc(&p, cap)); }
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    template <typename T> T* as() { return static_cast<T*>(view ? view : p); }
+    size_t capacity() const { return cap; }
+    // a buffer that only grows: reallocated (old one freed first, content not kept) when smaller than `bytes`
+    void grow(size_t bytes) {
+        if (cap >= bytes) return;
+        *this = DevBuf();
+        *this = DevBuf(bytes);
+    }
+private:
+    size_t cap = 0;
+    void swap(DevBuf& o) noexcept { std::swap(p, o.p); std::swap(view, o.view); std::swap(cap, o.cap); }
+};
+// a DevBuf that reads as a T* (the context's workspaces and tables)
+template <typename T> struct DevArray : DevBuf {
+    using DevBuf::DevBuf;
+    operator T*() const { return static_cast<T*>(p); }
+};
+template <typename H, hipError_t (*Destroy)(H)> struct Handle {
+    H h = nullptr;              // created in place: HIPCK(hipStreamCreate(&s.h))
+    Handle() = default;
+    Handle(Handle&& o) noexcept { std::swap(h, o.h); }
+    Handle& operator=(Handle&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using GraphExec = Handle<hipGraphExec_t, hipGraphExecDestroy>;
+using PinnedBuf = Handle<void*, hipHostFree>;   // page-locked host memory from host_alloc_on_node
+
 template <typename T>
-T* upload(const std::vector<T>& v) {
-    T* d = nullptr;
-    HIPCK(hipMalloc(&d, v.size() * sizeof(T) + 16));
-    HIPCK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+DevArray<T> upload(const std::vector<T>& v) {
+    DevArray<T> d(v.size() * sizeof(T) + 16);
+    HIPCK(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return d;
 }
 
-hipError_t host_alloc_on_node(void** p, size_t bytes, int node);   // api.hip
-int device_numa_node(int device);
+struct Workspace;   // rxloop.hip
+struct TxState;     // tx.hip
+struct Release { void operator()(Workspace*) const; void operator()(TxState*) const; };   // defined where each type is complete
 
 }  // namespace mgpu_detail
 using namespace mgpu_detail;
@@ -101,55 +145,50 @@ struct mgpu_ctx {
     mgpu::ModeTables tab;
     MgpuDev dev{};
     LdpcDev ldev{};
-    std::vector<void*> owned;       // device allocations freed in destroy
+    std::vector<DevBuf> tables;     // the constant tables dev / ldev point into (keep())
     std::string err;
     int max_batch = 0;
     int numa_node = -1;             // the device's NUMA node (sysfs), -1 when the platform names none: page-locked staging is allocated there
+    // Release order: mgpu_destroy drains the device before it deletes the context, so no work queued on the streams below (or on a
+    // caller's stream with these buffers) is still running when the members are released; their order does not matter then.
+    Stream stream;                  // private stream for the host-buffer entry points
     // workspaces (device)
-    double* d_baseband = nullptr;   // lazily sized for the host-buffer entry points
-    size_t baseband_cap = 0;
-    float* d_llr = nullptr;
-    float* d_variance = nullptr;
-    float* d_snrvar = nullptr;
-    uint8_t* d_payload = nullptr;
-    MgpuStatsDev* d_stats = nullptr;
-    uint8_t* d_bits = nullptr;
-    double* d_eqdata = nullptr;
-    double* d_fir[2] = {nullptr, nullptr};   // FIR_rx_time_sync, FIR_rx_data taps
-    hipEvent_t sync_ev[2]{};        // around the most recent synchroniser kernel
-    float last_sync_ms = -1.f;     // [max_batch][nData] c128, zero-forcing modes only (post-decode SNR)
-    int* d_iters = nullptr;
+    DevArray<double> d_baseband;    // lazily sized for the host-buffer entry points
+    DevArray<float> d_llr, d_variance, d_snrvar;
+    DevArray<uint8_t> d_payload;
+    DevArray<MgpuStatsDev> d_stats;
+    DevArray<uint8_t> d_bits;
+    DevArray<double> d_eqdata;      // [max_batch][nData] c128, zero-forcing modes only (post-decode SNR)
+    double* d_fir[2] = {nullptr, nullptr};   // FIR_rx_time_sync, FIR_rx_data taps (in tables)
+    Event sync_ev[2];               // around the most recent synchroniser kernel
+    float last_sync_ms = -1.f;
+    DevArray<int> d_iters;
     // single-frame fast path of mgpu_rx_batch: the copy-in / front-end / decoder / copy-out sequence as one hipGraph
-    hipGraphExec_t one_frame_graph = nullptr;
-    double* d_one_in = nullptr;     // the graph's own one-frame device buffer (never reallocated: the graph holds its address)
-    void* h_one_in = nullptr;       // page-locked staging for one frame of samples
-    void* h_one_out = nullptr;      // page-locked staging for its payload + stats
-    void* rxloop_ws = nullptr;      // device workspace of mgpu_receive_byte_batch, kept between calls (rxloop.hip)
+    GraphExec one_frame_graph;
+    DevArray<double> d_one_in;      // the graph's own one-frame device buffer (never reallocated: the graph holds its address)
+    PinnedBuf h_one_in;             // page-locked staging for one frame of samples
+    PinnedBuf h_one_out;            // page-locked staging for its payload + stats
+    std::unique_ptr<Workspace, Release> rxloop_ws;   // device workspace of mgpu_receive_byte_batch, kept between calls (rxloop.hip)
     int rxloop_ws_windows = 0;
-    void (*rxloop_ws_free)(void*) = nullptr;
-    void* rb_stage = nullptr;       // mgpu_receive_byte_batch from host memory: landing area of the whole call's windows (uploaded by a helper thread)
-    size_t rb_stage_cap = 0;
-    void* rb_compact = nullptr;     // mgpu_receive_byte_batch_samples: the windows as INT32 / INT16 / FLOAT32 samples, before the widening kernel
-    size_t rb_compact_cap = 0;
-    hipStream_t rb_stream = nullptr;
-    double* d_mix_cs = nullptr;     // receive mixer: cos / sin of the carrier phase per sample index (host libm) for mix_carrier
+    DevArray<double> rb_stage;      // mgpu_receive_byte_batch from host memory: landing area of the whole call's windows (uploaded by a helper thread)
+    DevArray<char> rb_compact;      // mgpu_receive_byte_batch_samples: the windows as INT32 / INT16 / FLOAT32 samples, before the widening kernel
+    Stream rb_stream;
+    DevArray<double> d_mix_cs;      // receive mixer: cos / sin of the carrier phase per sample index (host libm) for mix_carrier
     double mix_carrier = -1;
-    size_t mix_count = 0, mix_cap = 0;
-    void* tx_state = nullptr;       // transmit path: preamble baseband, filter taps, carrier table (tx.hip)
+    size_t mix_count = 0;
+    std::unique_ptr<TxState, Release> tx_state;      // transmit path: preamble baseband, filter taps, carrier table (tx.hip)
     std::vector<double> pre_eq;     // [Nc][2] installed pre_equalization_channel (empty: none); dev.pre_eq is its device copy
-    double* d_pre_eq_buf = nullptr; // device copy of pre_eq (owned through keep())
+    DevArray<double> d_pre_eq_buf;  // device copy of pre_eq
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
-    void (*tx_state_free)(void*) = nullptr;
-    hipStream_t stream = nullptr;   // private stream for the host-buffer entry points
-    struct Pipe { hipStream_t stream = nullptr; hipEvent_t done = nullptr, copied = nullptr; double* d_in = nullptr; size_t cap = 0; };
-    void* h_out = nullptr;          // page-locked staging for the payloads + stats of a pipelined call ([max_batch])
+    struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
+    PinnedBuf h_out;                // page-locked staging for the payloads + stats of a pipelined call ([max_batch])
     static constexpr int kPipes = 2;
     Pipe pipe[kPipes];                   // the two chunk pipelines of the blocking host-buffer entry points (api.hip rx_batch_pipelined)
-    hipEvent_t hp_ev[4]{};               // call start, first chunk copied, last chunk copied, all done (host-path profile)
+    Event hp_ev[4];                      // call start, first chunk copied, last chunk copied, all done (host-path profile)
     int hp_chunk = 0, hp_nchunks = 0;    // the last pipelined call: frames per chunk, chunks
     float hp_fill_ms = 0, hp_drain_ms = 0, hp_total_ms = 0;
     static constexpr int kEvRing = 64;
-    hipEvent_t ev[kEvRing][4]{};    // per launch: front-end start/stop, decoder start/stop
+    Event ev[kEvRing][4];           // per launch: front-end start/stop, decoder start/stop
     bool timing = false;
     int ev_count = 0;               // launches recorded since timing was enabled (ring of kEvRing)
     bool ev_fe[kEvRing]{};          // whether the front-end ran in that slot
@@ -160,7 +199,7 @@ struct mgpu_ctx {
     int wave_of_wgs = 0;            // decoder workgroups that fill the device once (2 per compute unit); 0 = not asked yet
 
     template <typename T>
-    T* keep(T* p) { owned.push_back(p); return p; }
+    T* keep(const std::vector<T>& v) { tables.push_back(upload(v)); return static_cast<T*>(tables.back().p); }
 };
 
 
@@ -258,15 +297,6 @@ inline int guard(mgpu_ctx* c, const std::function<void()>& fn) {
     }
 }
 inline void need(bool ok, const char* what) { if (!ok) throw std::invalid_argument(what); }
-struct DevBuf {
-    void* p = nullptr;
-    void* view = nullptr;       // when set: page-locked host memory holding the buffer's current content, which kernels read in place
-    explicit DevBuf(size_t bytes) { HIPCK(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    template <typename T> T* as() { return static_cast<T*>(view ? view : p); }
-};
 // mfsk.cc:82-95, :120-126, :149-155; the universal ACK/BREAK patterns use M = 16, one stream centred in Nc = 50
 // (telecom_system.cc:3006), hop step 7, 8 tones sent twice.
 constexpr int kAckTones[8] = {4, 7, 5, 12, 13, 1, 9, 15}, kBreakTones[8] = {6, 14, 2, 3, 10, 8, 11, 15};

@@ -58,58 +58,59 @@ struct Win {                       // one capture window's walk through receive_
     bool in_loop = false, recovery_attempted = false, decoded = false;
 };
 
+}  // namespace
+
+namespace mgpu_detail {
+
 // Device workspace for W windows; allocated on the first call and kept in the context (hipMalloc / hipFree of several GB
 // per call cost more than the kernels). Rebuilt when a call brings more windows, so its streams and events cover every call.
 struct Workspace {
     DevBuf d_pass, d_bbi, d_frames, d_carrier, d_ia, d_ib, d_ic, d_vals, d_sum, d_cnt, d_freq, d_meanh, d_stats_k, d_payload_k, d_snr_k;
     size_t vals_per_window;
-    double* h_vals = nullptr;        // page-locked landing area for the synchroniser metrics (tens of MB per call)
+    PinnedBuf h_vals;                // page-locked landing area for the synchroniser metrics (tens of MB per call)
     // page-locked arena for the small index / result arrays of the control rounds: a copy from or to pageable memory holds the calling
     // thread for ~20-40 us each while the runtime stages it; from here the copies are queued back to back and the host moves on.
     // Bump-allocated; reset whenever the stream has been synchronised (everything queued before has completed by then).
-    char* h_pin = nullptr;
+    PinnedBuf h_pin;
     size_t pin_cap = 0, pin_off = 0;
     struct PendingDown { void* dst; const void* src; size_t bytes; };
     std::vector<PendingDown> pending;
     void* pin_take(size_t bytes) {
         const size_t need = (bytes + 63) & ~size_t(63);
         if (pin_off + need > pin_cap) return nullptr;
-        void* p = h_pin + pin_off;
+        void* p = static_cast<char*>(h_pin.h) + pin_off;
         pin_off += need;
         return p;
     }
-    hipStream_t side = nullptr;      // the signal-strength sum (a 92 k-term dependent chain per window) runs beside the synchroniser
-    hipStream_t copy = nullptr;      // brings the capture windows in, slice by slice, under the first kernels
-    hipStream_t search = nullptr;    // the coarse search of a group of slices, beside the mixer / filter of the next ones
-    std::vector<hipEvent_t> slice_ev, group_ev, we_ev;   // one per slice of windows
-    hipEvent_t ev_search = nullptr, ev_ready = nullptr, ev_done = nullptr;
-    ~Workspace() {
-        if (h_vals) (void)hipHostFree(h_vals);
-        if (h_pin) (void)hipHostFree(h_pin);
-        for (hipStream_t q : {side, copy, search}) if (q) (void)hipStreamDestroy(q);
-        for (const auto* v : {&slice_ev, &group_ev, &we_ev}) for (hipEvent_t e : *v) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_search, ev_ready, ev_done}) if (e) (void)hipEventDestroy(e);
-    }
+    Stream side;                     // the signal-strength sum (a 92 k-term dependent chain per window) runs beside the synchroniser
+    Stream copy;                     // brings the capture windows in, slice by slice, under the first kernels
+    Stream search;                   // the coarse search of a group of slices, beside the mixer / filter of the next ones
+    std::vector<Event> slice_ev, group_ev, we_ev;   // one per slice of windows
+    Event ev_search, ev_ready, ev_done;
     Workspace(int W, int buf, int frame_n, size_t vals_per_window, int payload_stride, int numa_node)
         : d_pass(size_t(W) * buf * 8), d_bbi(size_t(W) * buf * 16), d_frames(size_t(W) * frame_n * 16), d_carrier(size_t(W) * 8),
           d_ia(size_t(W) * 128 * 4), d_ib(size_t(W) * 128 * 4), d_ic(size_t(W) * 4), d_vals(size_t(W) * vals_per_window * 8),
           d_sum(size_t(W) * 128 * 8), d_cnt(size_t(W) * 128 * 4), d_freq(size_t(W) * 16), d_meanh(size_t(W) * 8),
           d_stats_k(size_t(W) * sizeof(MgpuStatsDev)), d_payload_k(size_t(W) * payload_stride), d_snr_k(size_t(W) * 8), vals_per_window(vals_per_window) {
-        HIPCK(host_alloc_on_node(reinterpret_cast<void**>(&h_vals), size_t(W) * vals_per_window * 8, numa_node));      // control rounds' results: on the GPU's NUMA node
+        HIPCK(host_alloc_on_node(&h_vals.h, size_t(W) * vals_per_window * 8, numa_node));      // control rounds' results: on the GPU's NUMA node
         pin_cap = std::max<size_t>(size_t(1) << 20, size_t(W) * 128 * 8 * 6);             // a few rounds of the largest index / result arrays
-        HIPCK(host_alloc_on_node(reinterpret_cast<void**>(&h_pin), pin_cap, numa_node));
-        HIPCK(hipStreamCreate(&side));
-        HIPCK(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
-        HIPCK(hipStreamCreateWithFlags(&search, hipStreamNonBlocking));
+        HIPCK(host_alloc_on_node(&h_pin.h, pin_cap, numa_node));
+        HIPCK(hipStreamCreate(&side.h));
+        HIPCK(hipStreamCreateWithFlags(&copy.h, hipStreamNonBlocking));
+        HIPCK(hipStreamCreateWithFlags(&search.h, hipStreamNonBlocking));
         const int nsl = (W + kSlice - 1) / kSlice;
         for (auto* v : {&slice_ev, &group_ev, &we_ev}) {
-            v->assign(nsl, nullptr);
-            for (hipEvent_t& e : *v) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            v->resize(nsl);
+            for (Event& e : *v) HIPCK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
         }
-        for (hipEvent_t* e : {&ev_search, &ev_ready, &ev_done}) HIPCK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (Event* e : {&ev_search, &ev_ready, &ev_done}) HIPCK(hipEventCreateWithFlags(&e->h, hipEventDisableTiming));
     }
 };
-void free_workspace(void* p) { delete static_cast<Workspace*>(p); }
+void Release::operator()(Workspace* p) const { delete p; }
+
+}  // namespace mgpu_detail
+
+namespace {
 
 struct Loop {
     PhaseTimer pt;
@@ -136,15 +137,13 @@ struct Loop {
     static Workspace& workspace(mgpu_ctx* ctx, int W, int buffer_nsymb) {
         const auto& t = ctx->tab;
         if (!ctx->rxloop_ws || ctx->rxloop_ws_windows < W) {
-            if (ctx->rxloop_ws) free_workspace(ctx->rxloop_ws);
-            ctx->rxloop_ws = nullptr;
+            ctx->rxloop_ws.reset();
             const int buf = t.Nofdm * buffer_nsymb * kInterp, sym = t.Nofdm * kInterp;
             const size_t vals = size_t(std::max(buf / kCoarseStep + 2, 4 * sym + 2));       // coarse / fine candidate counts
-            ctx->rxloop_ws = new Workspace(W, buf, t.Nofdm * (t.Nsymb + t.preamble), vals, t.payload_stride, ctx->numa_node);
+            ctx->rxloop_ws.reset(new Workspace(W, buf, t.Nofdm * (t.Nsymb + t.preamble), vals, t.payload_stride, ctx->numa_node));
             ctx->rxloop_ws_windows = W;
-            ctx->rxloop_ws_free = free_workspace;
         }
-        return *static_cast<Workspace*>(ctx->rxloop_ws);
+        return *ctx->rxloop_ws;
     }
 
     Loop(mgpu_ctx* ctx, int W_, const mgpu_receive_config& rc_, int buffer_nsymb, mgpu_link_state* state_ = nullptr, uint8_t* payload_ = nullptr,
@@ -275,7 +274,7 @@ struct Loop {
             down_async(delay.data(), ws.d_cnt, size_t(n) * 4);
             down(corr.data(), ws.d_sum, size_t(n) * 8);
         } else {         // a few windows: one lane per window would crawl through its candidates; the host is quicker
-            const double* vals = ws.h_vals;
+            const double* vals = static_cast<const double*>(ws.h_vals.h);
             down(ws.h_vals, ws.d_vals, size_t(n) * ncmax * 8);
             for (int k = 0; k < n; ++k) select_peak(&vals[size_t(k) * ncmax], nc[k], step, size[k], loc[k], ntrials, &delay[k], &corr[k]);
         }
@@ -836,15 +835,6 @@ void launch_widen(const void* d_in, int fmt, size_t n, double* d_out, hipStream_
     else hipLaunchKernelGGL(mgpu_widen_capture_kernel<float>, grid, block, 0, s, static_cast<const float*>(d_in), n, 1.0, d_out);
     HIPCK(hipGetLastError());
 }
-// a device buffer of the context that only grows (its content is not kept)
-void grow(void*& p, size_t& cap, size_t bytes) {
-    if (cap >= bytes) return;
-    (void)hipFree(p);
-    p = nullptr; cap = 0;
-    HIPCK(hipMalloc(&p, bytes));
-    cap = bytes;
-}
-
 // The sub-batches [offset, count) a pipelined host call is cut into. Doubles are upload-bound (the synchroniser of a sub-batch is over before
 // the next one has landed): equal pieces of 256, so that little is left to do behind the last byte. Compact samples (4 or 2 bytes each) land
 // two to four times faster than they are processed, and every receive_byte_impl call pays its control rounds' fixed ~1.5 ms whatever its size:
@@ -873,8 +863,8 @@ std::vector<std::pair<int, int>> pieces(int W, int fmt) {
 // windows [off, off + n) of the host capture into the staging buffer as doubles (compact samples: copied, then widened), waited for
 hipError_t upload_piece(mgpu_ctx* c, const char* src, int fmt, size_t buf, int off, int n) {
     const size_t sb = sample_bytes(fmt);
-    double* stage = static_cast<double*>(c->rb_stage) + size_t(off) * buf;
-    void* dst = fmt == MGPU_SAMPLES_F64 ? static_cast<void*>(stage) : static_cast<char*>(c->rb_compact) + size_t(off) * buf * sb;
+    double* stage = c->rb_stage + size_t(off) * buf;
+    void* dst = fmt == MGPU_SAMPLES_F64 ? static_cast<void*>(stage) : c->rb_compact + size_t(off) * buf * sb;
     hipError_t e = hipMemcpyAsync(dst, src + size_t(off) * buf * sb, size_t(n) * buf * sb, hipMemcpyHostToDevice, c->rb_stream);
     if (e == hipSuccess && fmt != MGPU_SAMPLES_F64) {
         try { launch_widen(dst, fmt, size_t(n) * buf, stage, c->rb_stream); }
@@ -906,26 +896,26 @@ void receive_byte_any(mgpu_ctx* c, const void* capture, int fmt, int W, const mg
     const size_t buf = size_t(t.Nofdm) * mgpu_receive_buffer_nsymb(c) * kInterp;
     const size_t sb = sample_bytes(fmt);
     const char* src = static_cast<const char*>(capture);
-    if (!c->rb_stream) HIPCK(hipStreamCreateWithFlags(&c->rb_stream, hipStreamNonBlocking));
+    if (!c->rb_stream) HIPCK(hipStreamCreateWithFlags(&c->rb_stream.h, hipStreamNonBlocking));
     const int kMinSub = 256;
     if (on_device || no_pipe || W < 2 * kMinSub) {
         if (fmt == MGPU_SAMPLES_F64) { receive_byte_impl(c, static_cast<const double*>(capture), W, rcp, state, payload, stats); return; }
         // compact samples, one piece: (upload,) widen into the staging buffer, then the doubles path on device memory
-        grow(c->rb_stage, c->rb_stage_cap, size_t(W) * buf * 8);
+        c->rb_stage.grow(size_t(W) * buf * 8);
         const void* d_in = capture;
         if (!on_device) {
-            grow(c->rb_compact, c->rb_compact_cap, size_t(W) * buf * sb);
+            c->rb_compact.grow(size_t(W) * buf * sb);
             HIPCK(hipMemcpyAsync(c->rb_compact, capture, size_t(W) * buf * sb, hipMemcpyHostToDevice, c->rb_stream));
             d_in = c->rb_compact;
         }
-        launch_widen(d_in, fmt, size_t(W) * buf, static_cast<double*>(c->rb_stage), c->rb_stream);
+        launch_widen(d_in, fmt, size_t(W) * buf, c->rb_stage, c->rb_stream);
         HIPCK(hipStreamSynchronize(c->rb_stream));
-        receive_byte_impl(c, static_cast<const double*>(c->rb_stage), W, rcp, state, payload, stats);
+        receive_byte_impl(c, c->rb_stage, W, rcp, state, payload, stats);
         return;
     }
     const std::vector<std::pair<int, int>> ps = pieces(W, fmt);
-    grow(c->rb_stage, c->rb_stage_cap, size_t(W) * buf * 8);
-    if (fmt != MGPU_SAMPLES_F64) grow(c->rb_compact, c->rb_compact_cap, size_t(W) * buf * sb);
+    c->rb_stage.grow(size_t(W) * buf * 8);
+    if (fmt != MGPU_SAMPLES_F64) c->rb_compact.grow(size_t(W) * buf * sb);
     std::mutex m;
     std::condition_variable cv;
     int landed = 0;
@@ -951,7 +941,7 @@ void receive_byte_any(mgpu_ctx* c, const void* capture, int fmt, int W, const mg
                 cv.wait(lk, [&] { return landed > j || failed != hipSuccess; });
                 if (failed != hipSuccess) break;
             }
-            receive_byte_impl(c, static_cast<const double*>(c->rb_stage) + size_t(off) * buf, n, rcp, state ? state + off : nullptr,
+            receive_byte_impl(c, c->rb_stage + size_t(off) * buf, n, rcp, state ? state + off : nullptr,
                               payload + size_t(off) * t.payload_stride, stats + off);
         }
     } catch (...) {

@@ -166,40 +166,35 @@ extern "C" __global__ __launch_bounds__(256) void mgpu_fir97_kernel(const double
 
 using namespace mgpu_detail;
 
-namespace {
+namespace mgpu_detail {
 
 // per-context transmit state: preamble baseband, filter taps and carrier table for the last carrier / phase origin used
 struct TxState {
-    double* d_pre_bb = nullptr;
+    DevArray<double> d_pre_bb;
     double carrier = -1;
-    double* d_fir[2] = {nullptr, nullptr};
+    DevArray<double> d_fir[2];
     int ntaps[2] = {0, 0};
-    double* d_cs = nullptr;
-    size_t cs_cap = 0;
+    DevArray<double> d_cs;
     int pre_eq_version = 0;                             // the context's pre_eq_version d_pre_bb was built with
-    double* d_tx_buffer = nullptr;                      // passband_data_tx_buffer: 3 frames of unfiltered audio carried between the
+    DevArray<double> d_tx_buffer;                       // passband_data_tx_buffer: 3 frames of unfiltered audio carried between the
                                                         // FIRST / MIDDLE / FLUSH_MESSAGE calls (telecom_system.cc:559-590); zero at first
-    void* d_work[3] = {nullptr, nullptr, nullptr};      // data baseband, clipped passband, first filter's output: grown on demand, kept
-    size_t work_cap[3] = {0, 0, 0};
+    DevBuf d_work[3];                                   // data baseband, clipped passband, first filter's output: grown on demand, kept
     void* work(int i, size_t bytes, hipStream_t s) {
-        if (work_cap[i] < bytes) {
+        if (d_work[i].capacity() < bytes) {
             HIPCK(hipStreamSynchronize(s));
-            (void)hipFree(d_work[i]);
-            d_work[i] = nullptr; work_cap[i] = 0;
-            HIPCK(hipMalloc(&d_work[i], bytes));
-            work_cap[i] = bytes;
+            d_work[i].grow(bytes);
         }
-        return d_work[i];
+        return d_work[i].p;
     }
     double cs_carrier = -1;
     uint64_t cs_start = 0;
     size_t cs_count = 0;
-    ~TxState() {
-        (void)hipFree(d_pre_bb); (void)hipFree(d_fir[0]); (void)hipFree(d_fir[1]); (void)hipFree(d_cs); (void)hipFree(d_tx_buffer);
-        for (void* p : d_work) (void)hipFree(p);
-    }
 };
-void free_tx_state(void* p) { delete static_cast<TxState*>(p); }
+void Release::operator()(TxState* p) const { delete p; }
+
+}  // namespace mgpu_detail
+
+namespace {
 
 void launch_symbol_mod(mgpu_ctx* c, const double* d_carriers, int n, double* d_out, hipStream_t s) {
     hipLaunchKernelGGL(mgpu_symbol_mod_kernel, dim3((n + 3) / 4), dim3(256), 0, s, c->dev.twiddle, d_carriers, n, d_out);
@@ -223,21 +218,19 @@ void build_preamble_baseband(mgpu_ctx* c, TxState* st, hipStream_t s) {
 }
 
 TxState& tx_state(mgpu_ctx* c, hipStream_t s) {
-    if (c->tx_state && static_cast<TxState*>(c->tx_state)->pre_eq_version != c->pre_eq_version)
-        build_preamble_baseband(c, static_cast<TxState*>(c->tx_state), s);
+    if (c->tx_state && c->tx_state->pre_eq_version != c->pre_eq_version) build_preamble_baseband(c, c->tx_state.get(), s);
     if (!c->tx_state) {
-        std::unique_ptr<TxState> st(new TxState);            // published in the context only once it is complete
+        std::unique_ptr<TxState, Release> st(new TxState);   // published in the context only once it is complete
         const auto& t = c->tab;
-        HIPCK(hipMalloc(reinterpret_cast<void**>(&st->d_pre_bb), size_t(t.preamble) * t.Nofdm * 16));
+        st->d_pre_bb = DevArray<double>(size_t(t.preamble) * t.Nofdm * 16);
         build_preamble_baseband(c, st.get(), s);
         const size_t total = size_t(t.Nofdm) * (t.Nsymb + t.preamble) * 4;
-        HIPCK(hipMalloc(reinterpret_cast<void**>(&st->d_tx_buffer), 3 * total * 8));
+        st->d_tx_buffer = DevArray<double>(3 * total * 8);
         HIPCK(hipMemsetAsync(st->d_tx_buffer, 0, 3 * total * 8, s));
         HIPCK(hipStreamSynchronize(s));
-        c->tx_state = st.release();
-        c->tx_state_free = free_tx_state;
+        c->tx_state = std::move(st);
     }
-    return *static_cast<TxState*>(c->tx_state);
+    return *c->tx_state;
 }
 
 // carrier table from the host libm, as the reference evaluates it: cos / sin(2*M_PI*fc*(double)n*Ts), n from start_sample.
@@ -257,12 +250,8 @@ const double* ensure_carrier_table(TxState& st, double carrier_hz, uint64_t star
         ::sincos(2 * M_PI * carrier_hz * double(k) * Ts, &cs[2 * n + 1], &cs[2 * n]);
     }
     HIPCK(hipStreamSynchronize(s));                      // nothing in flight still reads the old table
-    if (st.cs_cap < cs.size()) {
-        (void)hipFree(st.d_cs);
-        st.d_cs = nullptr; st.cs_cap = 0; st.cs_count = 0;
-        HIPCK(hipMalloc(reinterpret_cast<void**>(&st.d_cs), cs.size() * 8));
-        st.cs_cap = cs.size();
-    }
+    st.cs_count = 0;                                     // no table until the new one is in place
+    st.d_cs.grow(cs.size() * 8);
     HIPCK(hipMemcpy(st.d_cs, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
     st.cs_carrier = carrier_hz; st.cs_start = start_sample; st.cs_count = build;
     return st.d_cs;
@@ -286,11 +275,10 @@ void transmit_dev(mgpu_ctx* c, const uint8_t* d_payload, int payload_stride, con
     const double* const d_cs = ensure_carrier_table(st, cfg.carrier_hz, cfg.start_sample, continuous ? size_t(used) * F : size_t(used), s);
     if (filtered && st.carrier != cfg.carrier_hz) {
         HIPCK(hipStreamSynchronize(s));
+        st.carrier = -1;                                 // no taps until both are in place
         for (int w = 0; w < 2; ++w) {
             const std::vector<double> taps = mgpu::design_tx_fir(w, cfg.carrier_hz);
-            (void)hipFree(st.d_fir[w]);
-            st.d_fir[w] = nullptr;
-            HIPCK(hipMalloc(reinterpret_cast<void**>(&st.d_fir[w]), taps.size() * 8));
+            st.d_fir[w].grow(taps.size() * 8);
             HIPCK(hipMemcpy(st.d_fir[w], taps.data(), taps.size() * 8, hipMemcpyHostToDevice));
             st.ntaps[w] = int(taps.size());
             need(st.ntaps[w] == FIR97_NT, "transmit filter design changed: the filter kernel is built for 97 taps");
@@ -404,7 +392,7 @@ int mgpu_set_pre_equalization_channel(mgpu_ctx* c, const double* channel_c128) {
         HIPCK(hipDeviceSynchronize());
         if (channel_c128) {
             c->pre_eq.assign(channel_c128, channel_c128 + 2 * size_t(c->tab.Nc));
-            if (!c->d_pre_eq_buf) c->d_pre_eq_buf = c->keep(upload(c->pre_eq));
+            if (!c->d_pre_eq_buf) c->d_pre_eq_buf = upload(c->pre_eq);
             else HIPCK(hipMemcpy(c->d_pre_eq_buf, c->pre_eq.data(), c->pre_eq.size() * 8, hipMemcpyHostToDevice));
             c->dev.pre_eq = c->d_pre_eq_buf;
         } else {

@@ -58,6 +58,14 @@ def test_explicit_parameters_are_validated_before_any_device_work():
         rc = lib.mgpu_create_explicit(C.byref(good), C.byref(xp), C.byref(h))
         assert rc == want and not h.value, (rc, want)
         assert lib.mgpu_last_error(None)
+    # geometries whose bits fit mode 0's codeword but not the front-end's interpolation table (a front-end LDS carve over 160 KiB
+    # is refused too, but no geometry inside the table's limits reaches one)
+    bpsk = Config(0, 50, 1, 1, 1, 0, 16, 0.0)
+    for xp in (ExplicitParams(0.0, 0, 0, 0, 0, 0, 0, 0, 0, 20, 33),     # Dy = 20 over 33 symbols: columns 13..39 hold fewer than two pilots
+               ExplicitParams(0.0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 61)):     # Dy = 2 over 61 symbols: 1525 pilots, the table indexes at most 1023
+        rc = lib.mgpu_create_explicit(C.byref(bpsk), C.byref(xp), C.byref(h))
+        assert rc == 3 and not h.value, rc
+        assert b"interpolation table" in lib.mgpu_last_error(None)
 
 
 def test_bad_arguments_return_error_codes():

@@ -1255,3 +1255,45 @@ def test_baseband_test_esn0_counts_match_the_oracle_frame_for_frame(cfg):
         assert abs(r["avg_iterations"] * n - it) < 1e-6 and r["BER"] == be / (n * nreal) and r["FER"] == fe / n
     assert res[0]["Error_frames_total"] > 0 and res[2]["Error_frames_total"] <= res[0]["Error_frames_total"]      # a curve, not a constant
     rx.close()
+
+
+def test_closing_a_context_releases_everything_it_made():
+    """mgpu_destroy releases every resource of a context, the lazily created ones included (max_batch workspaces, the one-frame graph and its
+    staging, the pipelined host path's streams / buffers / page-locked staging, the stage-tap buffers, receive_byte's workspace, upload
+    staging and mixer table, the transmit state): eight cycles of create / use each once / close leave the device's free memory where it was."""
+    import gc
+    import torch
+    from mercury_amd.physical_layer import pinned_empty
+    from oraclelib import CARRIER
+    W, F = 512, 64                  # 512 windows: receive_byte from host memory takes the pipelined upload (rb_stage / rb_compact)
+
+    def free_hbm():
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        return torch.cuda.mem_get_info()[0]
+
+    rng = np.random.default_rng(SEED)
+    pb = rng.standard_normal((W, 1)) * 0.01
+    first = free_hbm()
+    for cycle in range(8):
+        rx = _rx(8, max_batch=W)
+        bb = (rng.standard_normal((F, rx.frame_samples)) + 1j * rng.standard_normal((F, rx.frame_samples))) * 0.1
+        pinned = pinned_empty(bb.shape, np.complex128)
+        pinned[...] = bb
+        rx.receive(bb[:1])                                   # F = 1: the captured graph
+        rx.receive(bb)                                       # F > 1, pageable: pipelined
+        rx.receive(pinned)                                   # F > 1, page-locked: pipelined on the other schedule
+        rx.receive(bb[:2], taps=True)
+        passband = np.broadcast_to(pb, (W, rx.receive_buffer_samples())) * rng.standard_normal(rx.receive_buffer_samples())
+        rx.receive_byte((passband * 32768).astype(np.int16), CARRIER)          # host memory, compact samples
+        d_pass = torch.from_numpy(np.ascontiguousarray(passband)).cuda()
+        rx.receive_byte_dev(d_pass.data_ptr(), W, CARRIER)                     # device memory
+        rx.transmit_byte(np.zeros((2, rx.payload_stride), np.uint8), CARRIER)
+        rx.passband_to_baseband(passband[:2], CARRIER)
+        del d_pass, pinned
+        in_use = first - free_hbm()
+        rx.close()
+        assert in_use >= 1 << 30, in_use                     # the context did hold its workspaces
+        after = free_hbm()
+        assert abs(after - first) < 256 << 20, (cycle, first, after)
