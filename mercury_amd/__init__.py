@@ -5,12 +5,12 @@ declared in ``include/mercury_gpu.h``), ``data/`` (the LDPC graphs as compact de
 ``physical_layer.py`` (a ctypes loader mirroring the reference's physical_layer surface), ``shm.py`` (the
 shared-memory ring decoded payloads are published through, ``include/mercury_shm.h``).
 """
-from .physical_layer import (DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_SPA_FAST, EXPORTED_SYMBOLS, HF_CHANNEL_SYMBOLS, HF_PRESETS, LIB_PATH, HfChannel,
-                             MgpuError, RxPhy, RxPool, STATS_DTYPE, device_props, hf_channel_preset, host_hf_channel_draws, host_hf_channel_taps,
+from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_SPA_FAST, EXPORTED_SYMBOLS, HF_CHANNEL_SYMBOLS, HF_PRESETS, LIB_PATH, HfChannel,
+                             MgpuError, RxCapture, RxPhy, RxPool, STATS_DTYPE, device_props, hf_channel_preset, host_hf_channel_draws, host_hf_channel_taps,
                              host_hilbert_taps, load_library, pool_shard)
 
 from .shm import ShmRing  # noqa: E402
 
-__all__ = ["ShmRing", "RxPhy", "RxPool", "pool_shard", "MgpuError", "DEC_GBF", "DEC_SPA", "DEC_MINSUM", "DEC_SPA_FAST", "STATS_DTYPE", "load_library",
+__all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_shard", "MgpuError", "DEC_GBF", "DEC_SPA", "DEC_MINSUM", "DEC_SPA_FAST", "STATS_DTYPE", "load_library",
            "LIB_PATH", "EXPORTED_SYMBOLS", "device_props", "HfChannel", "HF_PRESETS", "HF_CHANNEL_SYMBOLS", "hf_channel_preset", "host_hilbert_taps",
            "host_hf_channel_draws", "host_hf_channel_taps"]

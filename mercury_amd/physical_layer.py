@@ -889,3 +889,141 @@ class RxPool:
         stats = np.zeros(W, RECEIVE_STATS_DTYPE)
         self._ck(self.lib.mgpu_pool_receive_byte_batch(self.h, src, C.c_int(W), C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
         return {"payload": payload, "stats": stats, "state": st}
+
+
+# ---- the receive loop over continuous captures (include/mercury_capture.h) ------------------------------------------------------------
+CAPTURE_SYMBOLS = ["mgpu_capture_create", "mgpu_capture_destroy", "mgpu_capture_geometry_get", "mgpu_capture_feed", "mgpu_capture_process",
+                   "mgpu_capture_run", "mgpu_capture_get_state", "mgpu_capture_set_state", "mgpu_capture_window", "mgpu_host_capture_prep",
+                   "mgpu_host_capture_process", "mgpu_host_capture_init_state"]
+CAPTURE_HELD_DTYPE = np.dtype([("iterations_done", "<i4"), ("message_decoded", "<i4"), ("crc", "<i4"), ("all_zeros", "<i4"), ("delay", "<i4"),
+                               ("sync_trials", "<i4"), ("frame_overflow_symbols", "<i4"), ("snr_db", "<f8"), ("freq_offset", "<f8"),
+                               ("coarse_metric", "<f8"), ("signal_strength_dbm", "<f8")], align=True)
+CAPTURE_STATE_DTYPE = np.dtype([("frames_to_read", "<i4"), ("n_under", "<i4"), ("data_ready", "<i4"), ("mfsk_search_raw", "<i4"),
+                                ("link", LINK_STATE_DTYPE), ("held", CAPTURE_HELD_DTYPE)], align=True)
+CAPTURE_EVENT_DTYPE = np.dtype([("capture", "<i4"), ("hop", "<i4"), ("stats", RECEIVE_STATS_DTYPE)], align=True)
+SAMPLE_FORMATS = {np.dtype(np.float64): 0, np.dtype(np.int32): 1, np.dtype(np.int16): 2, np.dtype(np.float32): 3}
+
+
+class CaptureGeometry(C.Structure):     # mgpu_capture_geometry
+    _fields_ = [("buffer_nsymb", C.c_int), ("nsymb", C.c_int), ("preamble_nsymb", C.c_int), ("symbol_period", C.c_int), ("mfsk", C.c_int)]
+
+
+def _sample_format(dtype):
+    fmt = SAMPLE_FORMATS.get(np.dtype(dtype))
+    if fmt is None:
+        raise MgpuError("capture samples are float64, int32, int16 or float32, not %s" % np.dtype(dtype))
+    return fmt
+
+
+def host_capture_init_state(geometry):
+    """the state a capture starts with (mgpu_host_capture_init_state)"""
+    st = np.zeros((), CAPTURE_STATE_DTYPE)
+    if load_library().mgpu_host_capture_init_state(C.byref(geometry), _ptr(st)) != 0:
+        raise MgpuError("mgpu_host_capture_init_state: bad geometry")
+    return st
+
+
+def host_capture_prep(geometry, window, samples, state):
+    """one hop of capture prep (audioio.c:1035-1057) on a host window, in place: window float64 [buffer samples], samples [P] of a sample
+    format, state a CAPTURE_STATE_DTYPE scalar array (updated)"""
+    x = np.ascontiguousarray(samples)
+    assert window.dtype == np.float64 and window.flags.c_contiguous and window.size == geometry.buffer_nsymb * geometry.symbol_period
+    assert x.size == geometry.symbol_period and state.dtype == CAPTURE_STATE_DTYPE
+    if load_library().mgpu_host_capture_prep(C.byref(geometry), _ptr(window), _ptr(x), C.c_int(_sample_format(x.dtype)), _ptr(state)) != 0:
+        raise MgpuError("mgpu_host_capture_prep: bad argument")
+
+
+def host_capture_process(geometry, state, stats=None, link=None):
+    """the process step's bookkeeping (telecom_system.cc:2304-2377) given receive_byte's result on the window (stats: RECEIVE_STATS_DTYPE
+    scalar, link: LINK_STATE_DTYPE scalar as receive_byte left it; only read when the step runs receive_byte). Returns whether it did."""
+    r = None if stats is None else np.ascontiguousarray(stats, RECEIVE_STATS_DTYPE)
+    ls = None if link is None else np.ascontiguousarray(link, LINK_STATE_DTYPE)
+    rc = load_library().mgpu_host_capture_process(C.byref(geometry), _ptr(state), _ptr(r), _ptr(ls))
+    if rc < 0:
+        raise MgpuError("mgpu_host_capture_process: bad argument (%d)" % rc)
+    return bool(rc)
+
+
+class RxCapture:
+    """S continuous captures on one RxPhy context: the reference's capture-prep thread and RX_SHM_process_main, batched on the GPU
+    (include/mercury_capture.h). Samples go in as [S, H * P] arrays of float64 / int32 / int16 / float32 (numpy, or torch tensors on the
+    context's device, read in place)."""
+
+    def __init__(self, rx, S, carrier_hz, trials_max=2, use_last_good_time_sync=1, use_last_good_freq_offset=1, coarse_freq_sync=0,
+                 initial_windows=None, max_hops=0):
+        self.rx, self.lib, self.S = rx, rx.lib, S
+        self.h = C.c_void_p()
+        cfg = ReceiveConfig(carrier_hz, trials_max, use_last_good_time_sync, use_last_good_freq_offset, coarse_freq_sync)
+        init = None
+        if initial_windows is not None:
+            init = np.ascontiguousarray(initial_windows, np.float64).reshape(S, -1)
+        rx._ck(self.lib.mgpu_capture_create(rx.h, C.c_int(S), C.byref(cfg), _ptr(init), C.c_int(max_hops), C.byref(self.h)))
+        self.geometry = CaptureGeometry()
+        rx._ck(self.lib.mgpu_capture_geometry_get(self.h, C.byref(self.geometry)))
+        self.P = self.geometry.symbol_period
+        self.window_samples = self.geometry.buffer_nsymb * self.P
+        self.payload_stride = rx.payload_stride
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.mgpu_capture_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _samples(self, samples):
+        """-> (pointer, format, H, keep-alive)"""
+        if hasattr(samples, "data_ptr"):                   # a device tensor
+            import torch
+            fmt = {torch.float64: 0, torch.int32: 1, torch.int16: 2, torch.float32: 3}.get(samples.dtype)
+            if fmt is None or not samples.is_contiguous():
+                raise MgpuError("device samples: a contiguous float64 / int32 / int16 / float32 tensor")
+            n = samples.numel()
+            ptr, keep = C.c_void_p(samples.data_ptr()), samples
+        else:
+            x = np.ascontiguousarray(samples)
+            fmt, n, ptr, keep = _sample_format(x.dtype), x.size, _ptr(x), x
+        if n % (self.S * self.P):
+            raise MgpuError("samples must be [S, H * P] with P = %d" % self.P)
+        return ptr, fmt, n // (self.S * self.P), keep
+
+    def feed(self, samples):
+        ptr, fmt, H, _keep = self._samples(samples)
+        self.rx._ck(self.lib.mgpu_capture_feed(self.h, ptr, C.c_int(fmt), C.c_int(H)))
+
+    def process(self):
+        """-> dict(ran [S] bool, stats [S] RECEIVE_STATS_DTYPE, payload [S, stride]); stats / payload are zero where ran is False"""
+        ran = np.zeros(self.S, np.int32)
+        stats = np.zeros(self.S, RECEIVE_STATS_DTYPE)
+        payload = np.zeros((self.S, self.payload_stride), np.uint8)
+        self.rx._ck(self.lib.mgpu_capture_process(self.h, _ptr(ran), _ptr(stats), _ptr(payload)))
+        return {"ran": ran.astype(bool), "stats": stats, "payload": payload}
+
+    def run(self, samples, max_events=None):
+        """H rounds of feed(1) + process() -> list of (capture, hop, stats, payload bytes) for the decoded frames, in order of hop, then capture"""
+        ptr, fmt, H, _keep = self._samples(samples)
+        m = self.S * H if max_events is None else max_events
+        ev = np.zeros(m, CAPTURE_EVENT_DTYPE)
+        pl = np.zeros((m, self.payload_stride), np.uint8)
+        n = C.c_int()
+        self.rx._ck(self.lib.mgpu_capture_run(self.h, ptr, C.c_int(fmt), C.c_int(H), _ptr(ev), _ptr(pl), C.c_int(m), C.byref(n)))
+        nb = self.rx.payload_bytes
+        return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
+
+    def state(self, s):
+        st = np.zeros((), CAPTURE_STATE_DTYPE)
+        self.rx._ck(self.lib.mgpu_capture_get_state(self.h, C.c_int(s), _ptr(st)))
+        return st
+
+    def set_state(self, s, st):
+        st = np.ascontiguousarray(st, CAPTURE_STATE_DTYPE)
+        self.rx._ck(self.lib.mgpu_capture_set_state(self.h, C.c_int(s), _ptr(st)))
+
+    def window(self, s):
+        out = np.zeros(self.window_samples)
+        self.rx._ck(self.lib.mgpu_capture_window(self.h, C.c_int(s), _ptr(out)))
+        return out
