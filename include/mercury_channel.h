@@ -70,6 +70,33 @@ int mgpu_hf_channel_apply(mgpu_ctx* ctx, const mgpu_hf_channel* ch, const void* 
 int mgpu_hf_channel_apply_dev(mgpu_ctx* ctx, const mgpu_hf_channel* ch, const void* d_in, int complex_input, double fs, int W, int n,
                               uint64_t seed, uint64_t realisation0, long long t0, void* d_out, void* stream);
 
+/* ---- streaming form -------------------------------------------------------------------------------------------
+ * A stateful channel for S real signals that are fed in chunks, so that a long run needs memory for one chunk only and a chunk edge is
+ * no discontinuity. Let x_s be everything fed to signal s, placed from the seek position on and zero before it, and y_s the output
+ * defined above for real input, t0 = 0 and realisation realisation0 + s, taken on the unbounded signal (the Hilbert FIR sees the real
+ * neighbours at a chunk edge). The output at absolute position T is
+ *
+ *   o_s[T] = y_s[T - L] + noise_amp[s] * g(seed, s, T)          (y_s[u] = 0 for u < 0),   L = mgpu_hf_stream_latency() = 256
+ *
+ * The Hilbert FIR reaches 215 samples ahead, so some latency is unavoidable; 256 keeps the kernel's 64-sample blocks aligned with
+ * absolute time, and chunks whose edges lie on multiples of 64 give, bit for bit, the doubles one piece gives (and those
+ * mgpu_hf_channel_apply gives on the whole signal). g is a standard normal draw of Philox stream 5 whose counter carries the signal index
+ * and all 64 bits of T (mgpu_host_hf_stream_noise is its host twin). noise_amp == NULL adds nothing and draws nothing. The identity
+ * channel returns its input delayed by L, bit for bit. A stream belongs to its context and is destroyed before it. */
+typedef struct mgpu_hf_stream mgpu_hf_stream;
+int mgpu_hf_stream_create(mgpu_ctx* ctx, const mgpu_hf_channel* ch, double fs, int S, uint64_t seed, uint64_t realisation0, mgpu_hf_stream** out);
+int mgpu_hf_stream_destroy(mgpu_hf_stream* st);
+/* position: a multiple of 64; the history becomes zeros. A new stream is at 0. */
+int mgpu_hf_stream_seek(mgpu_hf_stream* st, uint64_t position);
+int mgpu_hf_stream_latency(mgpu_hf_stream* st);
+/* n more samples of every signal, n a positive multiple of 64 (else MGPU_ERR_ARG and nothing changes): [S][n] doubles in, [S][n] out, no
+ * aliasing. noise_amp: NULL or [S] host doubles. Host buffers, blocking. */
+int mgpu_hf_stream_apply(mgpu_hf_stream* st, const double* in, int n, const double* noise_amp, double* out);
+/* the same on device buffers, enqueued on `stream` (NULL: the context's stream), asynchronous; d_in is read until the call's work is done */
+int mgpu_hf_stream_apply_dev(mgpu_hf_stream* st, const void* d_in, int n, const double* noise_amp, void* d_out, void* stream);
+/* host only: g(seed, signal, position + i) for i < n */
+int mgpu_host_hf_stream_noise(uint64_t seed, int signal, uint64_t position, int n, double* out);
+
 /* mgpu_passband_test_esn0 (mercury_rxloop.h) with the channel between the transmitter and the noise: each capture window (randomly
  * picked leading samples, the frame, zeros behind it) goes through the channel at 48 kHz, realisation = frame number, t0 = 0, and then
  * gets the same noise samples mgpu_passband_test_esn0 adds. The MFSK modes keep their sigma calibrated on the transmitted power and

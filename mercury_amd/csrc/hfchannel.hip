@@ -1,10 +1,13 @@
 // Watterson HF fading channel (CCIR Rec. 520 / ITU-R F.1487) for the self-simulations: model and C-ABI in include/mercury_channel.h,
-// definition and cost model in DESIGN.md §6.1. Four kernels share one body:
+// definition and cost model in DESIGN.md §6.1 (§6.2 for the streaming form). Five kernels share one body:
 //   mgpu_hf_channel_real_kernel      real signals [W][n] (analytic signal through the Hilbert FIR, Re() of the output)
 //   mgpu_hf_channel_complex_kernel   complex signals [W][n]
 //   mgpu_hf_passband_kernel          the capture windows of passband_test_esn0 built on the fly (mgpu_passband_channel_kernel's leading
 //                                    random picks, the frame, zeros) -> channel -> the same Philox stream-3 noise sample that kernel adds
 //   mgpu_hf_baseband_kernel          clean 12 kHz frames of the generator -> channel -> the generator's stream-1 noise, (x/16 + a n) 16
+//   mgpu_hf_stream_kernel            real signals fed in chunks (mgpu_hf_stream_*): the input is a per-signal history tail followed by the
+//                                    chunk, the output is delayed by HF_LATENCY samples and gets Philox stream-5 noise keyed by the 64-bit
+//                                    absolute position
 // One workgroup = one tile of HF_TILE output samples of one signal. The tile's input plus its halo (the largest path delay behind it,
 // for real input also the Hilbert FIR's half length on both sides) is staged in LDS once. Tap gains are not interpolated: sinusoid m of
 // path k at sample i0 + 64 b + l is A[b][m] * E[m][l & 7] * F[m][l >> 3], with the anchor A (one sincos per 64-sample block) and the
@@ -16,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../include/mercury_channel.h"
@@ -30,13 +34,15 @@
 #define HF_HILBERT_HALF 215                     // Hilbert FIR: offsets -215..215 (431 taps), non-zero at odd offsets only
 #define HF_HILBERT_ODD 108
 #define HF_STREAM 4u                            // Philox stream id of the channel draws (philox.h)
+#define HF_NOISE_STREAM 5u                      // Philox stream id of the streaming channel's noise
+#define HF_LATENCY 256                          // streaming form: output delay in samples (>= HF_HILBERT_HALF, a multiple of HF_BLK)
 #define HF_MAX_FS 192000.0
 
 namespace {
 
 struct cd { double re, im; };
 
-enum { HF_REAL = 0, HF_COMPLEX = 1, HF_PASSBAND = 2, HF_BASEBAND = 3 };
+enum { HF_REAL = 0, HF_COMPLEX = 1, HF_PASSBAND = 2, HF_BASEBAND = 3, HF_STREAMING = 4 };
 
 // everything the kernels need of a channel, resolved on the host: integer delays, normalised amplitudes (1/sqrt(N) included)
 struct HfPlan {
@@ -55,6 +61,11 @@ struct HfIo {
     int n, w0;          // samples per signal; first signal of this launch
     int total, delay;   // HF_PASSBAND: audio samples per frame, frame position in the window
     double noise;       // HF_PASSBAND: ampl (awgn.cc:68); HF_BASEBAND: noise_amp per component
+    // HF_STREAMING: in is the chunk [W][n]; output sample i is the channel's output at chunk sample i - HF_LATENCY
+    const double* hist;         // [W][nh] the nh samples fed before the chunk (zeros where nothing was fed)
+    const double* noise_amp;    // NULL (no noise, no draws) or [W]
+    int nh, fed;                // history length; samples fed since the seek before this chunk (clamped): older input is zero
+    uint64_t pos;               // absolute position of the chunk's first sample
 };
 
 // ---- host: the definitions ------------------------------------------------------------------------------------------------------
@@ -153,6 +164,11 @@ size_t lds_bytes(const HfPlan& p, bool real_in) {
 // input sample i of signal w (zero outside [0, n)); HF_PASSBAND builds mgpu_passband_channel_kernel's window before its noise
 template <int MODE>
 __device__ __forceinline__ cd source(const HfPlan& pl, const HfIo& io, int w, int i) {
+    if (MODE == HF_STREAMING) {                 // chunk sample i - HF_LATENCY: from the history tail when it lies before the chunk
+        const int j = i - HF_LATENCY;
+        if (j >= io.n || j < -io.nh) return {0.0, 0.0};
+        return {j < 0 ? io.hist[size_t(w) * io.nh + (io.nh + j)] : io.in[size_t(w) * io.n + j], 0.0};
+    }
     if (i < 0 || i >= io.n) return {0.0, 0.0};
     if (MODE == HF_REAL) return {io.in[size_t(w) * io.n + i], 0.0};
     if (MODE == HF_COMPLEX || MODE == HF_BASEBAND) {
@@ -172,6 +188,17 @@ template <int MODE>
 __device__ __forceinline__ void emit(const HfPlan& pl, const HfIo& io, int w, int i, cd y) {
     if (MODE == HF_REAL) { io.out[size_t(w) * io.n + i] = y.re; return; }
     if (MODE == HF_COMPLEX) { double* o = io.out + 2 * (size_t(w) * io.n + i); o[0] = y.re; o[1] = y.im; return; }
+    if (MODE == HF_STREAMING) {                // noise keyed by (signal, 64-bit absolute position): no wrap at 2^32 samples
+        double v = y.re;
+        if (io.noise_amp) {
+            const uint64_t T = io.pos + uint64_t(i);
+            uint32_t q[4];
+            philox4x32(pl.seed, uint32_t(T), HF_NOISE_STREAM, uint32_t(T >> 32), uint32_t(w), q);
+            v += io.noise_amp[w] * gauss_bm(q[0], q[1]);
+        }
+        io.out[size_t(w) * io.n + i] = v;
+        return;
+    }
     const uint64_t fr = pl.real0 + uint64_t(w);
     uint32_t r[4];
     if (MODE == HF_PASSBAND) {                 // mgpu_passband_channel_kernel's noise: stream 3, counter (sample, frame)
@@ -188,7 +215,7 @@ __device__ __forceinline__ void emit(const HfPlan& pl, const HfIo& io, int w, in
 
 template <int MODE>
 __device__ __forceinline__ void hf_body(const HfPlan& pl, const HfIo& io) {
-    constexpr bool kReal = MODE == HF_REAL || MODE == HF_PASSBAND;
+    constexpr bool kReal = MODE == HF_REAL || MODE == HF_PASSBAND || MODE == HF_STREAMING;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int w = io.w0 + int(blockIdx.y), i0 = int(blockIdx.x) * HF_TILE;
@@ -229,7 +256,8 @@ __device__ __forceinline__ void hf_body(const HfPlan& pl, const HfIo& io) {
         for (int j = tid; j < na; j += HF_THREADS) {
             const int i = base + j;
             cd v = {0.0, 0.0};
-            if (i >= 0 && i < io.n) {
+            // the analytic signal exists where the signal does: [0, n), or from the seek position on for a stream
+            if (MODE == HF_STREAMING ? i - HF_LATENCY + io.fed >= 0 : i >= 0 && i < io.n) {
                 const double* c = xr + j + HF_HILBERT_HALF;
                 double h = 0.0;
 #pragma unroll
@@ -306,15 +334,26 @@ extern "C" __global__ __launch_bounds__(HF_THREADS) void mgpu_hf_channel_real_ke
 extern "C" __global__ __launch_bounds__(HF_THREADS) void mgpu_hf_channel_complex_kernel(HfPlan pl, HfIo io) { hf_body<HF_COMPLEX>(pl, io); }
 extern "C" __global__ __launch_bounds__(HF_THREADS) void mgpu_hf_passband_kernel(HfPlan pl, HfIo io) { hf_body<HF_PASSBAND>(pl, io); }
 extern "C" __global__ __launch_bounds__(HF_THREADS) void mgpu_hf_baseband_kernel(HfPlan pl, HfIo io) { hf_body<HF_BASEBAND>(pl, io); }
+extern "C" __global__ __launch_bounds__(HF_THREADS) void mgpu_hf_stream_kernel(HfPlan pl, HfIo io) { hf_body<HF_STREAMING>(pl, io); }
+
+// the history of the next chunk: the last nh samples of (old history, chunk). grid: x over nh, y over signals
+extern "C" __global__ __launch_bounds__(256) void mgpu_hf_stream_roll_kernel(const double* __restrict__ old_hist, const double* __restrict__ in, int nh,
+                                                                             int n, double* __restrict__ new_hist) {
+    const size_t w = blockIdx.y;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nh; j += gridDim.x * blockDim.x) {
+        const long long q = (long long)j + n;
+        new_hist[w * nh + j] = q < nh ? old_hist[w * nh + q] : in[w * n + (q - nh)];
+    }
+}
 
 namespace {
 
 void launch(int mode, const HfPlan& pl, HfIo io, int W, hipStream_t s) {
-    const bool real_in = mode == HF_REAL || mode == HF_PASSBAND;
+    const bool real_in = mode == HF_REAL || mode == HF_PASSBAND || mode == HF_STREAMING;
     const size_t lds = pl.identity ? 0 : lds_bytes(pl, real_in);
     const unsigned tiles = unsigned((io.n + HF_TILE - 1) / HF_TILE);
     auto* k = mode == HF_REAL ? mgpu_hf_channel_real_kernel : mode == HF_COMPLEX ? mgpu_hf_channel_complex_kernel
-            : mode == HF_PASSBAND ? mgpu_hf_passband_kernel : mgpu_hf_baseband_kernel;
+            : mode == HF_PASSBAND ? mgpu_hf_passband_kernel : mode == HF_BASEBAND ? mgpu_hf_baseband_kernel : mgpu_hf_stream_kernel;
     for (int w0 = 0; w0 < W; w0 += 65535) {
         io.w0 = w0;
         hipLaunchKernelGGL(k, dim3(tiles, unsigned(std::min(W - w0, 65535))), dim3(HF_THREADS), lds, s, pl, io);
@@ -323,6 +362,43 @@ void launch(int mode, const HfPlan& pl, HfIo io, int W, hipStream_t s) {
 }
 
 }  // namespace
+
+// S signals fed in chunks (include/mercury_channel.h): the plan, the absolute position and, on the device, the last `nh` input samples of
+// every signal in one of two arrays (a chunk reads one and the roll kernel writes the other, so a chunk shorter than the history is safe)
+struct mgpu_hf_stream {
+    mgpu_ctx* c = nullptr;
+    HfPlan pl{};
+    int S = 0, nh = 0, cur = 0;
+    uint64_t pos = 0, start = 0;          // next input sample; the seek position (input before it is zero)
+    DevArray<double> hist[2];             // [S][nh] each
+    DevArray<double> d_noise;             // [S]
+    std::vector<double> noise;            // what d_noise holds (empty: nothing uploaded yet)
+    DevBuf d_in, d_out;                   // mgpu_hf_stream_apply's device copies
+
+    void apply(const double* d_x, int n, const double* noise_amp, double* d_y, hipStream_t s) {
+        if (noise_amp && (noise.empty() || std::memcmp(noise.data(), noise_amp, size_t(S) * 8) != 0)) {
+            HIPCK(hipStreamSynchronize(s));                 // no chunk in flight still reads the old amplitudes
+            noise.assign(noise_amp, noise_amp + S);
+            HIPCK(hipMemcpy(d_noise, noise.data(), size_t(S) * 8, hipMemcpyHostToDevice));
+        }
+        HfPlan p = pl;
+        p.t0 = (long long)(pos) - HF_LATENCY;               // anchor time of output block b of tile i0: pos - L + i0 + 64 b
+        HfIo io{d_x, d_y, n, 0, 0, 0, 0.0};
+        io.hist = hist[cur];
+        io.noise_amp = noise_amp ? static_cast<const double*>(d_noise) : nullptr;
+        io.nh = nh;
+        io.fed = int(std::min<uint64_t>(pos - start, uint64_t(1) << 24));
+        io.pos = pos;
+        launch(HF_STREAMING, p, io, S, s);
+        for (int w0 = 0; w0 < S; w0 += 65535) {
+            hipLaunchKernelGGL(mgpu_hf_stream_roll_kernel, dim3(unsigned((nh + 255) / 256), unsigned(std::min(S - w0, 65535))), dim3(256), 0, s,
+                               hist[cur] + size_t(w0) * nh, d_x + size_t(w0) * n, nh, n, hist[cur ^ 1] + size_t(w0) * nh);
+            HIPCK(hipGetLastError());
+        }
+        cur ^= 1;
+        pos += uint64_t(n);
+    }
+};
 
 namespace mgpu_detail {
 
@@ -402,6 +478,84 @@ int mgpu_host_hf_channel_taps(const mgpu_hf_channel* ch, double fs, uint64_t see
         }
     }
     return MGPU_OK;
+}
+
+int mgpu_host_hf_stream_noise(uint64_t seed, int signal, uint64_t position, int n, double* out) {
+    if (!out || n < 0 || signal < 0) return MGPU_ERR_ARG;
+    for (int i = 0; i < n; ++i) {
+        const uint64_t T = position + uint64_t(i);
+        uint32_t q[4];
+        philox4x32(seed, uint32_t(T), HF_NOISE_STREAM, uint32_t(T >> 32), uint32_t(signal), q);
+        out[i] = gauss_bm(q[0], q[1]);
+    }
+    return MGPU_OK;
+}
+
+int mgpu_hf_stream_create(mgpu_ctx* c, const mgpu_hf_channel* ch, double fs, int S, uint64_t seed, uint64_t realisation0, mgpu_hf_stream** out) {
+    if (!c || !out) return MGPU_ERR_ARG;
+    *out = nullptr;
+    return guard(c, [&] {
+        const HfPlan pl = make_plan(ch, fs, 0, seed, realisation0);
+        need(S >= 1 && S <= (1 << 22), "bad argument (S: 1..2^22)");
+        std::unique_ptr<mgpu_hf_stream> k(new mgpu_hf_stream);
+        k->c = c;
+        k->pl = pl;
+        k->S = S;
+        k->nh = HF_LATENCY + pl.dmax + HF_HILBERT_HALF;
+        for (auto& h : k->hist) {
+            h = DevArray<double>(size_t(S) * k->nh * 8);
+            HIPCK(hipMemsetAsync(h, 0, size_t(S) * k->nh * 8, c->stream));
+        }
+        k->d_noise = DevArray<double>(size_t(S) * 8);
+        HIPCK(hipStreamSynchronize(c->stream));
+        *out = k.release();
+    });
+}
+
+int mgpu_hf_stream_destroy(mgpu_hf_stream* k) {
+    if (!k) return MGPU_ERR_ARG;
+    mgpu_ctx* c = k->c;
+    return guard(c, [&] {
+        HIPCK(hipDeviceSynchronize());          // chunks may be queued on a caller's stream
+        delete k;
+    });
+}
+
+int mgpu_hf_stream_latency(mgpu_hf_stream* k) { return k ? HF_LATENCY : MGPU_ERR_ARG; }
+
+int mgpu_hf_stream_seek(mgpu_hf_stream* k, uint64_t position) {
+    if (!k) return MGPU_ERR_ARG;
+    return guard(k->c, [&] {
+        need(position % HF_BLK == 0, "the seek position must be a multiple of 64");
+        HIPCK(hipDeviceSynchronize());
+        HIPCK(hipMemset(k->hist[k->cur], 0, size_t(k->S) * k->nh * 8));
+        k->pos = k->start = position;
+    });
+}
+
+int mgpu_hf_stream_apply_dev(mgpu_hf_stream* k, const void* d_in, int n, const double* noise_amp, void* d_out, void* stream) {
+    if (!k) return MGPU_ERR_ARG;
+    return guard(k->c, [&] {
+        need(d_in && d_out && d_in != d_out, "bad argument (in and out must be given and may not alias)");
+        need(n > 0 && n % HF_BLK == 0, "n must be a positive multiple of 64");
+        k->apply(static_cast<const double*>(d_in), n, noise_amp, static_cast<double*>(d_out), stream ? static_cast<hipStream_t>(stream) : k->c->stream);
+    });
+}
+
+int mgpu_hf_stream_apply(mgpu_hf_stream* k, const double* in, int n, const double* noise_amp, double* out) {
+    if (!k) return MGPU_ERR_ARG;
+    return guard(k->c, [&] {
+        need(in && out && in != out, "bad argument (in and out must be given and may not alias)");
+        need(n > 0 && n % HF_BLK == 0, "n must be a positive multiple of 64");
+        const size_t bytes = size_t(k->S) * n * 8;
+        hipStream_t s = k->c->stream;
+        k->d_in.grow(bytes);
+        k->d_out.grow(bytes);
+        HIPCK(hipMemcpyAsync(k->d_in.p, in, bytes, hipMemcpyHostToDevice, s));
+        k->apply(k->d_in.as<double>(), n, noise_amp, k->d_out.as<double>(), s);
+        HIPCK(hipMemcpyAsync(out, k->d_out.p, bytes, hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+    });
 }
 
 int mgpu_hf_channel_apply_dev(mgpu_ctx* c, const mgpu_hf_channel* ch, const void* d_in, int complex_input, double fs, int W, int n,

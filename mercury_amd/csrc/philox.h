@@ -1,7 +1,8 @@
 // Philox4x32-10 and the Box-Muller draw of the library's random streams. One definition for every kernel that draws
 // from them, so that two kernels drawing the same (seed, counter) get the same bits; the host twin serves the host-only reference
 // functions (the integer part is exact on both sides, the Box-Muller transcendentals agree to rounding).
-// Stream ids (second counter word): 0 payload bytes, 1 baseband noise, 2 static echo phase, 3 passband noise, 4 HF channel draws.
+// Stream ids (second counter word): 0 payload bytes, 1 baseband noise, 2 static echo phase, 3 passband noise, 4 HF channel draws,
+// 5 streaming HF channel noise, 6 link simulator schedule, 7 link simulator payloads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

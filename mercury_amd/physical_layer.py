@@ -131,6 +131,10 @@ HF_MAX_PATHS, HF_SINUSOIDS = 4, 32
 HF_PRESETS = {"awgn": 0, "good": 1, "moderate": 2, "poor": 3, "flutter": 4}
 HF_CHANNEL_SYMBOLS = ["mgpu_hf_channel_preset", "mgpu_host_hilbert_taps", "mgpu_host_hf_channel_draws", "mgpu_host_hf_channel_taps",
                       "mgpu_hf_channel_apply", "mgpu_hf_channel_apply_dev", "mgpu_passband_test_esn0_hf", "mgpu_baseband_test_esn0_hf"]
+# the streaming form in the same header (HfStream below)
+HF_STREAM_SYMBOLS = ["mgpu_hf_stream_create", "mgpu_hf_stream_destroy", "mgpu_hf_stream_seek", "mgpu_hf_stream_latency", "mgpu_hf_stream_apply",
+                     "mgpu_hf_stream_apply_dev", "mgpu_host_hf_stream_noise"]
+HF_CHANNEL_SYMBOLS += HF_STREAM_SYMBOLS
 
 
 class HfChannel(C.Structure):
@@ -1027,3 +1031,187 @@ class RxCapture:
         out = np.zeros(self.window_samples)
         self.rx._ck(self.lib.mgpu_capture_window(self.h, C.c_int(s), _ptr(out)))
         return out
+
+
+# ---- streaming HF channel (include/mercury_channel.h) ----------------------------------------------------------------
+def host_hf_stream_noise(seed, signal, position, n):
+    """g(seed, signal, position + i), i < n: the streaming channel's unit noise (host-only twin, no GPU)."""
+    out = np.zeros(n)
+    lib = load_library()
+    lib.mgpu_host_hf_stream_noise.argtypes = [C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
+    if lib.mgpu_host_hf_stream_noise(seed, signal, position, n, _ptr(out)) != 0:
+        raise MgpuError("mgpu_host_hf_stream_noise: bad argument")
+    return out
+
+
+class HfStream:
+    """The Watterson channel on S real signals that are fed in chunks (mgpu_hf_stream_*): apply() takes float64 [S, n] (numpy, or a torch
+    tensor on the context's device, then `out` must be one too), n a multiple of 64, and returns the next n output samples of every
+    signal, delayed by `latency` samples."""
+
+    def __init__(self, rx, S, ch, seed, realisation0=0, fs=48000.0):
+        self.rx, self.lib, self.S = rx, rx.lib, S
+        self.h = C.c_void_p()
+        lib = self.lib
+        lib.mgpu_hf_stream_create.argtypes = [C.c_void_p, C.POINTER(HfChannel), C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
+        lib.mgpu_hf_stream_destroy.argtypes = [C.c_void_p]
+        lib.mgpu_hf_stream_seek.argtypes = [C.c_void_p, C.c_uint64]
+        lib.mgpu_hf_stream_latency.argtypes = [C.c_void_p]
+        lib.mgpu_hf_stream_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.mgpu_hf_stream_apply_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        rx._ck(lib.mgpu_hf_stream_create(rx.h, C.byref(_hf(ch)), fs, S, seed, realisation0, C.byref(self.h)))
+        self.latency = int(lib.mgpu_hf_stream_latency(self.h))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.mgpu_hf_stream_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_hf_stream_seek(self.h, position))
+
+    def apply(self, x, noise_amp=None, out=None, stream=None):
+        na = None if noise_amp is None else np.ascontiguousarray(noise_amp, np.float64).reshape(self.S)
+        if hasattr(x, "data_ptr"):                         # device tensors, asynchronous on `stream` (None: the context's stream)
+            import torch
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.numel() % self.S:
+                raise MgpuError("device samples: a contiguous float64 tensor [S, n]")
+            out = torch.empty_like(x) if out is None else out
+            self.rx._ck(self.lib.mgpu_hf_stream_apply_dev(self.h, x.data_ptr(), x.numel() // self.S, _ptr(na), out.data_ptr(), stream))
+            return out
+        a = np.ascontiguousarray(x, np.float64).reshape(self.S, -1)
+        out = np.empty_like(a) if out is None else out
+        self.rx._ck(self.lib.mgpu_hf_stream_apply(self.h, _ptr(a), a.shape[1], _ptr(na), _ptr(out)))
+        return out
+
+
+# ---- link simulator (include/mercury_linksim.h) --------------------------------------------------------------------------------------
+LINKSIM_SYMBOLS = ["mgpu_linksim_create", "mgpu_linksim_destroy", "mgpu_linksim_run", "mgpu_linksim_counters_get", "mgpu_linksim_capture",
+                   "mgpu_linksim_noise_amp", "mgpu_host_linksim_frame_start", "mgpu_host_linksim_payload"]
+LINKSIM_COUNTERS_DTYPE = np.dtype([("hops", "<i8"), ("frames_sent", "<i8"), ("delivered", "<i8"), ("duplicates", "<i8"), ("false_decodes", "<i8"),
+                                   ("iterations_sum", "<i8"), ("snr_db_sum", "<f8")], align=True)
+
+
+class LinkSimConfig(C.Structure):       # mgpu_linksim_config
+    _fields_ = [("struct_size", C.c_int), ("S", C.c_int), ("gap_hops", C.c_int), ("max_hops", C.c_int), ("seed", C.c_uint64),
+                ("channel", HfChannel), ("rx", ReceiveConfig), ("tx", TransmitConfig)]
+
+
+def linksim_config(S, carrier_hz, seed, channel="awgn", gap_hops=0, max_hops=0, output_power_watt=0.1, trials_max=2, use_last_good_time_sync=1,
+                   use_last_good_freq_offset=1, coarse_freq_sync=0, message_location=SINGLE_MESSAGE, start_sample=0):
+    """An mgpu_linksim_config with the reference's transmit and receive defaults around the given carrier."""
+    k = LinkSimConfig()
+    k.struct_size, k.S, k.gap_hops, k.max_hops, k.seed = C.sizeof(LinkSimConfig), S, gap_hops, max_hops, seed
+    k.channel = _hf(channel)
+    k.rx = ReceiveConfig(carrier_hz, trials_max, use_last_good_time_sync, use_last_good_freq_offset, coarse_freq_sync)
+    k.tx = TransmitConfig(carrier_hz, float(np.sqrt(2.0)), output_power_watt, 7.0, 10.0, start_sample, message_location, 0)
+    return k
+
+
+def host_linksim_frame_start(config, frame_samples, symbol_period, link, frame):
+    """transmit position of frame `frame` of link `link` (host only)"""
+    out = C.c_longlong()
+    lib = load_library()
+    lib.mgpu_host_linksim_frame_start.argtypes = [C.POINTER(LinkSimConfig), C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
+    if lib.mgpu_host_linksim_frame_start(C.byref(config), frame_samples, symbol_period, link, frame, C.byref(out)) != 0:
+        raise MgpuError("mgpu_host_linksim_frame_start: bad argument")
+    return out.value
+
+
+def host_linksim_payload(seed, link, frame, nbytes):
+    """the payload link `link` sends in its frame `frame`: uint8 [nbytes] (host only)"""
+    out = np.zeros(nbytes, np.uint8)
+    lib = load_library()
+    lib.mgpu_host_linksim_payload.argtypes = [C.c_uint64, C.c_int, C.c_longlong, C.c_int, C.c_void_p]
+    if lib.mgpu_host_linksim_payload(seed, link, frame, nbytes, _ptr(out)) != 0:
+        raise MgpuError("mgpu_host_linksim_payload: bad argument")
+    return out
+
+
+class _BorrowedCapture(RxCapture):
+    """the capture inside a LinkSim: state() and window() of RxCapture on a handle the simulator owns"""
+
+    def __init__(self, rx, handle, S):
+        self.rx, self.lib, self.S, self.h = rx, rx.lib, S, handle
+        self.geometry = CaptureGeometry()
+        rx._ck(self.lib.mgpu_capture_geometry_get(self.h, C.byref(self.geometry)))
+        self.P = self.geometry.symbol_period
+        self.window_samples = self.geometry.buffer_nsymb * self.P
+        self.payload_stride = rx.payload_stride
+
+    def close(self):
+        self.h = C.c_void_p()
+
+
+class LinkSim:
+    """S simplex links (transmitter -> streaming HF channel -> noise -> the capture receive loop) on one RxPhy context
+    (include/mercury_linksim.h). config: linksim_config(...); esn0_db: None (no noise), a number or [S]."""
+
+    def __init__(self, rx, config, esn0_db=None):
+        self.rx, self.lib, self.S, self.config = rx, rx.lib, config.S, config
+        self.h = C.c_void_p()
+        lib = self.lib
+        lib.mgpu_linksim_create.argtypes = [C.c_void_p, C.POINTER(LinkSimConfig), C.c_void_p, C.POINTER(C.c_void_p)]
+        lib.mgpu_linksim_destroy.argtypes = [C.c_void_p]
+        lib.mgpu_linksim_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+        lib.mgpu_linksim_counters_get.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mgpu_linksim_capture.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        es = None if esn0_db is None else np.ascontiguousarray(np.broadcast_to(np.asarray(esn0_db, np.float64), (self.S,)))
+        self.esn0_db = es
+        rx._ck(lib.mgpu_linksim_create(rx.h, C.byref(config), _ptr(es), C.byref(self.h)))
+        cap = C.c_void_p()
+        rx._ck(lib.mgpu_linksim_capture(self.h, C.byref(cap)))
+        self.capture = _BorrowedCapture(rx, cap, self.S)
+        self.P = self.capture.P
+        self.frame_samples = rx.transmit_frame_samples()
+        self.slot = self.frame_samples + config.gap_hops * self.P
+        self.payload_stride = rx.payload_stride
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.capture.close()
+            self.lib.mgpu_linksim_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, H, want_samples=False, max_events=None):
+        """H more hops for every link -> list of (link, hop since the start, stats, payload bytes) for the decoded frames; with
+        want_samples also the audio the captures were fed, float64 [S, H * P]"""
+        m = self.S * H if max_events is None else max_events
+        ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
+        pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
+        n = C.c_int()
+        audio = np.zeros((self.S, H * self.P)) if want_samples else None
+        self.rx._ck(self.lib.mgpu_linksim_run(self.h, C.c_int(H), _ptr(ev), _ptr(pl), C.c_int(m), C.byref(n), _ptr(audio)))
+        nb = self.rx.payload_bytes
+        events = [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
+        return (events, audio) if want_samples else events
+
+    def counters(self):
+        out = np.zeros(self.S, LINKSIM_COUNTERS_DTYPE)
+        self.rx._ck(self.lib.mgpu_linksim_counters_get(self.h, _ptr(out)))
+        return out
+
+    def noise_amp(self):
+        """the streaming channel's noise amplitude per link (zeros without noise)"""
+        out = np.zeros(self.S)
+        self.lib.mgpu_linksim_noise_amp.argtypes = [C.c_void_p, C.c_void_p]
+        self.rx._ck(self.lib.mgpu_linksim_noise_amp(self.h, _ptr(out)))
+        return out
+
+    def frame_start(self, link, frame):
+        return host_linksim_frame_start(self.config, self.frame_samples, self.P, link, frame)
+
+    def payload(self, link, frame):
+        return host_linksim_payload(self.config.seed, link, frame, self.rx.payload_bytes)
