@@ -21,29 +21,11 @@
 
 namespace {
 
-constexpr int kInterp = 4;
 constexpr int kDefaultHops = 16;
-
-bool on_device(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice) return true;
-    (void)hipGetLastError();
-    return false;
-}
-
-bool known_format(int fmt) {
-    return fmt == MGPU_SAMPLES_F64 || fmt == MGPU_SAMPLES_INT32 || fmt == MGPU_SAMPLES_INT16 || fmt == MGPU_SAMPLES_F32;
-}
-size_t sample_bytes(int fmt) { return fmt == MGPU_SAMPLES_F64 ? 8 : fmt == MGPU_SAMPLES_INT16 ? 2 : 4; }
 
 // the capture thread's widening (audioio.c:893-936), as mgpu_widen_capture_kernel does it
 double widen(const void* samples, int fmt, size_t i) {
-    switch (fmt) {
-        case MGPU_SAMPLES_INT32: return double(static_cast<const int32_t*>(samples)[i]) / 2147483647.0;
-        case MGPU_SAMPLES_INT16: return double(static_cast<const int16_t*>(samples)[i]) / 32768.0;
-        case MGPU_SAMPLES_F32: return double(static_cast<const float*>(samples)[i]);
-        default: return static_cast<const double*>(samples)[i];
-    }
+    return with_samples(fmt, samples, [i](auto* in, double divisor) { return divisor == 1.0 ? double(in[i]) : double(in[i]) / divisor; });
 }
 
 bool good_geometry(const mgpu_capture_geometry* g) {
@@ -191,14 +173,10 @@ struct mgpu_capture {
             const dim3 grid(gx, unsigned(ns)), block(256);
             double* r = ring + size_t(k0) * cap;
             const char* in = src + size_t(k0) * stride * sb;
-            if (fmt == MGPU_SAMPLES_INT32)
-                hipLaunchKernelGGL(mgpu_capture_feed_kernel<int32_t>, grid, block, 0, s(), reinterpret_cast<const int32_t*>(in), stride, int(row), 2147483647.0, r, cap, pos0);
-            else if (fmt == MGPU_SAMPLES_INT16)
-                hipLaunchKernelGGL(mgpu_capture_feed_kernel<int16_t>, grid, block, 0, s(), reinterpret_cast<const int16_t*>(in), stride, int(row), 32768.0, r, cap, pos0);
-            else if (fmt == MGPU_SAMPLES_F32)
-                hipLaunchKernelGGL(mgpu_capture_feed_kernel<float>, grid, block, 0, s(), reinterpret_cast<const float*>(in), stride, int(row), 1.0, r, cap, pos0);
-            else
-                hipLaunchKernelGGL(mgpu_capture_feed_kernel<double>, grid, block, 0, s(), reinterpret_cast<const double*>(in), stride, int(row), 1.0, r, cap, pos0);
+            with_samples(fmt, in, [&](auto* typed, double divisor) {
+                using T = std::remove_cv_t<std::remove_pointer_t<decltype(typed)>>;
+                hipLaunchKernelGGL(mgpu_capture_feed_kernel<T>, grid, block, 0, s(), typed, stride, int(row), divisor, r, cap, pos0);
+            });
             HIPCK(hipGetLastError());
         }
     }
@@ -321,7 +299,7 @@ int mgpu_capture_feed(mgpu_capture* k, const void* samples, int fmt, int H) {
     if (!k) return MGPU_ERR_ARG;
     return guard(k->c, [&] {
         check_feed_args(k, samples, fmt, H);
-        const bool dev = on_device(samples);
+        const bool dev = is_device_memory(samples);
         // only the last sp - 1 samples matter to the window: chunks of max_hops hops, each one upload and one launch
         for (int h0 = 0; h0 < H; h0 += k->max_hops) k->feed(samples, fmt, H, h0, std::min(k->max_hops, H - h0), dev);
         HIPCK(hipStreamSynchronize(k->c->stream));
@@ -342,7 +320,7 @@ int mgpu_capture_run(mgpu_capture* k, const void* samples, int fmt, int H, mgpu_
     return guard(k->c, [&] {
         check_feed_args(k, samples, fmt, H);
         need(n_events != nullptr && max_events >= 0 && (max_events == 0 || events), "bad argument (n_events, events)");
-        const bool dev = on_device(samples);
+        const bool dev = is_device_memory(samples);
         const int stride = k->c->tab.payload_stride;
         int n = 0;
         for (int h0 = 0; h0 < H; h0 += k->max_hops) {

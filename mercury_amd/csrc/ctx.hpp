@@ -1,5 +1,5 @@
 // Private to the library: the context behind the opaque mgpu_ctx handle, the kernel declarations and the helpers
-// that the host-side translation units (api.hip, rxloop.hip) share. Not part of the ABI.
+// that the host-side translation units share. Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -40,15 +41,18 @@ extern "C" __global__ void mgpu_p2b_slide_d1_kernel(const double*, int, const do
 extern "C" __global__ void mgpu_p2b_slide_d4_kernel(const double*, int, const double*, const int*, int, int, const double*, double, double, double*, const int*, const double*, const int*, int);
 extern "C" __global__ void mgpu_p2b_slide_d1_sincos_kernel(const double*, int, const double*, const int*, int, int, const double*, double, double, double*, const int*, const double*, const int*, int);
 extern "C" __global__ void mgpu_p2b_slide_d4_sincos_kernel(const double*, int, const double*, const int*, int, int, const double*, double, double, double*, const int*, const double*, const int*, int);
-extern "C" int mgpu_p2b_slide_geometry(int*);
+// launch shape of one kernel variant, and what the streaming coarse kernel is built for (sync.hip)
+struct MgpuKernelGeometry { int outputs_per_block, threads, lds_bytes; };
+struct MgpuStreamGeometry { int step, ngi, nfft, pre, K, ring; };
+extern "C" MgpuKernelGeometry mgpu_p2b_slide_geometry(int decim);      // decimation 1 or 4
 extern "C" __global__ void mgpu_tsync_metric_kernel(const double*, int, const int*, const int*, const int*, int, int, int, int, int, double*);
 extern "C" __global__ void mgpu_tsync_metric_dense_kernel(const double*, int, const int*, const int*, const int*, int, int, int, int, int, double*);
 extern "C" int mgpu_tsync_coarse_threads();
 extern "C" __global__ void mgpu_tsync_metric_stream_kernel(const double*, int, const int*, const int*, const int*, int, double*, int, int, int);
-extern "C" void mgpu_tsync_stream_geometry(int*);
+extern "C" MgpuStreamGeometry mgpu_tsync_stream_geometry();
 extern "C" __global__ void mgpu_tsync_metric_fine_kernel_r4(const double*, int, const int*, const int*, const int*, int, int, int, int, double*);
 extern "C" __global__ void mgpu_tsync_metric_fine_kernel_r8(const double*, int, const int*, const int*, const int*, int, int, int, int, double*);
-extern "C" int mgpu_tsync_fine_geometry(int*);
+extern "C" MgpuKernelGeometry mgpu_tsync_fine_geometry(int R);          // R = 4 or 8 candidates per lane
 extern "C" __global__ void mgpu_tsync_metric_generic_kernel(const double*, int, const int*, const int*, const int*, int, int, int, int, int, double*);
 extern "C" __global__ void mgpu_fsync_kernel(const double*, int, int, const double*, double*);
 extern "C" __global__ void mgpu_span_energy_kernel(const double*, int, const int*, const int*, int, int, double*, int*);
@@ -84,7 +88,7 @@ struct HipError : std::runtime_error { using std::runtime_error::runtime_error; 
         if (e_ != hipSuccess) throw HipError(std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-hipError_t host_alloc_on_node(void** p, size_t bytes, int node);   // api.hip
+hipError_t host_alloc_on_node(void** p, size_t bytes, int node);   // create.hip
 int device_numa_node(int device);
 
 // Owning handles: move-only, released by the destructor (errors ignored), so that a throw on any path frees what was made before it.
@@ -183,7 +187,7 @@ struct mgpu_ctx {
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     PinnedBuf h_out;                // page-locked staging for the payloads + stats of a pipelined call ([max_batch])
     static constexpr int kPipes = 2;
-    Pipe pipe[kPipes];                   // the two chunk pipelines of the blocking host-buffer entry points (api.hip rx_batch_pipelined)
+    Pipe pipe[kPipes];                   // the two chunk pipelines of the blocking host-buffer entry points (rx_batch.hip rx_batch_pipelined)
     Event hp_ev[4];                      // call start, first chunk copied, last chunk copied, all done (host-path profile)
     int hp_chunk = 0, hp_nchunks = 0;    // the last pipelined call: frames per chunk, chunks
     float hp_fill_ms = 0, hp_drain_ms = 0, hp_total_ms = 0;
@@ -205,13 +209,19 @@ struct mgpu_ctx {
 
 namespace mgpu_detail {
 
-// Workspaces sized by max_batch are created on first use (api.hip)
+// Workspaces sized by max_batch are created on first use (create.hip)
 enum : unsigned { WS_FRONTEND = 1, WS_LLR = 2, WS_OUT = 4, WS_BITS = 8 };
 void ensure_workspaces(mgpu_ctx* c, unsigned what);
 
 // HIP caps gridDim*blockDim below 2^32 threads, so very large batches go out in chunks of frames.
 constexpr int kMaxFramesPerLaunch = 1 << 21;
+template <typename Fn> void for_frame_chunks(int F, Fn&& fn) {      // fn(first frame, frames) per launch
+    for (int off = 0; off < F; off += kMaxFramesPerLaunch) fn(off, F - off < kMaxFramesPerLaunch ? F - off : kMaxFramesPerLaunch);
+}
 template <typename T> T* at(T* p, size_t off) { return p ? p + off : nullptr; }
+
+using FrontendKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
+inline FrontendKernel fe_kernel(int threads) { return threads == 1024 ? mgpu_frontend_kernel_t1024 : mgpu_frontend_kernel; }
 
 // frame_stride (complex samples between consecutive frames of d_bb) defaults to the mode's frame_samples
 // frame0: index of the call's first frame inside the context's max_batch-sized workspaces (the ZF modes keep their equalised symbols there)
@@ -220,18 +230,21 @@ void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float
 void launch_zf_snr(mgpu_ctx* c, int F, const uint8_t* d_payload, MgpuStatsDev* d_stats, hipStream_t s, int frame0 = 0, double* d_var_out = nullptr);
 void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
                     const float* d_var, const float* d_snrvar, hipStream_t s);
+// F generated frames from frame0 on into d_bb (and their payloads into d_payload, if given). channel -1: the transmit path's clean frames,
+// whose payloads come from tx_payload (frames tx_stride bytes apart, d_nbytes of each in use) instead of the generator
+void launch_txgen(mgpu_ctx* c, uint64_t seed, uint64_t frame0, int F, double noise_amp, int channel, double* d_bb, uint8_t* d_payload, hipStream_t s,
+                  const uint8_t* tx_payload = nullptr, int tx_stride = 0, const int* d_nbytes = nullptr);
 
-// the reference's peak selection (ofdm.cc:1943-1964): overwrite-not-swap partial sort over an array of `size` entries that
-// holds the metric of candidate k at index k*step and 0 elsewhere; returns the index (delay) and value of entry
-// `location_to_return` after nTrials_max passes
 // the scalar half of cl_ofdm::time_sync_mfsk (ofdm.cc:2004-2060) on the slot energies of one window ([nslots][Nc])
 int mfsk_sync_from_energies(const mgpu::ModeTables& t, const double* E, int nslots, int size, int search_start_symb);
 void launch_mfsk_sync(mgpu_ctx* c, const double* d_energy, int W, int nslots, int size, const int* d_search_start, int* d_delay, hipStream_t s);
 // passband_to_baseband launch for nwin windows (grid y) of `count` outputs each: the sliding-tap kernels for the reference's 33-tap filters
-// at decimation 1 / 4, the generic kernel otherwise (api.hip)
+// at decimation 1 / 4, the generic kernel otherwise (launch.hip)
 void launch_p2b(const double* passband, int in_size, const double* d_carrier, const int* d_start, int start_all, int count, int decim, const double* d_taps,
                 int ntaps, double* out, const int* widx, const double* cs, const int* out_row, int row_by_launch, int nwin, hipStream_t s);
-
+// the reference's peak selection (ofdm.cc:1943-1964): overwrite-not-swap partial sort over an array of `size` entries that
+// holds the metric of candidate k at index k*step and 0 elsewhere; returns the index (delay) and value of entry
+// `location_to_return` after nTrials_max passes
 void select_peak(const double* cand_vals, int ncand, int step, int size, int location_to_return, int nTrials_max, int* delay, double* corr);
 
 // carrier_sampling_frequency_sync's last step (ofdm.cc:594 with get_angle, misc.cc:34-56) on the sum the Moose kernel returns
@@ -301,7 +314,47 @@ inline void need(bool ok, const char* what) { if (!ok) throw std::invalid_argume
 // (telecom_system.cc:3006), hop step 7, 8 tones sent twice.
 constexpr int kAckTones[8] = {4, 7, 5, 12, 13, 1, 9, 15}, kBreakTones[8] = {6, 14, 2, 3, 10, 8, 11, 15};
 constexpr int kAckM = 16, kAckNsymb = 16, kAckLen = 8, kAckHop = 7, kAckOffset = 17;
+constexpr int kInterp = 4;                       // frequency_interpolation_rate, physical_config.cc:79
 constexpr double kSampleRate = 48000.0;          // telecom_system.cc:1569
-const double kCarrierAmplitude = 1.4142135623730951;   // sqrt(2.0), telecom_system.cc:69
+constexpr double kBandwidthHz = kSampleRate * 50.0 / 256 / 4;     // physical_config.cc:81, in its order
+constexpr double kCarrierAmplitude = 1.4142135623730951;   // sqrt(2.0), telecom_system.cc:69
+
+// run `launch(d_in..., d_out)` between an upload of the inputs and a download of the outputs on the context's stream
+struct Io {
+    mgpu_ctx* c;
+    hipStream_t s;
+    explicit Io(mgpu_ctx* ctx) : c(ctx), s(ctx->stream) {}
+    void up(DevBuf& d, const void* h, size_t bytes) { HIPCK(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, s)); }
+    void back(void* h, DevBuf& d, size_t bytes) { HIPCK(hipMemcpyAsync(h, d.p, bytes, hipMemcpyDeviceToHost, s)); }
+    void down(void* h, DevBuf& d, size_t bytes) { back(h, d, bytes); HIPCK(hipStreamSynchronize(s)); }      // the last output: waited for
+};
+
+// The audio device's sample formats (mercury_rxloop.h MGPU_SAMPLES_*; audioio.c:893-936): fn(samples as their element type, the divisor that
+// widens one to the double receive_byte works on)
+inline bool known_format(int fmt) {
+    return fmt == MGPU_SAMPLES_F64 || fmt == MGPU_SAMPLES_INT32 || fmt == MGPU_SAMPLES_INT16 || fmt == MGPU_SAMPLES_F32;
+}
+inline size_t sample_bytes(int fmt) { return fmt == MGPU_SAMPLES_F64 ? 8 : fmt == MGPU_SAMPLES_INT16 ? 2 : 4; }
+template <typename Fn> auto with_samples(int fmt, const void* samples, Fn&& fn) {
+    switch (fmt) {
+        case MGPU_SAMPLES_INT32: return fn(static_cast<const int32_t*>(samples), 2147483647.0);
+        case MGPU_SAMPLES_INT16: return fn(static_cast<const int16_t*>(samples), 32768.0);
+        case MGPU_SAMPLES_F32: return fn(static_cast<const float*>(samples), 1.0);
+        default: return fn(static_cast<const double*>(samples), 1.0);
+    }
+}
+inline bool is_device_memory(const void* p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// receive_byte for W windows in host or device memory, on the context's stream (rxloop.hip)
+void receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_receive_config* rcp, mgpu_link_state* state, uint8_t* payload,
+                       mgpu_receive_stats* stats);
+// Per-component noise amplitude of the audio-path simulations at esn0_db (selfsim.hip): OFDM from Es/N0 alone, MFSK calibrated from the mean
+// power of the first transmitted frame
+double audio_noise_amplitude(const mgpu::ModeTables& t, double esn0_db, double mean_power);
 
 }  // namespace mgpu_detail

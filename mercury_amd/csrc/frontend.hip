@@ -309,7 +309,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
     // reference's three passes over a full channel grid.
     const uint2* __restrict__ cell_lerp = reinterpret_cast<const uint2*>(T.cell_lerp);
     auto equalise_data = [&](int idx) {
-        // the cell, the pilot rows a / b it interpolates between and their pilots' indices in its column: tabulated on the host (api.hip)
+        // the cell, the pilot rows a / b it interpolates between and their pilots' indices in its column: tabulated on the host (create.hip)
         const uint2 q = cell_lerp[idx];
         const int c = int(q.x & 0xfffu), pa = int((q.x >> 12) & 0x3ffu), pb = int(q.x >> 22);
         const int a = int(q.y & 0xffu), b = int((q.y >> 8) & 0xffu), i = int(q.y >> 16);

@@ -23,7 +23,6 @@
 
 namespace {
 
-constexpr int kInterp = 4;
 constexpr int kDefaultHops = 16;
 
 const char* config_error(const mgpu_linksim_config* k) {
@@ -256,7 +255,7 @@ int mgpu_linksim_create(mgpu_ctx* c, const mgpu_linksim_config* kc, const double
         k->evpl.resize(k->ev.size() * k->stride);
         k->noisy = esn0_db != nullptr;
         if (k->noisy) {
-            // sigma as mgpu_passband_test_esn0 (telecom_system.cc:236-239 for OFDM; :266-279 for MFSK, from the power of the first frame link 0 sends)
+            // the noise of mgpu_passband_test_esn0 (selfsim.hip); MFSK calibrates it from the power of the first frame link 0 sends
             double psig = 0;
             if (t.mfsk_M > 0) {
                 uint8_t* hp = static_cast<uint8_t*>(k->h_payload.h);
@@ -273,14 +272,7 @@ int mgpu_linksim_create(mgpu_ctx* c, const mgpu_linksim_config* kc, const double
             k->noise_amp.resize(S);
             for (int s = 0; s < S; ++s) {
                 need(std::isfinite(esn0_db[s]), "esn0_db must be finite");
-                float sigma;
-                if (t.mfsk_M > 0) {
-                    const double bandwidth = 48000.0 * 50.0 / 256 / 4;
-                    sigma = float(std::sqrt(2.0 * psig * (48000.0 / 2.0) / (std::pow(10.0, double(float(esn0_db[s])) / 10.0) * bandwidth)));
-                } else {
-                    sigma = 1.0f / float(std::sqrt(std::pow(10.0f, float(esn0_db[s]) / 10.0f)));
-                }
-                k->noise_amp[s] = double(sigma / std::sqrt(2.0f));                                     // awgn.cc:68
+                k->noise_amp[s] = audio_noise_amplitude(t, esn0_db[s], psig);
             }
         }
         HIPCK(hipDeviceSynchronize());

@@ -27,7 +27,7 @@ extern "C" int mgpu_mfsk_syms_per_block() { return MF_SYMS; }
 namespace {
 
 // In every MFSK mode the tone band is carriers [9, 41) of the 50 (cl_mfsk::init, mfsk.cc:69-76: nStreams * M == 32
-// bins centred in Nc == 50); the host checks this before launching (api.hip).
+// bins centred in Nc == 50); the host checks this before launching (launch.hip).
 constexpr int kBandStart = 9, kBandEnd = 41, kNoiseBins = 50 - (kBandEnd - kBandStart);
 
 __device__ __forceinline__ double readlane_f64(double v, int src) {
@@ -197,7 +197,7 @@ extern "C" __global__ __launch_bounds__(MF_THREADS) void mgpu_mfsk_frontend_kern
 // (ofdm.cc:2011-2024) and cl_ofdm::detect_ack_pattern (ofdm.cc:2097-2105). Slot s of window w starts at
 // s * Nofdm * interp + Ngi * interp; its 256 samples are taken `interp` apart (the reference's decimation), transformed
 // with the 1/Nfft scale, and |X|^2 of the 50 carriers is written in carrier order. The sliding-window sums and
-// the arg-max over slots are a few hundred scalar operations per window and stay on the host (api.hip).
+// the arg-max over slots are a few hundred scalar operations per window and stay on the host (sync_api.hip).
 extern "C" __global__ __launch_bounds__(MF_THREADS) void mgpu_slot_energy_kernel(
     const double* __restrict__ baseband_interp, int size, int nslots, int interp, const double* __restrict__ twiddle,
     double* __restrict__ energy /*[W][nslots][50]*/) {
@@ -226,7 +226,7 @@ extern "C" __global__ __launch_bounds__(MF_THREADS) void mgpu_slot_energy_kernel
 // sum_p e_target(s + p) / e_total(s + p) over the np preamble symbols (e_total: the 50 carriers added in carrier order; e_target: the
 // streams' tones of preamble symbol p added in stream order; a slot with e_total <= 0 adds nothing; the sum stops at the first symbol
 // that does not fit the buffer), and the first slot with the largest metric from search_start on (the reference's strict ">"; nothing
-// beats the initial -1 -> slot 0). One workgroup per window; same operations in the same order as mfsk_sync_from_energies (api.hip),
+// beats the initial -1 -> slot 0). One workgroup per window; same operations in the same order as mfsk_sync_from_energies (launch.hip),
 // which stays as the few-window path and the host-side statement the CPU tests pin. 66 MB of energies per 256 ROBUST_0 windows no
 // longer cross PCIe for a few hundred scalar operations per window.
 extern "C" __global__ __launch_bounds__(256) void mgpu_mfsk_sync_kernel(

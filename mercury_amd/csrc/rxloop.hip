@@ -40,17 +40,10 @@ struct PhaseTimer {
     }
 };
 
-constexpr int kInterp = 4, kCoarseStep = 100;
+constexpr int kCoarseStep = 100;
 constexpr int kManySpans = 4096;          // span energies: the lane-per-span kernel from this many spans per launch
 constexpr int kSlice = 64, kCoarseGroup = 2;   // upload / mixer slices of windows; slices per coarse-search launch from host memory
 constexpr double kEnergyGate = 0.001, kMetricGate = 0.5, kMeanHGate = 0.3, kFreqIgnore = 0.1;   // telecom_system.cc:843, :854, :1269; physical_config.cc:60
-
-bool is_device_memory(const void* p) {
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice) return true;
-    (void)hipGetLastError();
-    return false;
-}
 
 struct Win {                       // one capture window's walk through receive_byte
     int delay = 0, pream = 1, sync_trials = 0, skip_h = 0;
@@ -652,7 +645,7 @@ struct Loop {
         std::vector<int> rw, rslot;
         for (int k = 0; k < n; ++k) {
             Win& x = win[act[k]];
-            double f = moose_hz(mul[2 * k], mul[2 * k + 1], (48000.0 * 50.0 / 256 / 4) / double(t.Nc));
+            double f = moose_hz(mul[2 * k], mul[2 * k + 1], kBandwidthHz / double(t.Nc));
             if (x.sync_trials == T && rc.use_last_good_freq_offset && state && state[act[k]].freq_offset_of_last_decoded_message != 0)
                 f = state[act[k]].freq_offset_of_last_decoded_message;
             x.freq = f;
@@ -765,7 +758,7 @@ extern "C" {
 int mgpu_receive_buffer_nsymb(mgpu_ctx* c) {
     if (!c) return -1;
     const auto& t = c->tab;                                      // data_container.cc:133-143
-    const double sym_time_ms = 1000.0 * t.Nofdm * kInterp / 48000.0;
+    const double sym_time_ms = 1000.0 * t.Nofdm * kInterp / kSampleRate;
     const int turnaround_symb = int(std::ceil(1200.0 / sym_time_ms)) + 4;
     const int frame_symb = t.preamble + t.Nsymb;
     int min_buf = frame_symb * 2;
@@ -794,10 +787,9 @@ int mgpu_measure_signal_only(mgpu_ctx* c, const double* passband, int W, double 
 
 }  // extern "C"
 
-namespace {
 // receive_byte for W windows that lie in host or device memory, on the context's stream: the reference's receive_byte, phase by phase
-void receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_receive_config* rcp, mgpu_link_state* state, uint8_t* payload,
-                       mgpu_receive_stats* stats) {
+void mgpu_detail::receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_receive_config* rcp, mgpu_link_state* state,
+                                    uint8_t* payload, mgpu_receive_stats* stats) {
     Loop lp(c, W, *rcp, mgpu_receive_buffer_nsymb(c), state, payload, stats);
     lp.pt.mark(lp.s, "device buffers");
     ensure_workspaces(c, WS_FRONTEND | WS_LLR | WS_OUT);
@@ -813,7 +805,6 @@ void receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_re
     }
     lp.finish();
 }
-}  // namespace
 
 // The capture thread's widening of the audio device's samples to the doubles receive_byte works on (radio_capture_thread,
 // audioio.c:893-936), on the device: INT32 / INT_MAX (:909), INT16 / 32768.0 (:907), FLOAT32 widened (:905). int -> double is exact and the
@@ -827,12 +818,12 @@ __global__ __launch_bounds__(256) void mgpu_widen_capture_kernel(const T* __rest
     }
 }
 namespace {
-size_t sample_bytes(int fmt) { return fmt == MGPU_SAMPLES_F64 ? 8 : fmt == MGPU_SAMPLES_INT16 ? 2 : 4; }
-void launch_widen(const void* d_in, int fmt, size_t n, double* d_out, hipStream_t s) {
+void launch_widen(const void* d_in, int fmt, size_t n, double* d_out, hipStream_t s) {      // compact formats only: doubles are read where they lie
     const dim3 grid(unsigned(std::min<size_t>((n + 255) / 256, 65535u * 4))), block(256);
-    if (fmt == MGPU_SAMPLES_INT32) hipLaunchKernelGGL(mgpu_widen_capture_kernel<int32_t>, grid, block, 0, s, static_cast<const int32_t*>(d_in), n, 2147483647.0, d_out);
-    else if (fmt == MGPU_SAMPLES_INT16) hipLaunchKernelGGL(mgpu_widen_capture_kernel<int16_t>, grid, block, 0, s, static_cast<const int16_t*>(d_in), n, 32768.0, d_out);
-    else hipLaunchKernelGGL(mgpu_widen_capture_kernel<float>, grid, block, 0, s, static_cast<const float*>(d_in), n, 1.0, d_out);
+    with_samples(fmt, d_in, [&](auto* in, double divisor) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(in)>>;
+        if constexpr (!std::is_same_v<T, double>) hipLaunchKernelGGL(mgpu_widen_capture_kernel<T>, grid, block, 0, s, in, n, divisor, d_out);
+    });
     HIPCK(hipGetLastError());
 }
 // The sub-batches [offset, count) a pipelined host call is cut into. Doubles are upload-bound (the synchroniser of a sub-batch is over before
@@ -878,7 +869,7 @@ hipError_t upload_piece(mgpu_ctx* c, const char* src, int fmt, size_t buf, int o
 void receive_byte_any(mgpu_ctx* c, const void* capture, int fmt, int W, const mgpu_receive_config* rcp, mgpu_link_state* state, uint8_t* payload,
                       mgpu_receive_stats* stats) {
     need(capture && rcp && payload && stats && W > 0 && W <= c->max_batch, "bad argument (W must be 1..max_batch)");
-    need(fmt == MGPU_SAMPLES_F64 || fmt == MGPU_SAMPLES_INT32 || fmt == MGPU_SAMPLES_INT16 || fmt == MGPU_SAMPLES_F32, "unknown sample format");
+    need(known_format(fmt), "unknown sample format");
     need(rcp->time_sync_trials_max >= 1 && rcp->time_sync_trials_max < 64,
          "time_sync_trials_max must be 1..63 (0 makes the reference index its peak table at -1)");
     // every argument is judged before the first copy or kernel is queued: an error return leaves nothing in flight and no state[] entry touched
@@ -964,100 +955,3 @@ extern "C" int mgpu_receive_byte_batch_samples(mgpu_ctx* c, const void* capture,
     if (!c) return MGPU_ERR_ARG;
     return guard(c, [&] { receive_byte_any(c, capture, sample_format, W, rcp, state, payload, stats); });
 }
-
-// cl_telecom_system::passband_test_EsN0 (telecom_system.cc:231-330) per Es/N0 point, batched: random payloads -> transmit_byte
-// (SINGLE_MESSAGE) -> apply_with_delay (AWGN on the audio, the frame `delay` samples into the capture window) -> receive_byte ->
-// cl_error_rate::check over the payload bits. Everything stays on the device except the per-window results receive_byte returns.
-// ch: NULL = AWGN alone (mgpu_passband_test_esn0), else the HF channel in front of the same noise (mgpu_passband_test_esn0_hf)
-static int passband_test_esn0_impl(mgpu_ctx* c, const double* esn0_db, int npoints, long long frames_per_point, uint64_t seed, uint64_t frame0,
-                                   double carrier_hz, double output_power_watt, const mgpu_hf_channel* ch, mgpu_error_rate* out, double* windows_out,
-                                   uint8_t* sent_out) {
-    if (!c) return MGPU_ERR_ARG;
-    return guard(c, [&] {
-        need(esn0_db && out && npoints > 0 && frames_per_point > 0 && output_power_watt > 0, "bad argument");
-        const auto& t = c->tab;
-        const bool mfsk = t.mfsk_M > 0;
-        const int total = mgpu_transmit_frame_samples(c);
-        const int window = t.Nofdm * mgpu_receive_buffer_nsymb(c) * kInterp;
-        const int delay = ((t.preamble + 2) * t.Nofdm + (t.Nfft == 1024 ? 100 : 50)) * kInterp;           // :242-249, :292
-        need(delay + total <= window, "the frame does not fit the capture window behind the test delay");
-        const int B = int(std::min<long long>(frames_per_point, std::min(c->max_batch, 1024)));            // 1024 windows = 0.76 GB of audio
-        const int stride = t.payload_stride, nbytes = t.payload_bytes;
-        DevBuf d_pl(size_t(B) * stride), d_audio(size_t(B) * total * 8), d_win(size_t(B) * window * 8);
-        std::vector<uint8_t> sent(size_t(B) * stride), got(size_t(B) * stride);
-        std::vector<mgpu_receive_stats> st(B);
-        std::vector<mgpu_link_state> ls(B);
-        const mgpu_transmit_config txc = {carrier_hz, 1.4142135623730951, output_power_watt, 7.0, 10.0, 0, MGPU_SINGLE_MESSAGE, 0};   // physical_config.cc defaults
-        const mgpu_receive_config rxc = {carrier_hz, 2, 1, 1, 0};
-        hipStream_t s = c->stream;
-        for (int p = 0; p < npoints; ++p) {
-            // sigma: :236-239 for OFDM; :266-279 calibrates it once per call from the first frame's power for MFSK
-            float sigma = mfsk ? 0.0f : 1.0f / float(std::sqrt(std::pow(10.0f, float(esn0_db[p]) / 10.0f)));
-            bool calibrated = !mfsk;
-            long long be = 0, fe = 0, ok = 0;
-            double iters = 0;
-            for (long long done = 0; done < frames_per_point; done += B) {
-                const int n = int(std::min<long long>(B, frames_per_point - done));
-                const uint64_t first = frame0 + uint64_t(p) * uint64_t(frames_per_point) + uint64_t(done);
-                hipLaunchKernelGGL(mgpu_gen_payload_kernel, dim3(n), dim3(256), 0, s, seed, first, n, nbytes, stride, d_pl.as<uint8_t>());
-                HIPCK(hipGetLastError());
-                if (mgpu_transmit_byte_batch_dev(c, d_pl.p, stride, nullptr, n, &txc, d_audio.p, s) != MGPU_OK) throw std::runtime_error(std::string(c->err));
-                if (!calibrated) {
-                    std::vector<double> a0(total);
-                    HIPCK(hipMemcpyAsync(a0.data(), d_audio.p, size_t(total) * 8, hipMemcpyDeviceToHost, s));
-                    HIPCK(hipStreamSynchronize(s));
-                    double psig = 0;
-                    for (int i = 0; i < total; ++i) psig += a0[i] * a0[i];
-                    psig /= total;
-                    const double bandwidth = 48000.0 * 50.0 / 256 / 4;
-                    sigma = float(std::sqrt(2.0 * psig * (48000.0 / 2.0) / (std::pow(10.0, double(float(esn0_db[p])) / 10.0) * bandwidth)));
-                    calibrated = true;
-                }
-                const double ampl = double(sigma / std::sqrt(2.0f));                                   // awgn.cc:68
-                if (ch) {
-                    launch_hf_passband(ch, d_audio.as<double>(), total, delay, window, ampl, seed, first, n, d_win.as<double>(), s);
-                } else {
-                    hipLaunchKernelGGL(mgpu_passband_channel_kernel, dim3((window + 255) / 256, n), dim3(256), 0, s, d_audio.as<double>(), total, delay, window,
-                                       ampl, seed, first, n, d_win.as<double>());
-                    HIPCK(hipGetLastError());
-                }
-                HIPCK(hipMemcpyAsync(sent.data(), d_pl.p, size_t(n) * stride, hipMemcpyDeviceToHost, s));
-                if (windows_out) HIPCK(hipMemcpyAsync(windows_out + (size_t(p) * frames_per_point + done) * window, d_win.p, size_t(n) * window * 8, hipMemcpyDeviceToHost, s));
-                HIPCK(hipStreamSynchronize(s));
-                if (sent_out) std::memcpy(sent_out + (size_t(p) * frames_per_point + done) * stride, sent.data(), size_t(n) * stride);
-                for (int w = 0; w < n; ++w) ls[w] = mgpu_link_state{-1, 0.0, 0, mfsk ? delay + 1 : 0};      // :293-296 mfsk_fixed_delay
-                receive_byte_impl(c, d_win.as<double>(), n, &rxc, ls.data(), got.data(), st.data());
-                for (int w = 0; w < n; ++w) {
-                    int e = 0;
-                    for (int b = 0; b < nbytes; ++b) e += __builtin_popcount(unsigned(sent[size_t(w) * stride + b] ^ got[size_t(w) * stride + b]));
-                    be += e; fe += e != 0; ok += st[w].message_decoded != 0;
-                    iters += st[w].iterations_done > 0 ? st[w].iterations_done : 0;
-                }
-            }
-            mgpu_error_rate& r = out[p];
-            r.esn0_db = esn0_db[p];
-            r.Frames_total = frames_per_point; r.Error_frames_total = fe;
-            r.Bits_total = frames_per_point * nbytes * 8; r.Error_bits_total = be;
-            r.BER = double(be) / double(r.Bits_total); r.FER = double(fe) / double(frames_per_point);
-            r.avg_iterations = iters / double(frames_per_point);
-            r.crc_ok_frames = ok;
-        }
-    });
-}
-
-extern "C" int mgpu_passband_test_esn0(mgpu_ctx* c, const double* esn0_db, int npoints, long long frames_per_point, uint64_t seed, uint64_t frame0,
-                                       double carrier_hz, double output_power_watt, mgpu_error_rate* out, double* windows_out, uint8_t* sent_out) {
-    return passband_test_esn0_impl(c, esn0_db, npoints, frames_per_point, seed, frame0, carrier_hz, output_power_watt, nullptr, out, windows_out,
-                                   sent_out);
-}
-
-extern "C" int mgpu_passband_test_esn0_hf(mgpu_ctx* c, const double* esn0_db, int npoints, long long frames_per_point, uint64_t seed, uint64_t frame0,
-                                          double carrier_hz, double output_power_watt, const mgpu_hf_channel* ch, mgpu_error_rate* out,
-                                          double* windows_out, uint8_t* sent_out) {
-    if (!c) return MGPU_ERR_ARG;
-    const int rc = guard(c, [&] { hf_check(ch); });     // a bad channel is refused before any device work
-    if (rc != MGPU_OK) return rc;
-    return passband_test_esn0_impl(c, esn0_db, npoints, frames_per_point, seed, frame0, carrier_hz, output_power_watt, ch, out, windows_out,
-                                   sent_out);
-}
-

@@ -18,15 +18,6 @@ extern "C" __global__ void mgpu_stage_crc16_kernel(const uint8_t*, int, int, uin
 
 namespace {
 
-// run `launch(d_in..., d_out)` between an upload of the inputs and a download of the output
-struct Io {
-    mgpu_ctx* c;
-    hipStream_t s;
-    explicit Io(mgpu_ctx* ctx) : c(ctx), s(ctx->stream) {}
-    void up(DevBuf& d, const void* h, size_t bytes) { HIPCK(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, s)); }
-    void down(void* h, DevBuf& d, size_t bytes) { HIPCK(hipMemcpyAsync(h, d.p, bytes, hipMemcpyDeviceToHost, s)); HIPCK(hipStreamSynchronize(s)); }
-};
-
 void ofdm_only(mgpu_ctx* c) { need(c->tab.mfsk_M == 0, "the per-method stages exist for the OFDM modes (cfg 0..16)"); }
 
 }  // namespace

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ctx.hpp"
 #include "glibc_trig.h"
 
 namespace {
@@ -46,7 +47,7 @@ extern "C" __global__ __launch_bounds__(P2B_THREADS) void mgpu_p2b_kernel(
         c2 v = {0.0, 0.0};
         if (i >= 0 && i < in_size) {
             const double a = in[i] * amplitude;
-            if (cs) {                // every window of this launch uses the carrier the table was made for (host libm, see api.hip)
+            if (cs) {                // every window of this launch uses the carrier the table was made for (host libm, see launch.hip)
                 v = {a * cs[2 * i], a * cs[2 * i + 1]};
             } else {
                 const double ph = 2 * M_PI * fc * double(i) * Ts;
@@ -204,10 +205,9 @@ P2S_KERNEL(mgpu_p2b_slide_d1_kernel, 1, 4, 256, true)
 P2S_KERNEL(mgpu_p2b_slide_d4_kernel, 4, 2, 128, true)
 P2S_KERNEL(mgpu_p2b_slide_d1_sincos_kernel, 1, 4, 256, false)
 P2S_KERNEL(mgpu_p2b_slide_d4_sincos_kernel, 4, 2, 128, false)
-extern "C" int mgpu_p2b_slide_geometry(int* o) {   // per kernel: outputs per block, threads, LDS bytes
-    o[0] = 256 * 4; o[1] = 256; o[2] = P2sGeom<33, 1, 4, 256>::M * P2sGeom<33, 1, 4, 256>::ROW * 16;
-    o[3] = 128 * 2; o[4] = 128; o[5] = P2sGeom<33, 4, 2, 128>::M * P2sGeom<33, 4, 2, 128>::ROW * 16;
-    return 0;
+extern "C" MgpuKernelGeometry mgpu_p2b_slide_geometry(int decim) {
+    if (decim == 1) return {256 * 4, 256, P2sGeom<33, 1, 4, 256>::M * P2sGeom<33, 1, 4, 256>::ROW * 16};
+    return {128 * 2, 128, P2sGeom<33, 4, 2, 128>::M * P2sGeom<33, 4, 2, 128>::ROW * 16};
 }
 
 // Schmidl-Cox metric (ofdm.cc:1893-1941). One lane per candidate offset i = cand*step; the three accumulators run
@@ -395,7 +395,7 @@ __device__ __forceinline__ void tss_segment_events(int ch, int js, int lane, int
 // the geometry the kernel is built for: the reference's coarse search (step 100, ofdm.cc:1893) on the x4 interpolated baseband of its
 // Nfft 256 / guard interval 1/16 / 4-symbol-preamble modes; anything else goes to the staged kernel
 typedef TssGeom<100, 64, 1024, 4> TssCoarse;
-extern "C" void mgpu_tsync_stream_geometry(int* g) { g[0] = TssCoarse::STEPV; g[1] = TssCoarse::NGI; g[2] = TssCoarse::NFFT; g[3] = TssCoarse::PRE; g[4] = TSS_K; g[5] = TSS_RING; }
+extern "C" MgpuStreamGeometry mgpu_tsync_stream_geometry() { return {TssCoarse::STEPV, TssCoarse::NGI, TssCoarse::NFFT, TssCoarse::PRE, TSS_K, TSS_RING}; }
 
 template <class G>
 __device__ __forceinline__ void tss_run(const double* __restrict__ bb, int stride, const int* __restrict__ start, const int* __restrict__ widx,
@@ -667,10 +667,9 @@ __device__ __forceinline__ void tfine_run(const double* __restrict__ bb, int str
     }
 }
 
-extern "C" int mgpu_tsync_fine_geometry(int* out) {   // candidates per workgroup, threads, LDS bytes for R = 4 and R = 8
-    out[0] = 64 * 4 * TfGeom<4>::WAVES; out[1] = 64 * TfGeom<4>::WAVES; out[2] = TfGeom<4>::WAVES * 2 * 4 * TfGeom<4>::ROW * 16;
-    out[3] = 64 * 8 * TfGeom<8>::WAVES; out[4] = 64 * TfGeom<8>::WAVES; out[5] = TfGeom<8>::WAVES * 2 * 8 * TfGeom<8>::ROW * 16;
-    return 0;
+extern "C" MgpuKernelGeometry mgpu_tsync_fine_geometry(int R) {   // outputs = candidates per workgroup
+    if (R == 4) return {64 * 4 * TfGeom<4>::WAVES, 64 * TfGeom<4>::WAVES, TfGeom<4>::WAVES * 2 * 4 * TfGeom<4>::ROW * 16};
+    return {64 * 8 * TfGeom<8>::WAVES, 64 * TfGeom<8>::WAVES, TfGeom<8>::WAVES * 2 * 8 * TfGeom<8>::ROW * 16};
 }
 
 extern "C" __global__ __launch_bounds__(64 * TfGeom<4>::WAVES) void mgpu_tsync_metric_fine_kernel_r4(
@@ -899,7 +898,7 @@ extern "C" __global__ __launch_bounds__(64) void mgpu_window_energy_kernel(
 // of the largest entry at or after j, so the scan parallelises: every lane keeps the first maximum of its own (position-ordered)
 // share of the candidates, lanes are merged with "larger value, else smaller position", the implicit zeros between / behind the
 // candidates are represented by the first of them, and the start entry is kept unless something is strictly larger (which also
-// reproduces the reference when that entry is NaN). Same result as select_peak in api.hip (the host emulation the CPU tests pin
+// reproduces the reference when that entry is NaN). Same result as select_peak in launch.hip (the host emulation the CPU tests pin
 // against the reference's loop); one lane per window crawling through 881 or 4352 entries took 0.37 ms per launch.
 extern "C" __global__ __launch_bounds__(64) void mgpu_select_peak_kernel(
     const double* __restrict__ vals, const int* __restrict__ ncand_w, int ncand_max, int step, const int* __restrict__ size_w,

@@ -58,7 +58,7 @@ struct LdpcGraph {
     double bank_model[2] = {0, 0}; // modelled LDS cycles per 32-lane gather group (1.0 = conflict-free) of the check pass's posterior reads / the variable update's message reads
     // the fp64 sum-product kernel's own tables (ldpc.hip, spa_decode): LDS byte offsets instead of indices, and the
     // product walk's execution masks tabulated per bin and step instead of compared per lane
-    // register-layout limits of individual kernels, recorded here and enforced where a context selects its decoder (api.hip: ctx_plan), so
+    // register-layout limits of individual kernels, recorded here and enforced where a context selects its decoder (create.hip: ctx_plan), so
     // that a graph one decoder cannot hold still loads for the others (GBF walks the plain lists and has no such limit)
     std::string fp64_limit, fp32_limit;   // empty = fits; otherwise what the fp64 / the fp32 sum-product + min-sum kernels cannot hold
     int maxdeg = 0;                // largest check degree

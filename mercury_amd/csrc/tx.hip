@@ -260,8 +260,8 @@ const double* ensure_carrier_table(TxState& st, double carrier_hz, uint64_t star
 void transmit_dev(mgpu_ctx* c, const uint8_t* d_payload, int payload_stride, const int* d_nbytes, int F, const mgpu_transmit_config& cfg,
                   double* d_out, hipStream_t s) {
     const auto& t = c->tab;
-    const int interp = 4, npre = t.preamble * t.Nofdm, ndata = t.active_nsymb * t.Nofdm, total = t.Nofdm * (t.Nsymb + t.preamble) * interp;
-    const int used = (npre + ndata) * interp;
+    const int npre = t.preamble * t.Nofdm, ndata = t.active_nsymb * t.Nofdm, total = t.Nofdm * (t.Nsymb + t.preamble) * kInterp;
+    const int used = (npre + ndata) * kInterp;
     TxState& st = tx_state(c, s);
     const bool batch = cfg.message_location == MGPU_BATCH_MESSAGE;
     // FIRST / MIDDLE / FLUSH_MESSAGE (telecom_system.cc:559-590): call n filters the span that starts half a frame into the 3-frame
@@ -286,7 +286,7 @@ void transmit_dev(mgpu_ctx* c, const uint8_t* d_payload, int payload_stride, con
         st.carrier = cfg.carrier_hz;
     }
     // scaling constants in the reference's types and order (telecom_system.cc:388, :506-527)
-    const float power_normalization = std::sqrt(double(t.Nfft * interp));
+    const float power_normalization = std::sqrt(double(t.Nfft * kInterp));
     const double mfsk_boost = t.mfsk_M > 0 ? std::sqrt(double(t.Nc) / t.mfsk_nstreams) * std::pow(10.0, -2.0 / 20.0) : 1.0;
     const double pw = std::sqrt(cfg.output_power_watt), preamble_boost = std::sqrt(2.0);          // telecom_system.cc:2840
     const double m_pre = pw * preamble_boost * mfsk_boost, m_data = pw * mfsk_boost;
@@ -298,13 +298,7 @@ void transmit_dev(mgpu_ctx* c, const uint8_t* d_payload, int payload_stride, con
     double* const t0 = filtered ? static_cast<double*>(st.work(1, (size_t(F) * total + 2 * pad) * 8, s)) : nullptr;
     double* const t1_all = filtered ? static_cast<double*>(st.work(2, (size_t(F) * total + 2 * pad) * 8, s)) : nullptr;
     double* clipped = filtered ? t0 + (stream_mode ? 2 * pad : pad) : d_out;     // stream form: two history frames in front
-    for (int off = 0; off < F; off += kMaxFramesPerLaunch) {
-        const int n = std::min(F - off, kMaxFramesPerLaunch);
-        hipLaunchKernelGGL(mgpu_txgen_kernel, dim3(n), dim3(256), c->lds_tx, s, c->dev, uint64_t(0), uint64_t(0), n, 0.0, -1,
-                           bb + size_t(off) * t.frame_samples * 2, static_cast<uint8_t*>(nullptr),
-                           d_payload + size_t(off) * size_t(payload_stride < 0 ? -payload_stride : payload_stride), payload_stride, at(d_nbytes, size_t(off)), 0, 0);
-        HIPCK(hipGetLastError());
-    }
+    launch_txgen(c, 0, 0, F, 0.0, -1, bb, nullptr, s, d_payload, payload_stride, d_nbytes);
     const int kMaxY = 32768;                                   // gridDim.y limit is 65535
     for (int off = 0; off < F; off += kMaxY) {
         const int n = std::min(F - off, kMaxY);
@@ -314,7 +308,7 @@ void transmit_dev(mgpu_ctx* c, const uint8_t* d_payload, int payload_stride, con
                            cfg.carrier_amplitude, d_cs + (continuous ? 2 * size_t(used) * off : 0), continuous ? used : 0,
                            o, total);
         HIPCK(hipGetLastError());
-        hipLaunchKernelGGL(mgpu_peak_clip_kernel, dim3(n, 2), dim3(256), 0, s, o, total, npre * interp, used, pow_pre, pow_data);
+        hipLaunchKernelGGL(mgpu_peak_clip_kernel, dim3(n, 2), dim3(256), 0, s, o, total, npre * kInterp, used, pow_pre, pow_data);
         HIPCK(hipGetLastError());
         if (filtered && !batch && !stream_mode) {
             double* t1 = t1_all + size_t(off) * total;
@@ -481,7 +475,7 @@ int mgpu_generate_ack_pattern_passband(mgpu_ctx* c, int pattern, const mgpu_tran
         need(cfg && out && (pattern == 1 || pattern == 2), "bad argument (pattern: 1 = ACK, 2 = BREAK)");
         need(cfg->carrier_hz > 0 && cfg->carrier_hz < kSampleRate / 2 && cfg->output_power_watt >= 0, "bad carrier or power");
         const auto& t = c->tab;
-        const int interp = 4, nbb = kAckNsymb * t.Nofdm, total = nbb * interp;
+        const int nbb = kAckNsymb * t.Nofdm, total = nbb * kInterp;
         hipStream_t s = c->stream;
         TxState& st = tx_state(c, s);
         // cl_mfsk::generate_ack_pattern / generate_break_pattern (mfsk.cc:195-230): one tone per symbol, hopping
@@ -493,7 +487,7 @@ int mgpu_generate_ack_pattern_passband(mgpu_ctx* c, int pattern, const mgpu_tran
         HIPCK(hipMemcpyAsync(d_car.p, car.data(), car.size() * 16, hipMemcpyHostToDevice, s));
         launch_symbol_mod(c, d_car.as<double>(), kAckNsymb, d_bb.as<double>(), s);
         const double* const d_cs = ensure_carrier_table(st, cfg->carrier_hz, cfg->start_sample, size_t(total), s);
-        const float power_normalization = std::sqrt(double(t.Nfft * interp));                       // telecom_system.cc:1595
+        const float power_normalization = std::sqrt(double(t.Nfft * kInterp));                       // telecom_system.cc:1595
         const double ack_boost = std::sqrt(double(t.Nc) / 1) * std::pow(10.0, -2.0 / 20.0);         // :1611
         const double m = std::sqrt(cfg->output_power_watt) * ack_boost;
         hipLaunchKernelGGL(mgpu_tx_mix_kernel, dim3((total + 255) / 256, 1), dim3(256), 0, s, d_bb.as<double>(), nbb, static_cast<const double*>(nullptr), 0,

@@ -331,7 +331,7 @@ def test_ldpc_iteration_cap(max_iters):
 def test_ldpc_spa_look_policy_changes_no_bit_and_no_count(cfg, max_iters, weights, monkeypatch):
     """ldpc.hip "adaptive": in a frame's first iterations the syndrome of an iteration's posteriors is tested either by a pass of its own or
     inside the next check pass; a judged look's sampled syndrome weight decides how many of the following looks (0, 1 or 2) are taken the
-    second way (api.hip: MERCURY_SPA_SPEC_WEIGHT="first look: one, two; later looks: one, two"). Whatever the thresholds - the defaults,
+    second way (create.hip: MERCURY_SPA_SPEC_WEIGHT="first look: one, two; later looks: one, two"). Whatever the thresholds - the defaults,
     always inside the check pass, never, and mixtures that switch forms from look to look - bits and iteration counts are the reference's
     (ldpc_decoder_SPA.cc:176-196), at iteration caps that end a frame in either form."""
     monkeypatch.setenv("MERCURY_SPA_SPEC_WEIGHT", weights)
@@ -856,7 +856,7 @@ def test_ragged_batch_sizes(F):
 
 @pytest.mark.parametrize("pinned", [False, True])
 def test_host_path_in_several_chunks_equals_one_piece(pinned, monkeypatch):
-    """mgpu_rx_batch's double-buffered host path (api.hip: input chunks on a copy stream, kernels on another, results through page-locked
+    """mgpu_rx_batch's double-buffered host path (rx_batch.hip: input chunks on a copy stream, kernels on another, results through page-locked
     staging) cut into many chunks with a ragged tail - pageable and page-locked input take different stream schedules - returns what
     the same call in one piece returns, frame for frame (payload bytes, stats records, LLRs), and what the oracle returns."""
     from mercury_amd.physical_layer import pinned_empty
@@ -1019,7 +1019,7 @@ def test_degenerate_inputs_behave_like_the_reference(cfg):
 
 
 def test_single_frame_graph_path_equals_batched_path():
-    """mgpu_rx_batch with F = 1 replays a captured hipGraph over fixed staging buffers (api.hip:rx_one_frame): many
+    """mgpu_rx_batch with F = 1 replays a captured hipGraph over fixed staging buffers (rx_batch.hip:rx_one_frame): many
     different frames through it, interleaved with batched calls, give exactly what the batched path gives."""
     cfg = 8
     orc = Oracle(cfg, 50)
