@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "mercury_estimator.h"
 #include "mercury_gpu.h"
 #include "mercury_rxloop.h"
 #include "mercury_stages.h"
@@ -235,6 +236,8 @@ public:
         mfsk_ctrl_mode = enable;
         select(enable ? 1 : 0);
     }
+    // not in the reference: an estimator ladder on the current context (mercury_estimator.h; off by default, lost when the configuration changes)
+    void set_estimator_ladder(const std::vector<mgpu_ls_window>& rungs) { detail::check(mgpu_set_estimator_ladder(ctx_, rungs.data(), int(rungs.size())), ctx_, "set_estimator_ladder"); }
     int get_active_nsymb() const { return info.active_nsymb; }                // telecom_system.h: get_active_nsymb()
     // char cl_telecom_system::get_configuration(double SNR) — telecom_system.cc:3036-3108: the fastest mode whose threshold the
     // measured SNR clears (the thresholds of common_defines.h:130-147 as that function states them)

@@ -248,6 +248,25 @@ int device_numa_node(int device) {
     return mgpu_host_numa_node_of_pci(id);
 }
 
+bool explicit_params_from(const mgpu_explicit_params* xp_in, mgpu::ExplicitParams& xp, std::string& err, int* rc) {
+    if (xp_in) {
+        // the kernels are specialised for the reference's carrier count, transform length and pilot column step: those fields only confirm them
+        if ((xp_in->Nc != 0 && xp_in->Nc != 50) || (xp_in->Nfft != 0 && xp_in->Nfft != 256) || (xp_in->Dx != 0 && xp_in->Dx != 1)) {
+            err = "explicit parameters: Nc / Nfft / Dx other than 50 / 256 / 1 are not supported (the kernels are specialised for them)";
+            *rc = MGPU_ERR_UNSUPPORTED; return false;
+        }
+        if (xp_in->Dy < 0 || xp_in->Dy > 255 || xp_in->Nsymb < 0 || xp_in->Nsymb > 255) { err = "explicit parameters: Dy / Nsymb must be 0 (the reference's default) .. 255"; *rc = MGPU_ERR_ARG; return false; }
+        if (xp_in->Dy != 0) xp.Dy = xp_in->Dy;
+        xp.Nsymb = xp_in->Nsymb;
+        if (xp_in->pilot_boost != 0.0f) xp.pilot_boost = xp_in->pilot_boost;
+        if (xp_in->ls_window != 0) xp.ls_window = xp_in->ls_window;
+        if (xp_in->ls_window < 0 || xp_in->ls_window > 21) { err = "explicit parameters: ls_window must be 1..21 (0 = the reference's 20)"; *rc = MGPU_ERR_ARG; return false; }
+        if (!(xp.pilot_boost > 0.0f) || !(xp.pilot_boost < 1e6f)) { err = "explicit parameters: pilot_boost must be positive and finite (0 = the reference's 1.33)"; *rc = MGPU_ERR_ARG; return false; }
+        if (xp_in->seeds_set) { xp.pilot_seed = xp_in->pilot_seed; xp.scrambler_seed = xp_in->scrambler_seed; xp.preamble_seed = xp_in->preamble_seed; }
+    }
+    return true;
+}
+
 }  // namespace mgpu_detail
 
 extern "C" {
@@ -261,20 +280,9 @@ int mgpu_create_explicit(const mgpu_config* cfg, const mgpu_explicit_params* xp_
     *out = nullptr;
     mgpu_internal_libm_notice();                 // only with MERCURY_GPU_LIBM_CHECK=1: is the host's libm the one the device restates? (once per process; stderr only if not)
     mgpu::ExplicitParams xp;
-    if (xp_in) {
-        // the kernels are specialised for the reference's carrier count, transform length and pilot column step: those fields only confirm them
-        if ((xp_in->Nc != 0 && xp_in->Nc != 50) || (xp_in->Nfft != 0 && xp_in->Nfft != 256) || (xp_in->Dx != 0 && xp_in->Dx != 1)) {
-            g_create_error = "explicit parameters: Nc / Nfft / Dx other than 50 / 256 / 1 are not supported (the kernels are specialised for them)";
-            return MGPU_ERR_UNSUPPORTED;
-        }
-        if (xp_in->Dy < 0 || xp_in->Dy > 255 || xp_in->Nsymb < 0 || xp_in->Nsymb > 255) { g_create_error = "explicit parameters: Dy / Nsymb must be 0 (the reference's default) .. 255"; return MGPU_ERR_ARG; }
-        if (xp_in->Dy != 0) xp.Dy = xp_in->Dy;
-        xp.Nsymb = xp_in->Nsymb;
-        if (xp_in->pilot_boost != 0.0f) xp.pilot_boost = xp_in->pilot_boost;
-        if (xp_in->ls_window != 0) xp.ls_window = xp_in->ls_window;
-        if (xp_in->ls_window < 0 || xp_in->ls_window > 21) { g_create_error = "explicit parameters: ls_window must be 1..21 (0 = the reference's 20)"; return MGPU_ERR_ARG; }
-        if (!(xp.pilot_boost > 0.0f) || !(xp.pilot_boost < 1e6f)) { g_create_error = "explicit parameters: pilot_boost must be positive and finite (0 = the reference's 1.33)"; return MGPU_ERR_ARG; }
-        if (xp_in->seeds_set) { xp.pilot_seed = xp_in->pilot_seed; xp.scrambler_seed = xp_in->scrambler_seed; xp.preamble_seed = xp_in->preamble_seed; }
+    {
+        int rc = MGPU_OK;
+        if (!mgpu_detail::explicit_params_from(xp_in, xp, g_create_error, &rc)) return rc;
     }
     int em, er, ep, ee;
     if (!((cfg->cfg >= 0 && cfg->cfg <= 16) || (cfg->cfg >= 100 && cfg->cfg <= 102) || mgpu::explicit_mode_row(cfg->cfg, &em, &er, &ep, &ee))) {

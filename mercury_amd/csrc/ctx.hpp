@@ -15,7 +15,9 @@
 #include "../../include/mercury_gpu.h"
 #include "../../include/mercury_rxloop.h"
 #include "../../include/mercury_channel.h"
+#include "../../include/mercury_estimator.h"
 #include "device_tables.h"
+#include "ls_rect.h"
 #include "tables.hpp"
 
 extern "C" const unsigned char mgpu_ldpc_blob[];
@@ -29,6 +31,11 @@ extern "C" size_t mgpu_txgen_lds_bytes(int G);
 
 extern "C" __global__ void mgpu_frontend_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
 extern "C" __global__ void mgpu_frontend_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
+extern "C" __global__ void mgpu_frontend_rect_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
+extern "C" __global__ void mgpu_frontend_rect_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
+extern "C" __global__ void mgpu_ladder_select_kernel(const MgpuStatsDev*, int, int, int*, int*, int*, unsigned long long*);
+extern "C" __global__ void mgpu_ladder_merge_kernel(const int*, int, int, int, int, const float*, const float*, const float*, const double*, const uint8_t*,
+                                                    const MgpuStatsDev*, float*, float*, float*, double*, uint8_t*, MgpuStatsDev*, int*, unsigned long long*);
 extern "C" __global__ void mgpu_mfsk_frontend_kernel_m32(MgpuDev, const double*, int, int, float*, float*, float*, MgpuTapsDev);
 extern "C" __global__ void mgpu_mfsk_frontend_kernel_m16x2(MgpuDev, const double*, int, int, float*, float*, float*, MgpuTapsDev);
 extern "C" int mgpu_mfsk_syms_per_block();
@@ -137,6 +144,26 @@ DevArray<T> upload(const std::vector<T>& v) {
     return d;
 }
 
+// The estimator ladder of a context (include/mercury_estimator.h; ladder.hip). n == 0: none, every entry point as without it.
+struct Ladder {
+    int n = 0;
+    mgpu_ls_window rung[MGPU_LADDER_MAX]{};
+    MgpuLsRect win[MGPU_LADDER_MAX]{};              // rung r as the rectangular front-end takes it (frames = NULL)
+    DevArray<double> weight[MGPU_LADDER_MAX];       // win[r].weight
+    bool rung0_is_default = false;                  // rung 0 is the context's own square window: the default kernel runs it
+    DevArray<int> d_rung;                           // [max_batch] winning rung per frame of the last call, -1 = none
+    DevArray<unsigned long long> d_counters;        // [MGPU_LADDER_MAX + 1] frames decoded by rung r; frames seen
+    // a retry's compact workspaces, [max_batch] each, created with the first ladder of more than one rung
+    DevArray<int> d_idx, d_count;
+    DevArray<float> d_llr, d_var, d_snrvar;
+    DevArray<double> d_meanh;
+    DevArray<uint8_t> d_payload;
+    DevArray<MgpuStatsDev> d_stats;
+    Event done;                                     // behind the last retry: the next one, on whatever stream, waits for the workspaces
+    bool done_recorded = false;
+    int last_F = 0;                                 // frames of the last fused-span call
+};
+
 struct Workspace;   // rxloop.hip
 struct TxState;     // tx.hip
 struct Release { void operator()(Workspace*) const; void operator()(TxState*) const; };   // defined where each type is complete
@@ -183,6 +210,7 @@ struct mgpu_ctx {
     std::unique_ptr<TxState, Release> tx_state;      // transmit path: preamble baseband, filter taps, carrier table (tx.hip)
     std::vector<double> pre_eq;     // [Nc][2] installed pre_equalization_channel (empty: none); dev.pre_eq is its device copy
     DevArray<double> d_pre_eq_buf;  // device copy of pre_eq
+    Ladder lad;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     PinnedBuf h_out;                // page-locked staging for the payloads + stats of a pipelined call ([max_batch])
@@ -227,6 +255,15 @@ inline FrontendKernel fe_kernel(int threads) { return threads == 1024 ? mgpu_fro
 // frame0: index of the call's first frame inside the context's max_batch-sized workspaces (the ZF modes keep their equalised symbols there)
 void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, const MgpuTapsDev& taps,
                      hipStream_t s, int frame_stride = 0, int frame0 = 0);
+// The estimator ladder behind rung 0 (ladder.hip), to be called right after launch_frontend + launch_decoder on the same arrays and stream:
+// marks each frame's rung and, rung by rung, re-runs the frames still undecoded and merges the ones that decode. Nothing without a ladder.
+// d_mean_H: the front-end's mean_H tap where the caller reads it, or null. Waits for the stream once per rung (the retry's frame count).
+void launch_ladder(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, uint8_t* d_payload, MgpuStatsDev* d_stats,
+                   double* d_mean_H, hipStream_t s, int frame_stride = 0, int frame0 = 0);
+void launch_frontend_rect(mgpu_ctx* c, const MgpuLsRect& win, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, const MgpuTapsDev& taps,
+                          hipStream_t s, int frame_stride);
+// mgpu_explicit_params as the table builder takes them; false (and *rc, err) when they are refused (create.hip)
+bool explicit_params_from(const mgpu_explicit_params* in, mgpu::ExplicitParams& xp, std::string& err, int* rc);
 void launch_zf_snr(mgpu_ctx* c, int F, const uint8_t* d_payload, MgpuStatsDev* d_stats, hipStream_t s, int frame0 = 0, double* d_var_out = nullptr);
 void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
                     const float* d_var, const float* d_snrvar, hipStream_t s);

@@ -25,6 +25,7 @@
 #include "device_tables.h"
 #include "fft256.h"
 #include "fe_math.h"
+#include "ls_rect.h"
 
 namespace {
 
@@ -105,10 +106,12 @@ __host__ __device__ inline FeCarve fe_carve(int G, int nPilots, int nBits, int F
 }
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve(G, nPilots, nBits, threads / 64).total; }
 
-template <int FE_THREADS>
+// RECT: the LS window has a width and a height of its own (`win`, ls_rect.h) instead of T.lsw squared, and the workgroup may take its
+// frame from a list: the form the estimator ladder runs (ladder.hip). Everything else is the one body.
+template <int FE_THREADS, bool RECT>
 __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
                                          float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out,
-                                         const MgpuTapsDev& taps) {
+                                         const MgpuTapsDev& taps, const MgpuLsRect& win) {
     constexpr int FE_WAVES = FE_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int G = T.G, Nc = 50, Ns = T.Nsymb;
@@ -127,7 +130,9 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f = blockIdx.x;
     if (f >= F) return;
-    const c2* bb = reinterpret_cast<const c2*>(baseband) + size_t(f) * T.frame_samples;
+    int fin = f;                                                    // the frame read; f is the row written
+    if constexpr (RECT) { if (win.frames) fin = win.frames[f]; }
+    const c2* bb = reinterpret_cast<const c2*>(baseband) + size_t(fin) * T.frame_samples;
     const double boost = T.pilot_boost;
     int stamp_i = 0;
 #define FE_STAMP() do { if (taps.cycles && f == (F >> 1) && tid == 0) taps.cycles[stamp_i] = __builtin_readcyclecounter(); ++stamp_i; } while (0)    /* a frame from the middle of the launch: the compute unit is in its steady mix of phases */
@@ -181,8 +186,10 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 
     FE_STAMP();   // 2: AGC done
     // ---- channel estimate at the pilots -------------------------------------------------------
-    const int hw = T.lsw / 2;
-    const bool ls_fast = T.estimator != 0 && T.regular_lattice;
+    const int hwt = RECT ? win.hw_t : T.lsw / 2, hwf = RECT ? win.hw_f : T.lsw / 2;      // half-widths in time (rows) and frequency (columns)
+    const int lattice = RECT ? win.lattice : T.regular_lattice;
+    const double* __restrict__ ls_weight = RECT ? win.weight : T.ls_weight;
+    const bool ls_fast = T.estimator != 0 && lattice;
     int ls_rows = 0;     // 1: every window row holds >= 3 pilots and every pilot of the frame is finite -> the branch-free row loop below
     if (ls_fast) {       // x*y for the LS sums: the pilot's sign applied once ((-w)*y == w*(-y) exactly), in pilot order
         int finite = 1;
@@ -193,15 +200,15 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
             yp[p] = type[q] < 0 ? c2{-y.re, -y.im} : y;
             finite &= (fabs(y.re) < __builtin_inf()) & (fabs(y.im) < __builtin_inf());
         }
-        ls_rows = __syncthreads_and(finite) && T.regular_lattice == 2;
+        ls_rows = __syncthreads_and(finite) && lattice == 2;
     }
     for (int p = tid; p < T.nPilots; p += FE_THREADS) {
         const int c = T.pilot_cell[p], i = c / Nc, j = c - i * Nc;
         if (T.estimator == 0) {            // ZF: Y / (x + 0i) reduces to two real divisions in __divdc3
             const double x = type[c] < 0 ? -boost : boost;
             Hp[p] = {grid[c].re / x, grid[c].im / x};
-        } else {                           // LS over the (clipped) 21x21 window, row-major order
-            const int k0 = max(i - hw, 0), k1 = min(i + hw, Ns - 1), l0 = max(j - hw, 0), l1 = min(j + hw, Nc - 1);
+        } else {                           // LS over the (clipped) window - 21x21 unless RECT -, row-major order
+            const int k0 = max(i - hwt, 0), k1 = min(i + hwt, Ns - 1), l0 = max(j - hwf, 0), l1 = min(j + hwf, Nc - 1);
             double hr = 0, hi = 0;
             if (ls_fast) {
                 // pilots of row k sit at columns == k (mod 3); rows hold 17,17,16 pilots cyclically, so the pilot
@@ -220,7 +227,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
                     int r = k0 % 3;
                     for (int k = k0; k <= k1; ++k) { n += r == 0 ? cntr[0] : r == 1 ? cntr[1] : cntr[2]; r = r == 2 ? 0 : r + 1; }
                 }
-                const double w = T.ls_weight[n];
+                const double w = ls_weight[n];
                 if (ls_rows) {
                     // Rows k0, k0+1, k0+2, k0+3, ... cycle through the three column residues, so a lane's (pilot count, first pilot) pair of a
                     // row depends only on the row's place in that cycle. A row's first three pilots are always inside the window; pilots
@@ -278,7 +285,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
                 int n = 0;
                 for (int k = k0; k <= k1; ++k)
                     for (int l = l0; l <= l1; ++l) n += type[k * Nc + l] != 0;
-                const double w = T.ls_weight[n];
+                const double w = ls_weight[n];
                 for (int k = k0; k <= k1; ++k)
                     for (int l = l0; l <= l1; ++l) {
                         const int q = k * Nc + l;
@@ -446,11 +453,25 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<512>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps);
+    fe_frame<512, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<1024>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps);
+    fe_frame<1024, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{});
+}
+
+// The same body with a rectangular LS window and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when
+// it is not the context's own window, and every later rung on the frames that rung left undecoded.
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_rect_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
+    fe_frame<512, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
+    fe_frame<1024, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win);
 }

@@ -34,6 +34,11 @@ void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float
         if (c->timing) HIPCK(hipEventRecord(c->ev[slot][1], s));
         return;
     }
+    if (c->lad.n > 0 && !c->lad.rung0_is_default) {     // rung 0 of an estimator ladder with a window of its own (ladder.hip)
+        launch_frontend_rect(c, c->lad.win[0], d_bb, F, d_llr, d_var, d_snrvar, taps, s, frame_stride);
+        if (c->timing) HIPCK(hipEventRecord(c->ev[slot][1], s));
+        return;
+    }
     for_frame_chunks(F, [&](int off, int n) {
         if (off && (taps.grid || taps.H || taps.eq || taps.syms || taps.llr_demod || taps.variance || taps.agc_gain || taps.mean_H))
             throw std::invalid_argument("stage taps are limited to 2^21 frames per call");

@@ -1,0 +1,11 @@
+// One LS estimator window of its own width and height (include/mercury_estimator.h) as the front-end's rectangular
+// instantiation takes it (frontend.hip), and the frame list of a ladder retry (ladder.hip). A kernel argument of its own:
+// MgpuDev (device_tables.h) stays what the default kernels and the decoder are built from.
+#pragma once
+
+struct MgpuLsRect {
+    const double* weight;   // [width*height+1] boost / sum_n(boost^2) per window population n (tables.cpp ls_weight_table)
+    const int* frames;      // workgroup b reads frame frames[b] and writes row b of compact outputs; NULL: frame b
+    int hw_f, hw_t;         // half-widths: frequency (columns) and time (rows)
+    int lattice;            // MgpuDev::regular_lattice evaluated for this width: 2 = every clipped window row holds >= 3 pilots of each column residue
+};

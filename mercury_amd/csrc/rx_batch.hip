@@ -89,6 +89,8 @@ int mgpu_rx_batch_dev(mgpu_ctx* c, const void* d_bb, int F, void* d_payload, voi
         launch_frontend(c, static_cast<const double*>(d_bb), F, llr, c->d_variance, c->d_snrvar, taps, s);
         launch_decoder(c, llr, F, nullptr, nullptr, static_cast<uint8_t*>(d_payload), static_cast<MgpuStatsDev*>(d_stats),
                        c->d_variance, c->d_snrvar, s);
+        launch_ladder(c, static_cast<const double*>(d_bb), F, llr, c->d_variance, c->d_snrvar, static_cast<uint8_t*>(d_payload),
+                      static_cast<MgpuStatsDev*>(d_stats), nullptr, s);
         launch_zf_snr(c, F, static_cast<uint8_t*>(d_payload), static_cast<MgpuStatsDev*>(d_stats), s);
     });
 }
@@ -161,6 +163,7 @@ int mgpu_rx_batch_taps(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, m
         }
         launch_frontend(c, c->d_baseband, F, c->d_llr, c->d_variance, c->d_snrvar, dt, s);
         launch_decoder(c, c->d_llr, F, nullptr, nullptr, c->d_payload, c->d_stats, c->d_variance, c->d_snrvar, s);
+        launch_ladder(c, c->d_baseband, F, c->d_llr, c->d_variance, c->d_snrvar, c->d_payload, c->d_stats, nullptr, s);      // the taps stay rung 0's
         launch_zf_snr(c, F, c->d_payload, c->d_stats, s);
         if (payload) HIPCK(hipMemcpyAsync(payload, c->d_payload, size_t(F) * t.payload_stride, hipMemcpyDeviceToHost, s));
         if (stats) HIPCK(hipMemcpyAsync(stats, c->d_stats, size_t(F) * sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, s));
@@ -289,9 +292,13 @@ static void rx_batch_pipelined(mgpu_ctx* c, const double* bb, int F, uint8_t* pa
             HIPCK(hipStreamWaitEvent(ks, p.copied, 0));
         }
         launch_frontend(c, p.d_in, n, c->d_llr + size_t(off) * t.N, c->d_variance + off, c->d_snrvar + off, none, ks, 0, off);
-        if (pinned) HIPCK(hipEventRecord(p.done, ks));               // the front-end is the only reader of the input buffer
+        const bool retries = c->lad.n > 1;                           // an estimator ladder's retries read the input again
+        if (pinned && !retries) HIPCK(hipEventRecord(p.done, ks));   // the front-end is the only reader of the input buffer
         launch_decoder(c, c->d_llr + size_t(off) * t.N, n, nullptr, nullptr, c->d_payload + size_t(off) * t.payload_stride, c->d_stats + off,
                        c->d_variance + off, c->d_snrvar + off, ks);
+        launch_ladder(c, p.d_in, n, c->d_llr + size_t(off) * t.N, c->d_variance + off, c->d_snrvar + off, c->d_payload + size_t(off) * t.payload_stride,
+                      c->d_stats + off, nullptr, ks, 0, off);
+        if (pinned && retries) HIPCK(hipEventRecord(p.done, ks));
         launch_zf_snr(c, n, c->d_payload + size_t(off) * t.payload_stride, c->d_stats + off, ks, off);
         if (payload) HIPCK(hipMemcpyAsync(h_payload + size_t(off) * t.payload_stride, c->d_payload + size_t(off) * t.payload_stride,
                                           size_t(n) * t.payload_stride, hipMemcpyDeviceToHost, ks));
@@ -318,7 +325,8 @@ int mgpu_host_path_last(mgpu_ctx* c, int* chunk_frames, int* n_chunks, float* fi
 }
 
 int mgpu_rx_batch(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, mgpu_frame_stats* stats, float* llr_opt) {
-    if (c && bb && F == 1 && !llr_opt && !c->timing && c->max_batch >= 1 && !std::getenv("MERCURY_NO_GRAPH"))
+    // (an estimator ladder's retry depends on the frame's result: it does not go into the captured graph)
+    if (c && bb && F == 1 && !llr_opt && !c->timing && c->max_batch >= 1 && c->lad.n == 0 && !std::getenv("MERCURY_NO_GRAPH"))
         return rx_one_frame(c, bb, payload, stats);
     if (c && bb && F > 1 && F <= c->max_batch && !llr_opt && !c->timing && !std::getenv("MERCURY_NO_PIPELINE"))
         return guard(c, [&] { rx_batch_pipelined(c, bb, F, payload, stats); });

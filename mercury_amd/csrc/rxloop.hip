@@ -662,6 +662,9 @@ struct Loop {
         if (!mfsk) taps.mean_H = ws.d_meanh.as<double>();
         launch_frontend(c, ws.d_frames.as<double>() + size_t(pre) * t.Nofdm * 2, n, c->d_llr, c->d_variance, c->d_snrvar, taps, s, frame_n);
         launch_decoder(c, c->d_llr, n, nullptr, nullptr, ws.d_payload_k.as<uint8_t>(), ws.d_stats_k.as<MgpuStatsDev>(), c->d_variance, c->d_snrvar, s);
+        // an estimator ladder retries inside this trial, before the host looks: a window a later rung decodes counts as decoded here
+        launch_ladder(c, ws.d_frames.as<double>() + size_t(pre) * t.Nofdm * 2, n, c->d_llr, c->d_variance, c->d_snrvar, ws.d_payload_k.as<uint8_t>(),
+                      ws.d_stats_k.as<MgpuStatsDev>(), taps.mean_H, s, frame_n);
         // receive_stats.SNR is a double (telecom_system.cc:1343-1396): 10 log10(1 / variance) of the float variance (LS modes), -10 log10 of
         // the re-encoded symbols' error power (ZF modes). The kernels' records carry it as a float (the mgpu_frame_stats ABI); here the
         // argument of the logarithm comes back and the host takes it with the libm the reference calls: the double equals the reference's.

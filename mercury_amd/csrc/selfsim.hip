@@ -42,6 +42,7 @@ static int baseband_test_esn0_impl(mgpu_ctx* c, const double* esn0_db, int npoin
                 MgpuTapsDev taps{};
                 launch_frontend(c, d_bb.as<double>(), n, c->d_llr, c->d_variance, c->d_snrvar, taps, s);
                 launch_decoder(c, c->d_llr, n, nullptr, nullptr, c->d_payload, c->d_stats, c->d_variance, c->d_snrvar, s);
+                launch_ladder(c, d_bb.as<double>(), n, c->d_llr, c->d_variance, c->d_snrvar, c->d_payload, c->d_stats, nullptr, s);
                 hipLaunchKernelGGL(mgpu_error_count_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_sent.as<uint8_t>(), c->d_payload, c->d_stats,
                                    t.payload_stride, t.nReal, n, d_acc.as<unsigned long long>());
                 HIPCK(hipGetLastError());

@@ -646,6 +646,16 @@ bool explicit_mode_row(int cfg, int* M, int* rate16, int* preamble, int* estimat
     return true;
 }
 
+std::vector<double> ls_weight_table(double pilot_boost, int max_population) {
+    std::vector<double> w(size_t(max_population) + 1, 0.0);
+    double s = 0;
+    for (size_t n = 1; n < w.size(); ++n) {
+        s += pilot_boost * pilot_boost;
+        w[n] = pilot_boost * (1.0 / s);
+    }
+    return w;
+}
+
 ModeTables build_mode_tables(int cfg, int mfsk_ctrl_mode, const uint8_t* blob, size_t blob_size, const ExplicitParams& xp) {
     const bool robust = cfg >= 100 && cfg <= 102;                             // common_defines.h:63-65
     ModeRow explicit_row = {0, 0, 0, 0};
@@ -764,14 +774,7 @@ ModeTables build_mode_tables(int cfg, int mfsk_ctrl_mode, const uint8_t* blob, s
         for (int p = 0; p < t.N; ++p) t.llr_dst[t.llr_src[p]] = uint16_t(p);
     }
     // LS weights: x' = x / sum(x*x) with x = +-boost, sums accumulated sequentially (misc.cc:73-91)
-    t.ls_weight.assign(size_t(t.lsw) * t.lsw + 1, 0.0);
-    {
-        double s = 0;
-        for (size_t n = 1; n < t.ls_weight.size(); ++n) {
-            s += t.pilot_boost * t.pilot_boost;
-            t.ls_weight[n] = t.pilot_boost * (1.0 / s);
-        }
-    }
+    t.ls_weight = ls_weight_table(t.pilot_boost, t.lsw * t.lsw);
     // ---- TX permutations (synthetic generator only) ----------------------------------------
     t.bit_il.resize(t.nBits);
     for (int i = 0; i < t.nBits; ++i) t.bit_il[bd[i]] = uint16_t(i);  // interleaver is the inverse gather: out[bd[i]] = in[i]

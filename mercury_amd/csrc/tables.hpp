@@ -116,6 +116,10 @@ struct ModeTables {
 // Throws std::runtime_error on a bad cfg or unreadable/corrupt table blob.
 ModeTables build_mode_tables(int cfg, int mfsk_ctrl_mode, const uint8_t* ldpc_blob, size_t ldpc_blob_size, const ExplicitParams& xp = ExplicitParams());
 
+// LS weights by window population n = 0..max_population: x' = x / sum(x*x) with x = +-boost, the sum accumulated sequentially
+// (misc.cc:73-91). ModeTables::ls_weight is this for lsw*lsw; an estimator ladder keeps one per rung, for width*height
+std::vector<double> ls_weight_table(double pilot_boost, int max_population);
+
 uint16_t crc16_modbus(const uint8_t* bytes, int n);
 
 // pre_equalization_channel of a freshly loaded configuration for a given carrier (telecom_system.cc:3108-3145): [Nc]

@@ -126,6 +126,48 @@ EXPORTED_SYMBOLS = [
 ]
 
 
+# ---- rectangular LS windows and the estimator ladder (include/mercury_estimator.h) -------------------------------
+ESTIMATOR_SYMBOLS = ["mgpu_set_estimator_ladder", "mgpu_get_estimator_ladder", "mgpu_estimator_rungs_last", "mgpu_estimator_ladder_counters",
+                     "mgpu_host_ls_estimate"]
+LADDER_MAX = 4
+
+
+class LsWindow(C.Structure):      # mgpu_ls_window
+    _fields_ = [("width", C.c_int), ("height", C.c_int)]
+
+
+def parse_ladder(text):
+    """'21x21,5x21' -> [(21, 21), (5, 21)] (width = carriers, height = symbols); '' or None -> []"""
+    if not text:
+        return []
+    return [tuple(int(v) for v in rung.lower().split("x")) for rung in text.split(",")]
+
+
+def host_ls_estimate(cfg, grid, width, height, explicit=None):
+    """mgpu_host_ls_estimate: the LS estimate at the pilot cells (row-major pilot order, complex128 [nPilots]) of one frame grid
+    (complex128 [Nsymb * Nc], after the AGC) for a width x height window; no GPU. explicit: as RxPhy's."""
+    lib = load_library()
+    lib.mgpu_host_ls_estimate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    g = np.ascontiguousarray(grid, np.complex128).ravel()
+    xp = None
+    if explicit:
+        seeds = any(k in explicit for k in ("pilot_seed", "scrambler_seed", "preamble_seed"))
+        xp = ExplicitParams(float(explicit.get("pilot_boost", 0.0)), int(explicit.get("ls_window", 0)), 1 if seeds else 0,
+                            int(explicit.get("pilot_seed", 0)), int(explicit.get("scrambler_seed", 0)), int(explicit.get("preamble_seed", 1)),
+                            int(explicit.get("Nc", 0)), int(explicit.get("Nfft", 0)), int(explicit.get("Dx", 0)), int(explicit.get("Dy", 0)),
+                            int(explicit.get("Nsymb", 0)))
+    ref = C.byref(xp) if xp is not None else None
+    # nPilots of the (possibly explicit) geometry: the entries a call on an all-zero grid writes
+    count = np.full(g.size, np.nan + 0j, np.complex128)
+    rc = lib.mgpu_host_ls_estimate(cfg, ref, int(width), int(height), _ptr(np.zeros_like(g)), _ptr(count))
+    if rc != 0:
+        raise MgpuError("mgpu_host_ls_estimate failed (%d)" % rc)
+    out = np.zeros(int(np.count_nonzero(~np.isnan(count.real))), np.complex128)
+    if lib.mgpu_host_ls_estimate(cfg, ref, int(width), int(height), _ptr(g), _ptr(out)) != 0:
+        raise MgpuError("mgpu_host_ls_estimate failed")
+    return out
+
+
 # ---- Watterson HF fading channel (include/mercury_channel.h, DESIGN.md §6.1) ----------------------------------------------------
 HF_MAX_PATHS, HF_SINUSOIDS = 4, 32
 HF_PRESETS = {"awgn": 0, "good": 1, "moderate": 2, "poor": 3, "flutter": 4}
@@ -308,6 +350,37 @@ class RxPhy:
             self.close()
         except Exception:
             pass
+
+    # ---- estimator ladder (include/mercury_estimator.h) ----------------------------------------
+    def set_estimator_ladder(self, rungs):
+        """rungs: [(width, height), ...] in cells (carriers x symbols), at most LADDER_MAX; [] or None: no ladder. Frames whose CRC fails are
+        re-estimated and decoded again with the next rung, on the device, in every receive entry point of this context."""
+        rungs = list(rungs or [])
+        arr = (LsWindow * max(len(rungs), 1))(*[LsWindow(int(w), int(h)) for w, h in rungs])
+        self.lib.mgpu_set_estimator_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._ck(self.lib.mgpu_set_estimator_ladder(self.h, arr if rungs else None, len(rungs)))
+
+    @property
+    def estimator_ladder(self):
+        """the rungs as they are applied (odd sides): [(width, height), ...]"""
+        arr, n = (LsWindow * LADDER_MAX)(), C.c_int()
+        self.lib.mgpu_get_estimator_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._ck(self.lib.mgpu_get_estimator_ladder(self.h, arr, C.byref(n)))
+        return [(arr[r].width, arr[r].height) for r in range(n.value)]
+
+    def last_rungs(self, F):
+        """winning rung of each of the first F frames of the last receive call, -1 where no rung decoded: int32 [F]"""
+        out = np.zeros(F, np.int32)
+        self.lib.mgpu_estimator_rungs_last.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._ck(self.lib.mgpu_estimator_rungs_last(self.h, _ptr(out), F))
+        return out
+
+    def ladder_counters(self, reset=False):
+        """(frames decoded by each rung: int64 [LADDER_MAX], frames seen) since the ladder was set or the last reset"""
+        by, n = np.zeros(LADDER_MAX, np.int64), C.c_longlong()
+        self.lib.mgpu_estimator_ladder_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        self._ck(self.lib.mgpu_estimator_ladder_counters(self.h, _ptr(by), C.byref(n), 1 if reset else 0))
+        return by, int(n.value)
 
     # ---- host-buffer entry points -------------------------------------------------------------
     def receive(self, baseband, taps=False, want_llr=False):
@@ -954,8 +1027,11 @@ class RxCapture:
     context's device, read in place)."""
 
     def __init__(self, rx, S, carrier_hz, trials_max=2, use_last_good_time_sync=1, use_last_good_freq_offset=1, coarse_freq_sync=0,
-                 initial_windows=None, max_hops=0):
+                 initial_windows=None, max_hops=0, ladder=None):
+        """ladder: [(width, height), ...] set on the context `rx` (RxPhy.set_estimator_ladder) before the capture is made; None: as it is"""
         self.rx, self.lib, self.S = rx, rx.lib, S
+        if ladder is not None:
+            rx.set_estimator_ladder(ladder)
         self.h = C.c_void_p()
         cfg = ReceiveConfig(carrier_hz, trials_max, use_last_good_time_sync, use_last_good_freq_offset, coarse_freq_sync)
         init = None
@@ -1153,8 +1229,11 @@ class LinkSim:
     """S simplex links (transmitter -> streaming HF channel -> noise -> the capture receive loop) on one RxPhy context
     (include/mercury_linksim.h). config: linksim_config(...); esn0_db: None (no noise), a number or [S]."""
 
-    def __init__(self, rx, config, esn0_db=None):
+    def __init__(self, rx, config, esn0_db=None, ladder=None):
+        """ladder: [(width, height), ...] set on the context `rx` (RxPhy.set_estimator_ladder) before the simulator is made; None: as it is"""
         self.rx, self.lib, self.S, self.config = rx, rx.lib, config.S, config
+        if ladder is not None:
+            rx.set_estimator_ladder(ladder)
         self.h = C.c_void_p()
         lib = self.lib
         lib.mgpu_linksim_create.argtypes = [C.c_void_p, C.POINTER(LinkSimConfig), C.c_void_p, C.POINTER(C.c_void_p)]

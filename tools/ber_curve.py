@@ -8,7 +8,9 @@ prints EsN0;BER;FER lines like the reference does, for far more frames per point
 (the CCIR 520 presets; awgn = identity, which gives exactly the plain loop's numbers). Without it the plain AWGN entry points run.
 --threshold (with --passband: ber_curve.py --passband [--channel C] --threshold cfg [frames_per_point]): Es/N0 from 3 dB below the
 reference's AWGN FER < 0.1 value (include/common/common_defines.h:130-147) to 40 dB above it in 1 dB steps, in one call; one JSON line
-gives the first point of the first run of three with FER < 0.1 ("fer01_esn0_db", null if none) beside the AWGN value."""
+gives the first point of the first run of three with FER < 0.1 ("fer01_esn0_db", null if none) beside the AWGN value.
+--ladder 21x21,5x21 (any form): an estimator ladder (include/mercury_estimator.h; windows as carriers x symbols) on the context; the JSON
+line then carries the frames each rung decoded."""
 import json
 import os
 import sys
@@ -25,18 +27,30 @@ AWGN_FER01 = {0: -10.0, 1: -7.5, 2: -6.0, 3: -4.5, 4: -3.5, 5: -2.5, 6: -1.5, 7:
               14: 9.0, 15: 12.5, 16: 13.5}
 
 
+LADDER = []          # --ladder
+
+
+def _ladder_fields(rx):
+    if not LADDER:
+        return {}
+    by, frames = rx.ladder_counters()
+    return {"ladder": ["%dx%d" % r for r in rx.estimator_ladder], "decoded_by_rung": [int(v) for v in by[: len(LADDER)]], "ladder_frames": frames}
+
+
 def threshold(cfg, n, channel):
     """One call over Es/N0 = AWGN value - 3 dB ... + 40 dB in 1 dB steps; the first point of the first run of three with FER < 0.1."""
     rx = RxPhy(cfg, max_batch=min(n, 1024))
+    rx.set_estimator_ladder(LADDER)
     pts = AWGN_FER01.get(cfg, -20.0) - 3.0 + np.arange(44, dtype=np.float64)
     t0 = time.perf_counter()
     res = rx.passband_test_esn0(pts, n, 1500.0, seed=2024, output_power_watt=1.0, hf_channel=channel)
+    extra = _ladder_fields(rx)
     rx.close()
     fer = [r["FER"] for r in res]
     first = next((float(pts[i]) for i in range(len(pts) - 2) if max(fer[i: i + 3]) < 0.1), None)
     print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "frames_per_point": n, "fer01_esn0_db": first,
                       "awgn_reference_db": AWGN_FER01.get(cfg), "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
-                      "seconds": round(time.perf_counter() - t0, 2)}), flush=True)
+                      "seconds": round(time.perf_counter() - t0, 2), **extra}), flush=True)
 
 
 def passband(argv, channel):
@@ -45,6 +59,7 @@ def passband(argv, channel):
     cfg = int(argv[0]) if argv else 8
     n = int(argv[1]) if len(argv) > 1 else 4096
     rx = RxPhy(cfg, max_batch=min(n, 1024))
+    rx.set_estimator_ladder(LADDER)
     pts = np.arange(31) * 1.0 - 25.0 if cfg >= 100 else np.arange(25) * 0.5 - 10.0
     rx.passband_test_esn0(pts[-1:], min(n, 1024), 1500.0, output_power_watt=1.0, hf_channel=channel)
     t0 = time.perf_counter()
@@ -53,7 +68,7 @@ def passband(argv, channel):
     for r in res:
         print("%.1f;%.3e;%.3e;%d" % (r["esn0_db"], r["BER"], r["FER"], r["crc_ok_frames"]))
     print(json.dumps({"cfg": cfg, "mode": "passband", "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
-                      "frames_per_s": len(res) * n / dt}), file=sys.stderr)
+                      "frames_per_s": len(res) * n / dt, **_ladder_fields(rx)}), file=sys.stderr)
 
 
 def main():
@@ -66,12 +81,18 @@ def main():
             if channel not in pl.HF_PRESETS:
                 sys.exit("--channel: one of " + ", ".join(pl.HF_PRESETS))
             break
+    for i, a in enumerate(argv):
+        if a == "--ladder" or a.startswith("--ladder="):
+            LADDER[:] = pl.parse_ladder(a.split("=", 1)[1] if "=" in a else argv[i + 1])
+            del argv[i: i + (1 if "=" in a else 2)]
+            break
     if argv and argv[0] == "--passband":
         return passband(argv[1:], channel)
     cfg = int(argv[0]) if argv else 8
     n = int(argv[1]) if len(argv) > 1 else 65536
     dec = {"spa": pl.DEC_SPA, "spa_fast": pl.DEC_SPA_FAST, "minsum": pl.DEC_MINSUM}[argv[2] if len(argv) > 2 else "spa"]
     rx = RxPhy(cfg, max_batch=min(n, 65536), agc=0, variance_source=0, decoder=dec)          # the variant baseband_test_EsN0 runs
+    rx.set_estimator_ladder(LADDER)
     pts = np.arange(-12.0, 13.0, 1.0)[:25] + (0.0 if cfg >= 7 else -6.0)
     rx.baseband_test_esn0(pts[:1], min(n, 4096), hf_channel=channel)
     t0 = time.perf_counter()
@@ -79,7 +100,8 @@ def main():
     dt = time.perf_counter() - t0
     for r in res:
         print("%.1f;%.3e;%.3e;%.2f" % (r["esn0_db"], r["BER"], r["FER"], r["avg_iterations"]))
-    print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt, "frames_per_s": len(res) * n / dt}), file=sys.stderr)
+    print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt, "frames_per_s": len(res) * n / dt,
+                      **_ladder_fields(rx)}), file=sys.stderr)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mercury_amd import HfStream, LinkSim, RxCapture, RxPhy, hf_channel_preset, linksim_config, load_library  # noqa: E402
+from mercury_amd import HfStream, LinkSim, RxCapture, RxPhy, hf_channel_preset, linksim_config, load_library, parse_ladder  # noqa: E402
 from mercury_amd.physical_layer import Info  # noqa: E402
 
 FP64_VECTOR_PEAK = 78.6e12          # MI355X fp64 vector FLOP/s (spec)
@@ -64,7 +64,7 @@ def plan(a):
 
 def run_sim(rx, a, info, esn0, hops):
     k = linksim_config(a.links, carrier_of(info), a.seed, channel=a.channel, gap_hops=a.gap_hops, max_hops=a.max_hops, output_power_watt=a.power)
-    sim = LinkSim(rx, k, esn0)
+    sim = LinkSim(rx, k, esn0, ladder=parse_ladder(a.ladder))
     sim.run(min(hops, 2 * (a.max_hops or 16)), max_events=0)              # warm: workspaces, carrier table, first frames
     t = time.perf_counter()
     done = 0
@@ -163,6 +163,7 @@ def main():
     ap.add_argument("--max-iters", type=int, default=50)
     ap.add_argument("--max-batch", type=int, default=0, help="receive_byte windows per call (0: the number of links)")
     ap.add_argument("--power", type=float, default=1.0, help="output_power_watt (1: Es/N0 is the signal's own, BER_PLOT_passband's convention)")
+    ap.add_argument("--ladder", default="", help="estimator ladder, e.g. 21x21,5x21 (carriers x symbols; include/mercury_estimator.h)")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--compare", action="store_true", help="simulator and baseline alternating, --repeats times each")
@@ -200,7 +201,10 @@ def main():
                                       "delivered_share": d / max(1, int(c["frames_sent"][m].sum()))}))
             rates[which].append(sim_seconds / wall)
     out = {"cfg": a.cfg, "links": a.links, "channel": a.channel, "gap_hops": a.gap_hops, "simulated_seconds_per_link": hops * p["symbol_period"] / FS,
-           "max_iters": a.max_iters}
+           "max_iters": a.max_iters, "ladder": a.ladder}
+    if a.ladder:
+        by, frames = rx.ladder_counters()
+        out["decoded_by_rung"], out["ladder_frames"] = [int(v) for v in by], frames
     for which, r in rates.items():
         if r:
             out[which + "_link_seconds_per_s"] = r
