@@ -225,7 +225,7 @@ struct mgpu_ctx {
     int ev_count = 0;               // launches recorded since timing was enabled (ring of kEvRing)
     bool ev_fe[kEvRing]{};          // whether the front-end ran in that slot
     size_t lds_fe = 0, lds_dec = 0, lds_tx = 0;
-    int fe_threads = 512;           // front-end workgroup size: 1024 when only one workgroup fits a compute unit's LDS anyway (long BPSK frames)
+    int fe_threads = 512;           // front-end workgroup size: 1024 when the 512-thread carve is more than half a compute unit's LDS (no mode or golden geometry today: 1024 runs under MERCURY_FE_THREADS only)
     DecoderKernel spa_kernel = nullptr;
     int dec_threads = 1024;         // workgroup size of the decoder kernel
     int wave_of_wgs = 0;            // decoder workgroups that fill the device once (2 per compute unit); 0 = not asked yet

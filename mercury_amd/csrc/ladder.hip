@@ -3,6 +3,8 @@
 // on compact buffers.
 #include <algorithm>
 #include <cstring>
+#include <memory>
+#include <mutex>
 
 #include "ctx.hpp"
 
@@ -230,7 +232,39 @@ int mgpu_estimator_ladder_counters(mgpu_ctx* c, long long decoded_by_rung[MGPU_L
     });
 }
 
-// The front-end's general path (frontend.hip: the reference's own walk over the window's cells, ofdm.cc:1315-1451) on the host
+// The front-end's general path (frontend.hip: the reference's own walk over the window's cells, ofdm.cc:1315-1451) on the host. What it needs
+// of the mode's tables is kept for the last geometry asked for: a sweep over windows and frames builds the tables once.
+namespace {
+struct TwinGeometry {
+    int cfg = -1;
+    mgpu::ExplicitParams xp;
+    bool ls = false;                    // an OFDM mode with the LS estimator
+    int Nc = 0, Nsymb = 0;
+    double pilot_boost = 0;
+    std::vector<uint8_t> cell_type;
+    std::vector<double> pilot_val;
+};
+std::mutex twin_mutex;
+std::shared_ptr<const TwinGeometry> twin_last;
+
+std::shared_ptr<const TwinGeometry> twin_geometry(int cfg, const mgpu::ExplicitParams& xp) {
+    std::lock_guard<std::mutex> lock(twin_mutex);
+    const auto same = [&](const TwinGeometry& g) {
+        return g.cfg == cfg && g.xp.pilot_boost == xp.pilot_boost && g.xp.ls_window == xp.ls_window && g.xp.pilot_seed == xp.pilot_seed &&
+               g.xp.scrambler_seed == xp.scrambler_seed && g.xp.preamble_seed == xp.preamble_seed && g.xp.Nsymb == xp.Nsymb && g.xp.Dy == xp.Dy;
+    };
+    if (twin_last && same(*twin_last)) return twin_last;
+    const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
+    auto g = std::make_shared<TwinGeometry>();
+    g->cfg = cfg; g->xp = xp;
+    g->ls = t.mfsk_M == 0 && t.estimator == MGPU_EST_LS;
+    g->Nc = t.Nc; g->Nsymb = t.Nsymb; g->pilot_boost = t.pilot_boost;
+    g->cell_type = t.cell_type; g->pilot_val = t.pilot_val;
+    twin_last = g;
+    return g;
+}
+}  // namespace
+
 int mgpu_host_ls_estimate(int cfg, const mgpu_explicit_params* p, int width, int height, const double* grid, double* H) {
     if (!grid || !H) return MGPU_ERR_ARG;
     const int wf = window_side(width), wt = window_side(height);
@@ -241,8 +275,9 @@ int mgpu_host_ls_estimate(int cfg, const mgpu_explicit_params* p, int width, int
     if (!explicit_params_from(p, xp, err, &rc)) return rc;
     xp.ls_window = mgpu::ExplicitParams().ls_window;
     try {
-        const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
-        if (t.mfsk_M > 0 || t.estimator != MGPU_EST_LS) return MGPU_ERR_UNSUPPORTED;
+        const std::shared_ptr<const TwinGeometry> geometry = twin_geometry(cfg, xp);
+        const TwinGeometry& t = *geometry;
+        if (!t.ls) return MGPU_ERR_UNSUPPORTED;
         const std::vector<double> weight = mgpu::ls_weight_table(t.pilot_boost, wf * wt);
         const int Nc = t.Nc, Ns = t.Nsymb, hf = wf / 2, ht = wt / 2;
         int pilot = 0;

@@ -107,6 +107,40 @@ def test_argument_validation():
     assert fn(8, C.byref(bad), 5, 21, g, o) == 1
 
 
+def _geometries():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden.py"))
+    mg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mg)
+    frames = [(cfg, x) for cfg, x in mg.EXPLICIT_CASES if "Nsymb" in x or "Dy" in x]
+    assert len(frames) == 6
+    return [(cfg, None) for cfg in range(17)] + frames
+
+
+def test_the_front_end_carve_fits_a_compute_unit_at_either_workgroup_size():
+    """MERCURY_FE_THREADS=1024 cannot fail at launch on any mode or on the golden explicit geometries: the 1024-thread carve
+    fits the 160 KB of a compute unit, as the 512-thread one does. mgpu_create takes 1024 threads by itself when the 512-thread carve is more
+    than half of that (create.hip): the list of such geometries is part of the assertion - today there is none, so the 1024-thread
+    kernels run under the variable only (tests/test_gpu_frontend_shapes.py)."""
+    from mercury_amd import load_library
+    fn = load_library().mgpu_frontend_lds_bytes
+    fn.restype, fn.argtypes = C.c_size_t, [C.c_int] * 4
+    lds_cu = 160 * 1024
+    carve, by_default_1024 = {}, []
+    for cfg, x in _geometries():
+        orc = Oracle(cfg, 50, explicit=dict(x or {}))
+        G = orc.Nsymb * orc.Nc
+        b512, b1024 = fn(G, orc.nPilots, orc.nBits, 512), fn(G, orc.nPilots, orc.nBits, 1024)
+        assert 16 * G + 16 * orc.nPilots < b512 <= lds_cu and b512 <= b1024 <= lds_cu, (cfg, x, b512, b1024)
+        carve[(cfg, tuple(sorted((x or {}).items())))] = (b512, b1024)
+        if b512 > lds_cu // 2:
+            by_default_1024.append((cfg, x))
+    assert by_default_1024 == []
+    dy5 = (("Dy", 5), ("Nsymb", 20))
+    assert [carve[k] for k in ((0, ()), (8, ()), (11, ()), (13, ()), (8, dy5))] == [(73632, 106400), (49920, 86784), (47616, 80384), (44416, 77184), (50816, 83584)]
+
+
 def test_parse_ladder():
     from mercury_amd import parse_ladder
     assert parse_ladder("21x21,5x21") == [(21, 21), (5, 21)]

@@ -56,6 +56,40 @@ def _variants(cfg):
     return [(1, 1, FLAGS_RECEIVE_BYTE), (0, 0, FLAGS_BASEBAND_TEST)]
 
 
+def stages_match_oracle(rx, orc, bb, payloads, snrs, flags):
+    """What test_all_stages_match_oracle holds one context to: every stage tap, the float variance, payload, CRC and iteration count of
+    receive(bb, taps=True) against the CPU oracle run with `flags`. snrs: the Es/N0 each frame was made at (60.0 or more: it must decode)."""
+    cfg = rx.cfg
+    out = rx.receive(bb, taps=True)
+    for f in range(len(snrs)):
+        ref = orc.rx(bb[f], flags)
+        # FP64 front-end: the reference's operations in the reference's order, its libm's atan / sincos restated
+        # (csrc/glibc_trig.h) -> every stage BIT-IDENTICAL where the host runs the libm build that was restated
+        # (FMA-capable x86-64, see tests/test_glibc_trig.py); elsewhere the PSK modes' phasors may differ in the last ulp
+        exact = EXACT_TRIG or not orc.amp_restore
+        for key in ("grid", "H", "eq", "syms"):        # H: the channel grid after estimate + interpolation + amplitude restoration (rows a4-a7)
+            d = np.abs(out[key][f] - ref[key]).max()
+            scale = np.abs(ref[key]).max()
+            assert d <= (0.0 if exact or key == "grid" else 1e-12) * scale, (cfg, flags, f, key, d, scale)
+        if exact and np.isfinite(ref["variance"]):
+            assert out["variance"][f] == ref["variance"], (cfg, f)
+            assert np.float32(out["stats"]["variance"][f]) == np.float32(ref["variance_f"])
+            assert np.array_equal(out["llr_demod"][f], ref["llr_demod"], equal_nan=True), (cfg, flags, f, "llr_demod")
+            assert np.array_equal(out["llr_ldpc"][f], ref["llr_ldpc"], equal_nan=True), (cfg, flags, f, "llr_ldpc")
+        else:
+            assert abs(out["variance"][f] - ref["variance"]) <= 1e-12 * abs(ref["variance"]), (cfg, f)
+        assert _llr_close(out["llr_demod"][f], ref["llr_demod"]).all(), (cfg, flags, f, "llr_demod")
+        assert _llr_close(out["llr_ldpc"][f], ref["llr_ldpc"]).all(), (cfg, flags, f, "llr_ldpc")
+        # integer / byte outputs: bit exact
+        assert out["stats"]["iterations_done"][f] == ref["iterations"], (cfg, flags, f, "iterations")
+        assert np.array_equal(out["payload"][f], ref["bytes"].astype(np.uint8)), (cfg, flags, f, "payload")
+        assert out["stats"]["crc"][f] == ref["crc"], (cfg, flags, f)
+        assert out["stats"]["all_zeros"][f] == ref["all_zeros"], (cfg, flags, f)
+        if ref["iterations"] <= 50 and snrs[f] > 0 or snrs[f] >= 60.0:
+            assert np.array_equal(out["payload"][f][: orc.payload_bytes], payloads[f].astype(np.uint8))
+    return out
+
+
 @pytest.mark.parametrize("cfg", list(range(17)))
 def test_all_stages_match_oracle(cfg):
     orc = Oracle(cfg, 50)
@@ -64,33 +98,7 @@ def test_all_stages_match_oracle(cfg):
     bb, payloads = _frames(orc, snrs)
     for agc, vs, flags in _variants(cfg):
         rx = _rx(cfg, max_iters=50, agc=agc, variance_source=vs, max_batch=len(snrs))
-        out = rx.receive(bb, taps=True)
-        for f in range(len(snrs)):
-            ref = orc.rx(bb[f], flags)
-            # FP64 front-end: the reference's operations in the reference's order, its libm's atan / sincos restated
-            # (csrc/glibc_trig.h) -> every stage BIT-IDENTICAL where the host runs the libm build that was restated
-            # (FMA-capable x86-64, see tests/test_glibc_trig.py); elsewhere the PSK modes' phasors may differ in the last ulp
-            exact = EXACT_TRIG or not orc.amp_restore
-            for key in ("grid", "H", "eq", "syms"):        # H: the channel grid after estimate + interpolation + amplitude restoration (rows a4-a7)
-                d = np.abs(out[key][f] - ref[key]).max()
-                scale = np.abs(ref[key]).max()
-                assert d <= (0.0 if exact or key == "grid" else 1e-12) * scale, (cfg, flags, f, key, d, scale)
-            if exact and np.isfinite(ref["variance"]):
-                assert out["variance"][f] == ref["variance"], (cfg, f)
-                assert np.float32(out["stats"]["variance"][f]) == np.float32(ref["variance_f"])
-                assert np.array_equal(out["llr_demod"][f], ref["llr_demod"], equal_nan=True), (cfg, flags, f, "llr_demod")
-                assert np.array_equal(out["llr_ldpc"][f], ref["llr_ldpc"], equal_nan=True), (cfg, flags, f, "llr_ldpc")
-            else:
-                assert abs(out["variance"][f] - ref["variance"]) <= 1e-12 * abs(ref["variance"]), (cfg, f)
-            assert _llr_close(out["llr_demod"][f], ref["llr_demod"]).all(), (cfg, flags, f, "llr_demod")
-            assert _llr_close(out["llr_ldpc"][f], ref["llr_ldpc"]).all(), (cfg, flags, f, "llr_ldpc")
-            # integer / byte outputs: bit exact
-            assert out["stats"]["iterations_done"][f] == ref["iterations"], (cfg, flags, f, "iterations")
-            assert np.array_equal(out["payload"][f], ref["bytes"].astype(np.uint8)), (cfg, flags, f, "payload")
-            assert out["stats"]["crc"][f] == ref["crc"], (cfg, flags, f)
-            assert out["stats"]["all_zeros"][f] == ref["all_zeros"], (cfg, flags, f)
-            if ref["iterations"] <= 50 and snrs[f] > 0 or snrs[f] == 60.0:
-                assert np.array_equal(out["payload"][f][: orc.payload_bytes], payloads[f].astype(np.uint8))
+        stages_match_oracle(rx, orc, bb, payloads, snrs, flags)
         rx.close()
 
 
