@@ -199,7 +199,7 @@ void ctx_upload(mgpu_ctx* c, const Plan& p) {
     l.vinfo2 = c->keep(t.graph.vinfo2);
     l.hard_frames = reinterpret_cast<unsigned long long*>(c->keep(std::vector<uint64_t>(64, 0)));
     HIPCK(hipStreamCreate(&c->stream.h));
-    for (auto& q : c->ev) for (auto& e : q) HIPCK(hipEventCreate(&e.h));
+    for (auto& q : c->kt.ev) for (auto& e : q) HIPCK(hipEventCreate(&e.h));
     for (auto& e : c->sync_ev) HIPCK(hipEventCreate(&e.h));
     auto lds_limit = [](auto kernel, size_t bytes) {
         HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));

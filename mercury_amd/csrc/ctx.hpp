@@ -164,6 +164,19 @@ struct Ladder {
     int last_F = 0;                                 // frames of the last fused-span call
 };
 
+// The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
+struct SpanIo {
+    const double* bb = nullptr;         // input frames
+    int frame_stride = 0;               // complex samples between consecutive frames of bb, 0 = the mode's frame_samples
+    float *llr = nullptr, *var = nullptr, *snrvar = nullptr;
+    uint8_t* payload = nullptr;
+    MgpuStatsDev* stats = nullptr;
+    double* mean_H = nullptr;           // the front-end's mean_H tap, which the ladder also merges (receive_byte's gate), or null
+    double* zf_var = nullptr;           // zero-forcing modes: the argument of the SNR's logarithm per frame, or null
+    int frame0 = 0;                     // row of the call's first frame in the context's max_batch-sized workspaces (d_eqdata, the ladder's d_rung)
+    bool zf_snr = true;                 // false: no zero-forcing SNR launch (the baseband self-simulation's error counter does not read snr_db)
+};
+
 struct Workspace;   // rxloop.hip
 struct TxState;     // tx.hip
 struct Release { void operator()(Workspace*) const; void operator()(TxState*) const; };   // defined where each type is complete
@@ -195,10 +208,12 @@ struct mgpu_ctx {
     float last_sync_ms = -1.f;
     DevArray<int> d_iters;
     // single-frame fast path of mgpu_rx_batch: the copy-in / front-end / decoder / copy-out sequence as one hipGraph
-    GraphExec one_frame_graph;
-    DevArray<double> d_one_in;      // the graph's own one-frame device buffer (never reallocated: the graph holds its address)
-    PinnedBuf h_one_in;             // page-locked staging for one frame of samples
-    PinnedBuf h_one_out;            // page-locked staging for its payload + stats
+    struct OneFrame {
+        GraphExec graph;
+        DevArray<double> d_in;      // the graph's own one-frame device buffer (never reallocated: the graph holds its address)
+        PinnedBuf h_in;             // page-locked staging for one frame of samples
+        PinnedBuf h_out;            // page-locked staging for its payload + stats
+    } one;
     std::unique_ptr<Workspace, Release> rxloop_ws;   // device workspace of mgpu_receive_byte_batch, kept between calls (rxloop.hip)
     int rxloop_ws_windows = 0;
     DevArray<double> rb_stage;      // mgpu_receive_byte_batch from host memory: landing area of the whole call's windows (uploaded by a helper thread)
@@ -213,22 +228,28 @@ struct mgpu_ctx {
     Ladder lad;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
-    PinnedBuf h_out;                // page-locked staging for the payloads + stats of a pipelined call ([max_batch])
-    static constexpr int kPipes = 2;
-    Pipe pipe[kPipes];                   // the two chunk pipelines of the blocking host-buffer entry points (rx_batch.hip rx_batch_pipelined)
-    Event hp_ev[4];                      // call start, first chunk copied, last chunk copied, all done (host-path profile)
-    int hp_chunk = 0, hp_nchunks = 0;    // the last pipelined call: frames per chunk, chunks
-    float hp_fill_ms = 0, hp_drain_ms = 0, hp_total_ms = 0;
-    static constexpr int kEvRing = 64;
-    Event ev[kEvRing][4];           // per launch: front-end start/stop, decoder start/stop
-    bool timing = false;
-    int ev_count = 0;               // launches recorded since timing was enabled (ring of kEvRing)
-    bool ev_fe[kEvRing]{};          // whether the front-end ran in that slot
+    // the blocking host-buffer entry points' chunk pipeline (rx_batch.hip rx_batch_pipelined)
+    struct HostPath {
+        static constexpr int kPipes = 2;
+        Pipe pipe[kPipes];              // the two chunk pipelines
+        PinnedBuf h_out;                // page-locked staging for the payloads + stats of a pipelined call ([max_batch])
+        Event ev[4];                    // call start, first chunk copied, last chunk copied, all done (host-path profile)
+        int chunk = 0, nchunks = 0;     // the last pipelined call: frames per chunk, chunks
+        float fill_ms = 0, drain_ms = 0, total_ms = 0;
+        int wave_of_wgs = 0;            // decoder workgroups that fill the device once (2 per compute unit); 0 = not asked yet
+    } hp;
+    // kernel timing (mgpu_enable_timing): named by launch.hip's two timed launchers and rx_batch.hip's queries only
+    struct KernelTimes {
+        static constexpr int kEvRing = 64;
+        Event ev[kEvRing][4];           // per launch: front-end start/stop, decoder start/stop
+        bool timing = false;
+        int ev_count = 0;               // launches recorded since timing was enabled (ring of kEvRing)
+        bool ev_fe[kEvRing]{};          // whether the front-end ran in that slot
+    } kt;
     size_t lds_fe = 0, lds_dec = 0, lds_tx = 0;
     int fe_threads = 512;           // front-end workgroup size: 1024 when the 512-thread carve is more than half a compute unit's LDS (no mode or golden geometry today: 1024 runs under MERCURY_FE_THREADS only)
     DecoderKernel spa_kernel = nullptr;
     int dec_threads = 1024;         // workgroup size of the decoder kernel
-    int wave_of_wgs = 0;            // decoder workgroups that fill the device once (2 per compute unit); 0 = not asked yet
 
     template <typename T>
     T* keep(const std::vector<T>& v) { tables.push_back(upload(v)); return static_cast<T*>(tables.back().p); }
@@ -250,23 +271,41 @@ template <typename T> T* at(T* p, size_t off) { return p ? p + off : nullptr; }
 
 using FrontendKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
 inline FrontendKernel fe_kernel(int threads) { return threads == 1024 ? mgpu_frontend_kernel_t1024 : mgpu_frontend_kernel; }
+using FrontendRectKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
+inline FrontendRectKernel fe_rect_kernel(int threads) { return threads == 1024 ? mgpu_frontend_rect_kernel_t1024 : mgpu_frontend_rect_kernel; }
 
-// frame_stride (complex samples between consecutive frames of d_bb) defaults to the mode's frame_samples
-// frame0: index of the call's first frame inside the context's max_batch-sized workspaces (the ZF modes keep their equalised symbols there)
-void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, const MgpuTapsDev& taps,
-                     hipStream_t s, int frame_stride = 0, int frame0 = 0);
-// The estimator ladder behind rung 0 (ladder.hip), to be called right after launch_frontend + launch_decoder on the same arrays and stream:
-// marks each frame's rung and, rung by rung, re-runs the frames still undecoded and merges the ones that decode. Nothing without a ladder.
-// d_mean_H: the front-end's mean_H tap where the caller reads it, or null. Waits for the stream once per rung (the retry's frame count).
-void launch_ladder(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, uint8_t* d_payload, MgpuStatsDev* d_stats,
-                   double* d_mean_H, hipStream_t s, int frame_stride = 0, int frame0 = 0);
-void launch_frontend_rect(mgpu_ctx* c, const MgpuLsRect& win, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, const MgpuTapsDev& taps,
-                          hipStream_t s, int frame_stride);
-// mgpu_explicit_params as the table builder takes them; false (and *rc, err) when they are refused (create.hip)
-bool explicit_params_from(const mgpu_explicit_params* in, mgpu::ExplicitParams& xp, std::string& err, int* rc);
-void launch_zf_snr(mgpu_ctx* c, int F, const uint8_t* d_payload, MgpuStatsDev* d_stats, hipStream_t s, int frame0 = 0, double* d_var_out = nullptr);
+// whether the caller wants a tap with a row per frame (a launch's kernel writes them from row 0: one launch per call then)
+inline bool wants_frame_taps(const MgpuTapsDev& t) { return t.grid || t.H || t.eq || t.syms || t.llr_demod || t.variance || t.agc_gain; }
+
+// the context's own workspaces from frame `frame0` on (the caller sets bb, and whatever array is not the context's)
+inline SpanIo own_span(mgpu_ctx* c, int frame0 = 0) {
+    SpanIo io;
+    io.llr = c->d_llr + size_t(frame0) * c->tab.N; io.var = c->d_variance + frame0; io.snrvar = c->d_snrvar + frame0;
+    io.payload = c->d_payload + size_t(frame0) * c->tab.payload_stride; io.stats = c->d_stats + frame0;
+    io.frame0 = frame0;
+    return io;
+}
+
+// The fused span of the production receive path, on one stream: front-end, decoder, the estimator ladder's retries, zero-forcing SNR.
+// taps: the stage taps of the front-end (rung 0's; mean_H comes from io). input_free, when given, is recorded behind the last launch that
+// reads io.bb: the front-end, or the ladder where a retry can read the frames again.
+void launch_span(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s, hipEvent_t input_free = nullptr);
+// The halves of the span, timed when mgpu_enable_timing is on (launch.hip). The front-end reads io.bb and writes llr, var, snrvar, mean_H.
+void launch_frontend(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s);
 void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
                     const float* d_var, const float* d_snrvar, hipStream_t s);
+// The same launches without the timing events, as the ladder's retries run them: the kernel timings describe rung 0.
+// rect: null = rung 0 (the ladder's first window where it is not the context's own, else the default kernel); a retry's window otherwise,
+// whose `frames` list names the frame each row of the compact outputs in io belongs to.
+void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s);
+void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
+                     const float* d_var, const float* d_snrvar, hipStream_t s);
+// The estimator ladder behind rung 0 (ladder.hip), called by launch_span alone: marks each frame's rung and, rung by rung, re-runs the
+// frames still undecoded and merges the ones that decode. Nothing without a ladder. Waits for the stream once per rung (the retry's frame count).
+void launch_ladder(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
+void launch_zf_snr(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
+// mgpu_explicit_params as the table builder takes them; false (and *rc, err) when they are refused (create.hip)
+bool explicit_params_from(const mgpu_explicit_params* in, mgpu::ExplicitParams& xp, std::string& err, int* rc);
 // F generated frames from frame0 on into d_bb (and their payloads into d_payload, if given). channel -1: the transmit path's clean frames,
 // whose payloads come from tx_payload (frames tx_stride bytes apart, d_nbytes of each in use) instead of the generator
 void launch_txgen(mgpu_ctx* c, uint64_t seed, uint64_t frame0, int F, double noise_amp, int channel, double* d_bb, uint8_t* d_payload, hipStream_t s,

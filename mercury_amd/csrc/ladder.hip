@@ -1,6 +1,6 @@
 // The estimator ladder (include/mercury_estimator.h): the two small kernels around a retry, the host loop over the rungs, the setters and
-// the host twin of the LS estimate. The retry itself is the rectangular front-end (frontend.hip) on a frame list and the unchanged decoder
-// on compact buffers.
+// the host twin of the LS estimate. The retry itself is the rectangular front-end (frontend.hip; launched by launch.hip's front-end core)
+// on a frame list and the unchanged decoder on compact buffers.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -68,72 +68,41 @@ extern "C" __global__ __launch_bounds__(256) void mgpu_ladder_merge_kernel(const
 
 namespace mgpu_detail {
 
-using FrontendRectKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
-static FrontendRectKernel fe_rect_kernel(int threads) { return threads == 1024 ? mgpu_frontend_rect_kernel_t1024 : mgpu_frontend_rect_kernel; }
-
-// the rectangular front-end on F rows: frames by win.frames (a retry) or in place (rung 0 with a window that is not the context's)
-void launch_frontend_rect(mgpu_ctx* c, const MgpuLsRect& win, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, const MgpuTapsDev& taps,
-                          hipStream_t s, int frame_stride) {
-    const auto& t = c->tab;
-    MgpuDev dev = c->dev;
-    if (frame_stride > 0) dev.frame_samples = frame_stride;
-    const size_t stride = size_t(dev.frame_samples);
-    for_frame_chunks(F, [&](int off, int n) {
-        if (off && (taps.grid || taps.H || taps.eq || taps.syms || taps.llr_demod || taps.variance || taps.agc_gain))
-            throw std::invalid_argument("stage taps are limited to 2^21 frames per call");
-        MgpuLsRect w = win;
-        MgpuTapsDev tp = taps;
-        const double* bb = d_bb;
-        if (w.frames) w.frames += off; else bb += size_t(off) * stride * 2;
-        tp.mean_H = at(taps.mean_H, off);
-        hipLaunchKernelGGL(fe_rect_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, d_llr + size_t(off) * t.N, d_var + off,
-                           at(d_snrvar, off), static_cast<double*>(nullptr), tp, w);
-        HIPCK(hipGetLastError());
-    });
-}
-
-void launch_ladder(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar, uint8_t* d_payload, MgpuStatsDev* d_stats,
-                   double* d_mean_H, hipStream_t s, int frame_stride, int frame0) {
+void launch_ladder(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s) {
     Ladder& L = c->lad;
     if (L.n == 0 || F <= 0) return;
     const auto& t = c->tab;
-    need(d_payload && d_stats && size_t(frame0) + size_t(F) <= size_t(c->max_batch), "estimator ladder: the call needs payload and stats arrays of at most max_batch frames");
-    int* rung = L.d_rung + frame0;
-    L.last_F = frame0 + F;
+    need(io.payload && io.stats && size_t(io.frame0) + size_t(F) <= size_t(c->max_batch), "estimator ladder: the call needs payload and stats arrays of at most max_batch frames");
+    int* rung = L.d_rung + io.frame0;
+    L.last_F = io.frame0 + F;
     // a retry's workspaces are the context's: one retry at a time, whatever streams the calls come on
     if (L.done_recorded) HIPCK(hipStreamWaitEvent(s, L.done, 0));
-    const bool timing = c->timing;       // the kernel timings describe rung 0
-    c->timing = false;
-    try {
-        for (int r = 1; r == 1 || r < L.n; ++r) {
-            const bool retry = r < L.n;      // a one-rung ladder still marks the frames and counts them
-            hipLaunchKernelGGL(mgpu_ladder_select_kernel, dim3(1), dim3(1024), 0, s, d_stats, F, r == 1 ? 1 : 0, rung, retry ? static_cast<int*>(L.d_idx) : nullptr,
-                               retry ? static_cast<int*>(L.d_count) : nullptr, static_cast<unsigned long long*>(L.d_counters));
+    SpanIo k = io;           // the same frames into the compact workspaces, row b = frame d_idx[b]
+    k.llr = L.d_llr; k.var = L.d_var; k.snrvar = L.d_snrvar; k.payload = L.d_payload; k.stats = L.d_stats;
+    k.mean_H = io.mean_H ? static_cast<double*>(L.d_meanh) : nullptr;
+    for (int r = 1; r == 1 || r < L.n; ++r) {
+        const bool retry = r < L.n;      // a one-rung ladder still marks the frames and counts them
+        hipLaunchKernelGGL(mgpu_ladder_select_kernel, dim3(1), dim3(1024), 0, s, io.stats, F, r == 1 ? 1 : 0, rung, retry ? static_cast<int*>(L.d_idx) : nullptr,
+                           retry ? static_cast<int*>(L.d_count) : nullptr, static_cast<unsigned long long*>(L.d_counters));
+        HIPCK(hipGetLastError());
+        if (!retry) break;
+        int n = 0;       // the decoder's launch size: the one value per rung the host has to see
+        HIPCK(hipMemcpyAsync(&n, L.d_count, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCK(hipStreamSynchronize(s));
+        if (n == 0) break;
+        MgpuLsRect w = L.win[r];
+        w.frames = L.d_idx;
+        // untimed: the kernel timings describe rung 0
+        frontend_untimed(c, k, n, MgpuTapsDev{}, &w, s);
+        decoder_untimed(c, k.llr, n, nullptr, nullptr, k.payload, k.stats, k.var, k.snrvar, s);
+        for_frame_chunks(n, [&](int off, int m) {
+            hipLaunchKernelGGL(mgpu_ladder_merge_kernel, dim3(m), dim3(256), 0, s, L.d_idx + off, m, r, t.N, t.payload_stride, k.llr + size_t(off) * t.N,
+                               k.var + off, k.snrvar + off, at(k.mean_H, off), k.payload + size_t(off) * t.payload_stride,
+                               k.stats + off, io.llr, io.var, io.snrvar, io.mean_H, io.payload, io.stats, rung,
+                               static_cast<unsigned long long*>(L.d_counters));
             HIPCK(hipGetLastError());
-            if (!retry) break;
-            int n = 0;       // the decoder's launch size: the one value per rung the host has to see
-            HIPCK(hipMemcpyAsync(&n, L.d_count, sizeof(int), hipMemcpyDeviceToHost, s));
-            HIPCK(hipStreamSynchronize(s));
-            if (n == 0) break;
-            MgpuLsRect w = L.win[r];
-            w.frames = L.d_idx;
-            MgpuTapsDev taps{};
-            if (d_mean_H) taps.mean_H = L.d_meanh;
-            launch_frontend_rect(c, w, d_bb, n, L.d_llr, L.d_var, L.d_snrvar, taps, s, frame_stride);
-            launch_decoder(c, L.d_llr, n, nullptr, nullptr, L.d_payload, L.d_stats, L.d_var, L.d_snrvar, s);
-            for_frame_chunks(n, [&](int off, int m) {
-                hipLaunchKernelGGL(mgpu_ladder_merge_kernel, dim3(m), dim3(256), 0, s, L.d_idx + off, m, r, t.N, t.payload_stride, L.d_llr + size_t(off) * t.N,
-                                   L.d_var + off, L.d_snrvar + off, d_mean_H ? L.d_meanh + off : nullptr, L.d_payload + size_t(off) * t.payload_stride,
-                                   L.d_stats + off, d_llr, d_var, d_snrvar, d_mean_H, d_payload, d_stats, rung,
-                                   static_cast<unsigned long long*>(L.d_counters));
-                HIPCK(hipGetLastError());
-            });
-        }
-    } catch (...) {
-        c->timing = timing;
-        throw;
+        });
     }
-    c->timing = timing;
     HIPCK(hipEventRecord(L.done, s));
     L.done_recorded = true;
 }

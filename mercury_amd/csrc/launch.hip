@@ -1,4 +1,5 @@
-// The kernel launches the host-side translation units share (declared in ctx.hpp): front-end, decoder, zero-forcing SNR, the synchroniser's
+// The kernel launches the host-side translation units share (declared in ctx.hpp): the fused receive span (launch_span) and its parts -
+// front-end and decoder, untimed and timed, and zero-forcing SNR; the ladder's part is in ladder.hip -, the synchroniser's
 // metric / mixer / MFSK search kernels with the host halves of their searches, and the frame generator.
 #include <algorithm>
 #include <atomic>
@@ -8,14 +9,16 @@
 
 namespace mgpu_detail {
 
-void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float* d_var, float* d_snrvar,
-                     const MgpuTapsDev& taps, hipStream_t s, int frame_stride, int frame0) {
-    const int slot = c->ev_count % mgpu_ctx::kEvRing;
+void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s) {
     const auto& t = c->tab;
     MgpuDev dev = c->dev;                        // kernel argument; the frame stride can differ from the frame length
-    if (frame_stride > 0) dev.frame_samples = frame_stride;
+    if (io.frame_stride > 0) dev.frame_samples = io.frame_stride;
     const size_t stride = size_t(dev.frame_samples);
-    if (c->timing) { HIPCK(hipEventRecord(c->ev[slot][0], s)); c->ev_fe[slot] = true; }
+    MgpuTapsDev tp = taps;
+    auto begin_chunk = [&](int off) {            // the per-frame taps have no row offset, so they allow one launch per call; mean_H has one
+        if (off && wants_frame_taps(taps)) throw std::invalid_argument("stage taps are limited to one launch per call");
+        tp.mean_H = at(io.mean_H, off);
+    };
     if (t.mfsk_M > 0) {
         // MFSK modes: workgroups of (frame, run of symbols); keep gridDim * blockDim below 2^32
         const int per = mgpu_mfsk_syms_per_block(), chunks = (t.active_nsymb + per - 1) / per;
@@ -25,28 +28,58 @@ void launch_frontend(mgpu_ctx* c, const double* d_bb, int F, float* d_llr, float
         const int max_frames = (1 << 23) / chunks;
         for (int off = 0; off < F; off += max_frames) {
             const int n = F - off < max_frames ? F - off : max_frames;
-            if (off && (taps.grid || taps.llr_demod || taps.variance || taps.agc_gain))
-                throw std::invalid_argument("stage taps are limited to one launch per call");
+            begin_chunk(off);
             hipLaunchKernelGGL(t.mfsk_M == 32 ? mgpu_mfsk_frontend_kernel_m32 : mgpu_mfsk_frontend_kernel_m16x2, dim3(unsigned(n) * chunks), dim3(256), 0, s, dev,
-                               d_bb + size_t(off) * stride * 2, n, chunks, d_llr + size_t(off) * t.N, d_var + off, at(d_snrvar, off), taps);
+                               io.bb + size_t(off) * stride * 2, n, chunks, io.llr + size_t(off) * t.N, io.var + off, at(io.snrvar, off), tp);
             HIPCK(hipGetLastError());
         }
-        if (c->timing) HIPCK(hipEventRecord(c->ev[slot][1], s));
         return;
     }
-    if (c->lad.n > 0 && !c->lad.rung0_is_default) {     // rung 0 of an estimator ladder with a window of its own (ladder.hip)
-        launch_frontend_rect(c, c->lad.win[0], d_bb, F, d_llr, d_var, d_snrvar, taps, s, frame_stride);
-        if (c->timing) HIPCK(hipEventRecord(c->ev[slot][1], s));
-        return;
-    }
+    if (!rect && c->lad.n > 0 && !c->lad.rung0_is_default) rect = &c->lad.win[0];      // rung 0 of an estimator ladder with a window of its own
     for_frame_chunks(F, [&](int off, int n) {
-        if (off && (taps.grid || taps.H || taps.eq || taps.syms || taps.llr_demod || taps.variance || taps.agc_gain || taps.mean_H))
-            throw std::invalid_argument("stage taps are limited to 2^21 frames per call");
-        hipLaunchKernelGGL(fe_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, d_bb + size_t(off) * stride * 2, n,
-                           d_llr + size_t(off) * t.N, d_var + off, at(d_snrvar, off), at<double>(c->d_eqdata, (size_t(frame0) + off) * t.nData * 2), taps);
+        begin_chunk(off);
+        const double* bb = io.bb + size_t(off) * stride * 2;
+        float *llr = io.llr + size_t(off) * t.N, *var = io.var + off, *snrvar = at(io.snrvar, off);
+        if (rect) {
+            MgpuLsRect w = *rect;
+            if (w.frames) { w.frames += off; bb = io.bb; }       // a retry: workgroup b reads frame frames[b] and writes row b
+            hipLaunchKernelGGL(fe_rect_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar,
+                               static_cast<double*>(nullptr), tp, w);
+        } else {
+            hipLaunchKernelGGL(fe_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar,
+                               at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2), tp);
+        }
         HIPCK(hipGetLastError());
     });
-    if (c->timing) HIPCK(hipEventRecord(c->ev[slot][1], s));
+}
+
+// The timed launchers: the only code that records into the context's event ring, one start and one stop around the untimed launches.
+// A slot is a front-end and the decoder launch behind it; the decoder's stop closes it (mgpu_frontend_dev alone leaves it open).
+void launch_frontend(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s) {
+    auto& k = c->kt;
+    const int slot = k.ev_count % k.kEvRing;
+    if (k.timing) { HIPCK(hipEventRecord(k.ev[slot][0], s)); k.ev_fe[slot] = true; }
+    frontend_untimed(c, io, F, taps, nullptr, s);
+    if (k.timing) HIPCK(hipEventRecord(k.ev[slot][1], s));
+}
+
+void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload,
+                    MgpuStatsDev* d_stats, const float* d_var, const float* d_snrvar, hipStream_t s) {
+    auto& k = c->kt;
+    const int slot = k.ev_count % k.kEvRing;
+    if (k.timing) HIPCK(hipEventRecord(k.ev[slot][2], s));
+    decoder_untimed(c, d_llr, F, d_bits, d_iters, d_payload, d_stats, d_var, d_snrvar, s);
+    if (k.timing) { HIPCK(hipEventRecord(k.ev[slot][3], s)); ++k.ev_count; k.ev_fe[k.ev_count % k.kEvRing] = false; }
+}
+
+void launch_span(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s, hipEvent_t input_free) {
+    const bool retries = c->lad.n > 1;           // an estimator ladder's retries read the input again
+    launch_frontend(c, io, F, taps, s);
+    if (input_free && !retries) HIPCK(hipEventRecord(input_free, s));      // the front-end is the only reader of the input
+    launch_decoder(c, io.llr, F, nullptr, nullptr, io.payload, io.stats, io.var, io.snrvar, s);
+    launch_ladder(c, io, F, s);
+    if (input_free && retries) HIPCK(hipEventRecord(input_free, s));
+    if (io.zf_snr) launch_zf_snr(c, io, F, s);
 }
 
 void select_peak(const double* cand_vals, int ncand, int step, int size, int location_to_return, int nTrials_max, int* delay, double* corr) {
@@ -211,22 +244,20 @@ int mfsk_sync_from_energies(const mgpu::ModeTables& t, const double* E, int nslo
 
 // zero-forcing modes: SNR from the re-encoded decision (telecom_system.cc:1374-1396); needs the payload and
 // the de-framed equalised symbols the front-end kept.
-void launch_zf_snr(mgpu_ctx* c, int F, const uint8_t* d_payload, MgpuStatsDev* d_stats, hipStream_t s, int frame0, double* d_var_out) {
+void launch_zf_snr(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s) {
     const auto& t = c->tab;
-    if (t.estimator != MGPU_EST_ZF || !d_payload || !d_stats) return;
+    if (t.estimator != MGPU_EST_ZF || !io.payload || !io.stats) return;
     for_frame_chunks(F, [&](int off, int n) {
         hipLaunchKernelGGL(mgpu_zf_snr_kernel, dim3(n), dim3(256), mgpu_zfsnr_lds_bytes(t.nData), s, c->dev,
-                           d_payload + size_t(off) * t.payload_stride, c->d_eqdata + (size_t(frame0) + off) * t.nData * 2, n, d_stats + off,
-                           d_var_out ? d_var_out + off : nullptr);
+                           io.payload + size_t(off) * t.payload_stride, c->d_eqdata + (size_t(io.frame0) + off) * t.nData * 2, n, io.stats + off,
+                           at(io.zf_var, off));
         HIPCK(hipGetLastError());
     });
 }
 
-void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload,
-                    MgpuStatsDev* d_stats, const float* d_var, const float* d_snrvar, hipStream_t s) {
-    const int slot = c->ev_count % mgpu_ctx::kEvRing;
+void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload,
+                     MgpuStatsDev* d_stats, const float* d_var, const float* d_snrvar, hipStream_t s) {
     const auto& t = c->tab;
-    if (c->timing) HIPCK(hipEventRecord(c->ev[slot][2], s));
     for_frame_chunks(F, [&](int off, int n) {
         const float* llr = d_llr + size_t(off) * t.N;
         uint8_t* bits = at(d_bits, size_t(off) * t.K);
@@ -241,7 +272,6 @@ void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int
             hipLaunchKernelGGL(c->spa_kernel, dim3(n), dim3(c->dec_threads), c->lds_dec, s, c->ldev, llr, n, bits, iters, pay, st, var, sv);
         HIPCK(hipGetLastError());
     });
-    if (c->timing) { HIPCK(hipEventRecord(c->ev[slot][3], s)); ++c->ev_count; c->ev_fe[c->ev_count % mgpu_ctx::kEvRing] = false; }
 }
 
 void launch_txgen(mgpu_ctx* c, uint64_t seed, uint64_t frame0, int F, double noise_amp, int channel, double* d_bb, uint8_t* d_payload, hipStream_t s,

@@ -10,9 +10,9 @@ extern "C" {
 
 int mgpu_enable_timing(mgpu_ctx* c, int on) {
     if (!c) return MGPU_ERR_ARG;
-    c->timing = on != 0;
-    c->ev_count = 0;
-    for (auto& b : c->ev_fe) b = false;
+    c->kt.timing = on != 0;
+    c->kt.ev_count = 0;
+    for (auto& b : c->kt.ev_fe) b = false;
     return MGPU_OK;
 }
 
@@ -36,16 +36,17 @@ int mgpu_last_kernel_ms(mgpu_ctx* c, float ms[2]) {
 int mgpu_kernel_ms_avg(mgpu_ctx* c, float ms[2], int* n_launches) {
     if (!c || !ms) return MGPU_ERR_ARG;
     return guard(c, [&] {
-        need(c->timing && c->ev_count > 0, "timing not enabled or nothing launched");
-        const int n = c->ev_count < mgpu_ctx::kEvRing ? c->ev_count : mgpu_ctx::kEvRing;
+        const auto& k = c->kt;
+        need(k.timing && k.ev_count > 0, "timing not enabled or nothing launched");
+        const int n = k.ev_count < k.kEvRing ? k.ev_count : k.kEvRing;
         double fe = 0, dec = 0;
         int nfe = 0;
         for (int i = 0; i < n; ++i) {
-            HIPCK(hipEventSynchronize(c->ev[i][3]));
+            HIPCK(hipEventSynchronize(k.ev[i][3]));
             float t = 0;
-            HIPCK(hipEventElapsedTime(&t, c->ev[i][2], c->ev[i][3]));
+            HIPCK(hipEventElapsedTime(&t, k.ev[i][2], k.ev[i][3]));
             dec += t;
-            if (c->ev_fe[i]) { HIPCK(hipEventElapsedTime(&t, c->ev[i][0], c->ev[i][1])); fe += t; ++nfe; }
+            if (k.ev_fe[i]) { HIPCK(hipEventElapsedTime(&t, k.ev[i][0], k.ev[i][1])); fe += t; ++nfe; }
         }
         ms[0] = nfe ? float(fe / nfe) : 0.f;
         ms[1] = float(dec / n);
@@ -59,9 +60,10 @@ int mgpu_frontend_dev(mgpu_ctx* c, const void* d_bb, int F, void* d_llr, void* d
         need(d_bb && d_llr && F >= 0 && F <= c->max_batch, "bad argument (F must be <= max_batch)");
         if (F == 0) return;
         ensure_workspaces(c, WS_FRONTEND);
-        MgpuTapsDev taps{};
-        launch_frontend(c, static_cast<const double*>(d_bb), F, static_cast<float*>(d_llr),
-                        d_variance_f ? static_cast<float*>(d_variance_f) : c->d_variance, c->d_snrvar, taps, static_cast<hipStream_t>(stream));
+        SpanIo io;
+        io.bb = static_cast<const double*>(d_bb); io.llr = static_cast<float*>(d_llr);
+        io.var = d_variance_f ? static_cast<float*>(d_variance_f) : c->d_variance; io.snrvar = c->d_snrvar;
+        launch_frontend(c, io, F, MgpuTapsDev{}, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -82,16 +84,12 @@ int mgpu_rx_batch_dev(mgpu_ctx* c, const void* d_bb, int F, void* d_payload, voi
     return guard(c, [&] {
         need(d_bb && d_payload && d_stats && F >= 0 && F <= c->max_batch, "bad argument (F must be <= max_batch)");
         if (F == 0) return;
-        hipStream_t s = static_cast<hipStream_t>(stream);
         ensure_workspaces(c, WS_FRONTEND | (d_llr_opt ? 0u : unsigned(WS_LLR)));
-        float* llr = d_llr_opt ? static_cast<float*>(d_llr_opt) : c->d_llr;
-        MgpuTapsDev taps{};
-        launch_frontend(c, static_cast<const double*>(d_bb), F, llr, c->d_variance, c->d_snrvar, taps, s);
-        launch_decoder(c, llr, F, nullptr, nullptr, static_cast<uint8_t*>(d_payload), static_cast<MgpuStatsDev*>(d_stats),
-                       c->d_variance, c->d_snrvar, s);
-        launch_ladder(c, static_cast<const double*>(d_bb), F, llr, c->d_variance, c->d_snrvar, static_cast<uint8_t*>(d_payload),
-                      static_cast<MgpuStatsDev*>(d_stats), nullptr, s);
-        launch_zf_snr(c, F, static_cast<uint8_t*>(d_payload), static_cast<MgpuStatsDev*>(d_stats), s);
+        SpanIo io = own_span(c);
+        io.bb = static_cast<const double*>(d_bb);
+        if (d_llr_opt) io.llr = static_cast<float*>(d_llr_opt);
+        io.payload = static_cast<uint8_t*>(d_payload); io.stats = static_cast<MgpuStatsDev*>(d_stats);
+        launch_span(c, io, F, MgpuTapsDev{}, static_cast<hipStream_t>(stream));
     });
 }
 
@@ -161,10 +159,9 @@ int mgpu_rx_batch_taps(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, m
             if (taps->cycles) { dt.cycles = static_cast<long long*>(dalloc(16 * 8)); HIPCK(hipMemsetAsync(dt.cycles, 0, 16 * 8, s)); }
             if (taps->agc_gain) { dt.agc_gain = static_cast<double*>(dalloc(size_t(F) * 8)); HIPCK(hipMemsetAsync(dt.agc_gain, 0, size_t(F) * 8, s)); }
         }
-        launch_frontend(c, c->d_baseband, F, c->d_llr, c->d_variance, c->d_snrvar, dt, s);
-        launch_decoder(c, c->d_llr, F, nullptr, nullptr, c->d_payload, c->d_stats, c->d_variance, c->d_snrvar, s);
-        launch_ladder(c, c->d_baseband, F, c->d_llr, c->d_variance, c->d_snrvar, c->d_payload, c->d_stats, nullptr, s);      // the taps stay rung 0's
-        launch_zf_snr(c, F, c->d_payload, c->d_stats, s);
+        SpanIo io = own_span(c);
+        io.bb = c->d_baseband;
+        launch_span(c, io, F, dt, s);        // the taps stay rung 0's
         if (payload) HIPCK(hipMemcpyAsync(payload, c->d_payload, size_t(F) * t.payload_stride, hipMemcpyDeviceToHost, s));
         if (stats) HIPCK(hipMemcpyAsync(stats, c->d_stats, size_t(F) * sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, s));
         if (taps) {
@@ -187,24 +184,24 @@ static int rx_one_frame(mgpu_ctx* c, const double* bb, uint8_t* payload, mgpu_fr
         const auto& t = c->tab;
         const size_t in_bytes = size_t(t.frame_samples) * 16, out_bytes = size_t(t.payload_stride) + sizeof(MgpuStatsDev);
         hipStream_t s = c->stream;
-        if (!c->one_frame_graph) {
+        auto& one = c->one;
+        if (!one.graph) {
             ensure_workspaces(c, WS_FRONTEND | WS_LLR | WS_OUT);
             // The graph bakes in every address it touches, so it reads from a device buffer and staging buffers of its own
             // that live as long as the context (d_baseband may be reallocated by a larger batch later; the max_batch-sized
             // workspaces never are). Nothing is published in the context until the whole graph exists.
-            c->d_one_in.grow(in_bytes);
-            if (!c->h_one_in) HIPCK(host_alloc_on_node(&c->h_one_in.h, in_bytes, c->numa_node));
-            if (!c->h_one_out) HIPCK(host_alloc_on_node(&c->h_one_out.h, out_bytes, c->numa_node));
+            one.d_in.grow(in_bytes);
+            if (!one.h_in) HIPCK(host_alloc_on_node(&one.h_in.h, in_bytes, c->numa_node));
+            if (!one.h_out) HIPCK(host_alloc_on_node(&one.h_out.h, out_bytes, c->numa_node));
             hipGraph_t graph = nullptr;
             HIPCK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             try {
-                HIPCK(hipMemcpyAsync(c->d_one_in, c->h_one_in, in_bytes, hipMemcpyHostToDevice, s));
-                MgpuTapsDev dt{};
-                launch_frontend(c, c->d_one_in, 1, c->d_llr, c->d_variance, c->d_snrvar, dt, s);
-                launch_decoder(c, c->d_llr, 1, nullptr, nullptr, c->d_payload, c->d_stats, c->d_variance, c->d_snrvar, s);
-                launch_zf_snr(c, 1, c->d_payload, c->d_stats, s);
-                HIPCK(hipMemcpyAsync(c->h_one_out, c->d_payload, t.payload_stride, hipMemcpyDeviceToHost, s));
-                HIPCK(hipMemcpyAsync(static_cast<char*>(c->h_one_out.h) + t.payload_stride, c->d_stats, sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, s));
+                HIPCK(hipMemcpyAsync(one.d_in, one.h_in, in_bytes, hipMemcpyHostToDevice, s));
+                SpanIo io = own_span(c);
+                io.bb = one.d_in;
+                launch_span(c, io, 1, MgpuTapsDev{}, s);      // no ladder is set here (mgpu_rx_batch): its part returns before any HIP call
+                HIPCK(hipMemcpyAsync(one.h_out, c->d_payload, t.payload_stride, hipMemcpyDeviceToHost, s));
+                HIPCK(hipMemcpyAsync(static_cast<char*>(one.h_out.h) + t.payload_stride, c->d_stats, sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, s));
             } catch (...) {
                 (void)hipStreamEndCapture(s, &graph);
                 if (graph) (void)hipGraphDestroy(graph);
@@ -215,14 +212,48 @@ static int rx_one_frame(mgpu_ctx* c, const double* bb, uint8_t* payload, mgpu_fr
             const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
             HIPCK(e);
-            c->one_frame_graph.h = exec;
+            one.graph.h = exec;
         }
-        std::memcpy(c->h_one_in, bb, in_bytes);
-        HIPCK(hipGraphLaunch(c->one_frame_graph, s));
+        std::memcpy(one.h_in, bb, in_bytes);
+        HIPCK(hipGraphLaunch(one.graph, s));
         HIPCK(hipStreamSynchronize(s));
-        if (payload) std::memcpy(payload, c->h_one_out, t.payload_stride);
-        if (stats) std::memcpy(stats, static_cast<char*>(c->h_one_out.h) + t.payload_stride, sizeof(MgpuStatsDev));
+        if (payload) std::memcpy(payload, one.h_out, t.payload_stride);
+        if (stats) std::memcpy(stats, static_cast<char*>(one.h_out.h) + t.payload_stride, sizeof(MgpuStatsDev));
     });
+}
+
+// Chunk size: a decoder launch keeps the whole chip busy only from 2 workgroups per CU upwards (512 codewords on 256 CUs; a
+// smaller launch takes just as long), and a copy should carry a few MB; so chunks are multiples of that wave of workgroups
+// and a batch that is not larger than one chunk goes through in one piece.
+static int pipeline_chunk_frames(mgpu_ctx* c, int F, size_t frame_bytes) {
+    int& wave_of_wgs = c->hp.wave_of_wgs;
+    if (wave_of_wgs == 0) {              // per context: the devices of a pool need not be alike
+        int cus = 256;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device);
+        wave_of_wgs = 2 * (cus > 0 ? cus : 256);
+    }
+    int chunk = wave_of_wgs;
+    while (size_t(chunk) * frame_bytes < (size_t(8) << 20)) chunk += wave_of_wgs;
+    if (const char* e = std::getenv("MERCURY_RX_CHUNK")) chunk = std::max(1, std::atoi(e));
+    return std::min(chunk, F);
+}
+
+// The two pipes' streams, events and input buffers of `in_bytes`, the profile's events and the result staging, made on first use.
+static void pipeline_resources(mgpu_ctx* c, size_t in_bytes, size_t out_bytes) {
+    for (auto& p : c->hp.pipe) {
+        if (!p.stream) HIPCK(hipStreamCreateWithFlags(&p.stream.h, hipStreamNonBlocking));
+        if (!p.done) HIPCK(hipEventCreateWithFlags(&p.done.h, hipEventDisableTiming));
+        if (!p.copied) HIPCK(hipEventCreateWithFlags(&p.copied.h, hipEventDisableTiming));
+        if (p.d_in.capacity() < in_bytes) {
+            HIPCK(hipStreamSynchronize(p.stream));
+            p.d_in.grow(in_bytes);
+        }
+    }
+    // Results come back through page-locked staging owned by the context: a device-to-host copy into the caller's pageable
+    // arrays would block the host until the chunk's kernels have finished, i.e. before the next chunk's input copy could even
+    // be queued, and nothing would overlap.
+    if (!c->hp.h_out) HIPCK(host_alloc_on_node(&c->hp.h_out.h, out_bytes + 16, c->numa_node));
+    for (auto& e : c->hp.ev) if (!e) HIPCK(hipEventCreate(&e.h));
 }
 
 // The blocking host-buffer entry point for F > 1 with no stage taps: classic double buffering. The batch goes through in
@@ -233,38 +264,13 @@ static int rx_one_frame(mgpu_ctx* c, const double* bb, uint8_t* payload, mgpu_fr
 // frame offset. Results are byte-identical to the one-launch path (frames are independent).
 static void rx_batch_pipelined(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, mgpu_frame_stats* stats) {
     const auto& t = c->tab;
+    auto& hp = c->hp;
     ensure_workspaces(c, WS_FRONTEND | WS_LLR | WS_OUT);
     const size_t frame_bytes = size_t(t.frame_samples) * 16;
-    // chunk size: a decoder launch keeps the whole chip busy only from 2 workgroups per CU upwards (512 codewords on 256 CUs; a
-    // smaller launch takes just as long), and a copy should carry a few MB; so chunks are multiples of that wave of workgroups
-    // and a batch that is not larger than one chunk goes through in one piece.
-    if (c->wave_of_wgs == 0) {           // per context: the devices of a pool need not be alike
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device);
-        c->wave_of_wgs = 2 * (cus > 0 ? cus : 256);
-    }
-    const int wave_of_wgs = c->wave_of_wgs;
-    int chunk = wave_of_wgs;
-    while (size_t(chunk) * frame_bytes < (size_t(8) << 20)) chunk += wave_of_wgs;
-    if (const char* e = std::getenv("MERCURY_RX_CHUNK")) chunk = std::max(1, std::atoi(e));
-    chunk = std::min(chunk, F);
-    for (auto& p : c->pipe) {
-        if (!p.stream) HIPCK(hipStreamCreateWithFlags(&p.stream.h, hipStreamNonBlocking));
-        if (!p.done) HIPCK(hipEventCreateWithFlags(&p.done.h, hipEventDisableTiming));
-        if (!p.copied) HIPCK(hipEventCreateWithFlags(&p.copied.h, hipEventDisableTiming));
-        if (p.d_in.capacity() < size_t(chunk) * frame_bytes) {
-            HIPCK(hipStreamSynchronize(p.stream));
-            p.d_in.grow(size_t(chunk) * frame_bytes);
-        }
-    }
-    // Results come back through page-locked staging owned by the context: a device-to-host copy into the caller's pageable
-    // arrays would block the host until the chunk's kernels have finished, i.e. before the next chunk's input copy could even
-    // be queued, and nothing would overlap.
-    const size_t out_bytes = size_t(c->max_batch) * (t.payload_stride + sizeof(MgpuStatsDev));
-    if (!c->h_out) HIPCK(host_alloc_on_node(&c->h_out.h, out_bytes + 16, c->numa_node));
-    uint8_t* h_payload = static_cast<uint8_t*>(c->h_out.h);
+    const int chunk = pipeline_chunk_frames(c, F, frame_bytes);
+    pipeline_resources(c, size_t(chunk) * frame_bytes, size_t(c->max_batch) * (t.payload_stride + sizeof(MgpuStatsDev)));
+    uint8_t* h_payload = static_cast<uint8_t*>(hp.h_out.h);
     MgpuStatsDev* h_stats = reinterpret_cast<MgpuStatsDev*>(h_payload + ((size_t(c->max_batch) * t.payload_stride + 15) & ~size_t(15)));
-    MgpuTapsDev none{};
     // Two ways to overlap, chosen by the kind of host memory (measured on MI355X / PCIe Gen5, tools/bench_host_path.py):
     //  * page-locked input (mgpu_alloc_host, hipHostMalloc/Register): the copy is a true asynchronous DMA. One copy stream runs
     //    ahead into the other input buffer while ONE kernel stream keeps the launches in order (two decoder launches sharing the
@@ -275,60 +281,52 @@ static void rx_batch_pipelined(mgpu_ctx* c, const double* bb, int F, uint8_t* pa
     hipPointerAttribute_t attr{};
     const bool pinned = hipPointerGetAttributes(&attr, bb) == hipSuccess && attr.type == hipMemoryTypeHost;
     if (!pinned) (void)hipGetLastError();
-    for (auto& e : c->hp_ev) if (!e) HIPCK(hipEventCreate(&e.h));
     const int nchunks = (F + chunk - 1) / chunk;
     int k = 0;
     for (int off = 0; off < F; off += chunk, ++k) {
-        auto& p = c->pipe[k % mgpu_ctx::kPipes];                     // input buffer of this chunk
-        hipStream_t cs = pinned ? c->pipe[0].stream : p.stream, ks = pinned ? c->pipe[1].stream : p.stream;
+        auto& p = hp.pipe[k % hp.kPipes];                            // input buffer of this chunk
+        hipStream_t cs = pinned ? hp.pipe[0].stream : p.stream, ks = pinned ? hp.pipe[1].stream : p.stream;
         const int n = std::min(chunk, F - off);
-        if (pinned && k >= mgpu_ctx::kPipes) HIPCK(hipStreamWaitEvent(cs, p.done, 0));          // the front-end of chunk k-2 has consumed it
-        if (k == 0) HIPCK(hipEventRecord(c->hp_ev[0], cs));
+        if (pinned && k >= hp.kPipes) HIPCK(hipStreamWaitEvent(cs, p.done, 0));                 // the span of chunk k-2 has consumed it
+        if (k == 0) HIPCK(hipEventRecord(hp.ev[0], cs));
         HIPCK(hipMemcpyAsync(p.d_in, reinterpret_cast<const char*>(bb) + size_t(off) * frame_bytes, size_t(n) * frame_bytes, hipMemcpyHostToDevice, cs));
-        if (k == 0) HIPCK(hipEventRecord(c->hp_ev[1], cs));          // fill: nothing can compute before the first chunk has landed
-        if (k == nchunks - 1) HIPCK(hipEventRecord(c->hp_ev[2], cs)); // drain: what is left when the last input byte has landed
+        if (k == 0) HIPCK(hipEventRecord(hp.ev[1], cs));             // fill: nothing can compute before the first chunk has landed
+        if (k == nchunks - 1) HIPCK(hipEventRecord(hp.ev[2], cs));   // drain: what is left when the last input byte has landed
         if (pinned) {
             HIPCK(hipEventRecord(p.copied, cs));
             HIPCK(hipStreamWaitEvent(ks, p.copied, 0));
         }
-        launch_frontend(c, p.d_in, n, c->d_llr + size_t(off) * t.N, c->d_variance + off, c->d_snrvar + off, none, ks, 0, off);
-        const bool retries = c->lad.n > 1;                           // an estimator ladder's retries read the input again
-        if (pinned && !retries) HIPCK(hipEventRecord(p.done, ks));   // the front-end is the only reader of the input buffer
-        launch_decoder(c, c->d_llr + size_t(off) * t.N, n, nullptr, nullptr, c->d_payload + size_t(off) * t.payload_stride, c->d_stats + off,
-                       c->d_variance + off, c->d_snrvar + off, ks);
-        launch_ladder(c, p.d_in, n, c->d_llr + size_t(off) * t.N, c->d_variance + off, c->d_snrvar + off, c->d_payload + size_t(off) * t.payload_stride,
-                      c->d_stats + off, nullptr, ks, 0, off);
-        if (pinned && retries) HIPCK(hipEventRecord(p.done, ks));
-        launch_zf_snr(c, n, c->d_payload + size_t(off) * t.payload_stride, c->d_stats + off, ks, off);
-        if (payload) HIPCK(hipMemcpyAsync(h_payload + size_t(off) * t.payload_stride, c->d_payload + size_t(off) * t.payload_stride,
-                                          size_t(n) * t.payload_stride, hipMemcpyDeviceToHost, ks));
-        if (stats) HIPCK(hipMemcpyAsync(h_stats + off, c->d_stats + off, size_t(n) * sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, ks));
-        if (k == nchunks - 1) HIPCK(hipEventRecord(c->hp_ev[3], ks));
+        SpanIo io = own_span(c, off);
+        io.bb = p.d_in;
+        launch_span(c, io, n, MgpuTapsDev{}, ks, pinned ? static_cast<hipEvent_t>(p.done) : nullptr);     // p.done: behind the input's last reader
+        if (payload) HIPCK(hipMemcpyAsync(h_payload + size_t(off) * t.payload_stride, io.payload, size_t(n) * t.payload_stride, hipMemcpyDeviceToHost, ks));
+        if (stats) HIPCK(hipMemcpyAsync(h_stats + off, io.stats, size_t(n) * sizeof(MgpuStatsDev), hipMemcpyDeviceToHost, ks));
+        if (k == nchunks - 1) HIPCK(hipEventRecord(hp.ev[3], ks));
     }
-    for (auto& p : c->pipe) HIPCK(hipStreamSynchronize(p.stream));
-    c->hp_chunk = chunk; c->hp_nchunks = nchunks;
-    (void)hipEventElapsedTime(&c->hp_fill_ms, c->hp_ev[0], c->hp_ev[1]);
-    (void)hipEventElapsedTime(&c->hp_drain_ms, c->hp_ev[2], c->hp_ev[3]);
-    (void)hipEventElapsedTime(&c->hp_total_ms, c->hp_ev[0], c->hp_ev[3]);
+    for (auto& p : hp.pipe) HIPCK(hipStreamSynchronize(p.stream));
+    hp.chunk = chunk; hp.nchunks = nchunks;
+    (void)hipEventElapsedTime(&hp.fill_ms, hp.ev[0], hp.ev[1]);
+    (void)hipEventElapsedTime(&hp.drain_ms, hp.ev[2], hp.ev[3]);
+    (void)hipEventElapsedTime(&hp.total_ms, hp.ev[0], hp.ev[3]);
     if (payload) std::memcpy(payload, h_payload, size_t(F) * t.payload_stride);
     if (stats) std::memcpy(stats, h_stats, size_t(F) * sizeof(MgpuStatsDev));
 }
 
 int mgpu_host_path_last(mgpu_ctx* c, int* chunk_frames, int* n_chunks, float* fill_ms, float* drain_ms, float* total_ms) {
     if (!c) return MGPU_ERR_ARG;
-    if (chunk_frames) *chunk_frames = c->hp_chunk;
-    if (n_chunks) *n_chunks = c->hp_nchunks;
-    if (fill_ms) *fill_ms = c->hp_fill_ms;
-    if (drain_ms) *drain_ms = c->hp_drain_ms;
-    if (total_ms) *total_ms = c->hp_total_ms;
+    if (chunk_frames) *chunk_frames = c->hp.chunk;
+    if (n_chunks) *n_chunks = c->hp.nchunks;
+    if (fill_ms) *fill_ms = c->hp.fill_ms;
+    if (drain_ms) *drain_ms = c->hp.drain_ms;
+    if (total_ms) *total_ms = c->hp.total_ms;
     return MGPU_OK;
 }
 
 int mgpu_rx_batch(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, mgpu_frame_stats* stats, float* llr_opt) {
     // (an estimator ladder's retry depends on the frame's result: it does not go into the captured graph)
-    if (c && bb && F == 1 && !llr_opt && !c->timing && c->max_batch >= 1 && c->lad.n == 0 && !std::getenv("MERCURY_NO_GRAPH"))
+    if (c && bb && F == 1 && !llr_opt && !c->kt.timing && c->max_batch >= 1 && c->lad.n == 0 && !std::getenv("MERCURY_NO_GRAPH"))
         return rx_one_frame(c, bb, payload, stats);
-    if (c && bb && F > 1 && F <= c->max_batch && !llr_opt && !c->timing && !std::getenv("MERCURY_NO_PIPELINE"))
+    if (c && bb && F > 1 && F <= c->max_batch && !llr_opt && !c->kt.timing && !std::getenv("MERCURY_NO_PIPELINE"))
         return guard(c, [&] { rx_batch_pipelined(c, bb, F, payload, stats); });
     mgpu_stage_taps taps{};
     taps.llr_ldpc = llr_opt;

@@ -658,18 +658,17 @@ struct Loop {
     // :1132-1345 the hot path on the data symbols (they start `preamble` symbols into each extracted frame), then each window's result
     void decode(const std::vector<int>& act) {
         const int n = int(act.size());
-        MgpuTapsDev taps{};
-        if (!mfsk) taps.mean_H = ws.d_meanh.as<double>();
-        launch_frontend(c, ws.d_frames.as<double>() + size_t(pre) * t.Nofdm * 2, n, c->d_llr, c->d_variance, c->d_snrvar, taps, s, frame_n);
-        launch_decoder(c, c->d_llr, n, nullptr, nullptr, ws.d_payload_k.as<uint8_t>(), ws.d_stats_k.as<MgpuStatsDev>(), c->d_variance, c->d_snrvar, s);
-        // an estimator ladder retries inside this trial, before the host looks: a window a later rung decodes counts as decoded here
-        launch_ladder(c, ws.d_frames.as<double>() + size_t(pre) * t.Nofdm * 2, n, c->d_llr, c->d_variance, c->d_snrvar, ws.d_payload_k.as<uint8_t>(),
-                      ws.d_stats_k.as<MgpuStatsDev>(), taps.mean_H, s, frame_n);
+        const bool zf = t.estimator == MGPU_EST_ZF;
+        SpanIo io = own_span(c);
+        io.bb = ws.d_frames.as<double>() + size_t(pre) * t.Nofdm * 2; io.frame_stride = frame_n;
+        io.payload = ws.d_payload_k.as<uint8_t>(); io.stats = ws.d_stats_k.as<MgpuStatsDev>();
+        if (!mfsk) io.mean_H = ws.d_meanh.as<double>();
         // receive_stats.SNR is a double (telecom_system.cc:1343-1396): 10 log10(1 / variance) of the float variance (LS modes), -10 log10 of
         // the re-encoded symbols' error power (ZF modes). The kernels' records carry it as a float (the mgpu_frame_stats ABI); here the
         // argument of the logarithm comes back and the host takes it with the libm the reference calls: the double equals the reference's.
-        const bool zf = t.estimator == MGPU_EST_ZF;
-        launch_zf_snr(c, n, ws.d_payload_k.as<uint8_t>(), ws.d_stats_k.as<MgpuStatsDev>(), s, 0, zf ? ws.d_snr_k.as<double>() : nullptr);
+        if (zf) io.zf_var = ws.d_snr_k.as<double>();
+        // an estimator ladder retries inside this span, before the host looks: a window a later rung decodes counts as decoded here
+        launch_span(c, io, n, MgpuTapsDev{}, s);
         std::vector<double> zf_var(zf ? n : 0, 1.0), mh(n, 1.0);
         std::vector<float> snr_var(!zf && !mfsk ? n : 0, 1.0f);
         std::vector<MgpuStatsDev> st(n);

@@ -39,10 +39,10 @@ static int baseband_test_esn0_impl(mgpu_ctx* c, const double* esn0_db, int npoin
                 const uint64_t first = frame0 + uint64_t(p) * uint64_t(frames_per_point) + uint64_t(done);
                 launch_txgen(c, seed, first, n, hf ? 0.0 : noise_amp, channel, (hf ? d_clean : d_bb).as<double>(), d_sent.as<uint8_t>(), s);
                 if (hf) launch_hf_baseband(hf, d_clean.as<double>(), t.frame_samples, noise_amp, seed, first, n, d_bb.as<double>(), s);
-                MgpuTapsDev taps{};
-                launch_frontend(c, d_bb.as<double>(), n, c->d_llr, c->d_variance, c->d_snrvar, taps, s);
-                launch_decoder(c, c->d_llr, n, nullptr, nullptr, c->d_payload, c->d_stats, c->d_variance, c->d_snrvar, s);
-                launch_ladder(c, d_bb.as<double>(), n, c->d_llr, c->d_variance, c->d_snrvar, c->d_payload, c->d_stats, nullptr, s);
+                SpanIo io = own_span(c);
+                io.bb = d_bb.as<double>();
+                io.zf_snr = false;           // the error counter does not read snr_db: one launch less per batch in the zero-forcing modes
+                launch_span(c, io, n, MgpuTapsDev{}, s);
                 hipLaunchKernelGGL(mgpu_error_count_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_sent.as<uint8_t>(), c->d_payload, c->d_stats,
                                    t.payload_stride, t.nReal, n, d_acc.as<unsigned long long>());
                 HIPCK(hipGetLastError());

@@ -173,6 +173,31 @@ def test_a_frame_does_not_depend_on_its_batch():
     rx.close()
 
 
+@pytest.mark.parametrize("pinned", [False, True])
+def test_a_retry_reads_a_chunk_before_the_next_copy_lands_on_it(pinned, monkeypatch):
+    """The chunked host path with a ladder whose retries read a chunk's input again, in several chunks (a ragged tail of 2 frames behind
+    six chunks of 5; two chunks of 16): page-locked input has a copy stream running ahead into the buffer of chunk k-2, which must wait
+    for that chunk's retry and not only for its front-end; pageable input alternates two streams. Same records and rungs as one piece."""
+    from mercury_amd.physical_layer import pinned_empty
+    t, whole = _two_path(), _two_path_gpu()
+    bb = t["bb"]
+    if pinned:
+        buf = pinned_empty(bb.shape, np.complex128)
+        buf[...] = bb
+        bb = buf
+    rx = _rx(8, max_batch=F2)
+    rx.set_estimator_ladder([(21, 21), (5, 5)])
+    for chunk in ("5", "16"):
+        monkeypatch.setenv("MERCURY_RX_CHUNK", chunk)
+        for rep in range(2):
+            out = rx.receive(bb)
+            for f in range(F2):
+                assert _record(out, f) == _record(whole, f), (chunk, rep, f)
+            assert np.array_equal(rx.last_rungs(F2), whole["rungs"]), (chunk, rep)
+    monkeypatch.delenv("MERCURY_RX_CHUNK", raising=False)
+    rx.close()
+
+
 def test_nothing_to_retry_and_everything_to_retry():
     orc = Oracle(8, 50)
     clean = np.stack([orc.gen_frame(SEED, f, 0.0)[0] for f in range(16)])
