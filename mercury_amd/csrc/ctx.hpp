@@ -16,6 +16,7 @@
 #include "../../include/mercury_rxloop.h"
 #include "../../include/mercury_channel.h"
 #include "../../include/mercury_estimator.h"
+#include "../../include/mercury_diversity.h"
 #include "device_tables.h"
 #include "ls_rect.h"
 #include "tables.hpp"
@@ -164,6 +165,17 @@ struct Ladder {
     int last_F = 0;                                 // frames of the last fused-span call
 };
 
+// Diversity combining (include/mercury_diversity.h; combine.hip): the decoder's compact rows of a grouped span, [max_batch] each, created
+// with the first grouped call, and the device copy of a stand-alone combine's CSR.
+struct Diversity {
+    DevArray<float> d_llr;                          // [G][N] the groups' summed LLRs
+    DevArray<uint8_t> d_payload;
+    DevArray<MgpuStatsDev> d_stats;
+    DevArray<int> d_csr;                            // first[G + 1], member[]
+    Event done;                                     // behind the last user of the above: the next one, on whatever stream, waits for it
+    bool done_recorded = false;
+};
+
 // The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
 struct SpanIo {
     const double* bb = nullptr;         // input frames
@@ -175,6 +187,7 @@ struct SpanIo {
     double* zf_var = nullptr;           // zero-forcing modes: the argument of the SNR's logarithm per frame, or null
     int frame0 = 0;                     // row of the call's first frame in the context's max_batch-sized workspaces (d_eqdata, the ladder's d_rung)
     bool zf_snr = true;                 // false: no zero-forcing SNR launch (the baseband self-simulation's error counter does not read snr_db)
+    int group = 0;                      // D >= 1: frames g*D .. g*D+D-1 are the branches of one transmitted frame, decoded from their summed LLRs; 0: every frame alone
 };
 
 struct Workspace;   // rxloop.hip
@@ -226,6 +239,7 @@ struct mgpu_ctx {
     std::vector<double> pre_eq;     // [Nc][2] installed pre_equalization_channel (empty: none); dev.pre_eq is its device copy
     DevArray<double> d_pre_eq_buf;  // device copy of pre_eq
     Ladder lad;
+    Diversity div;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     // the blocking host-buffer entry points' chunk pipeline (rx_batch.hip rx_batch_pipelined)
@@ -304,6 +318,11 @@ void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, in
 // frames still undecoded and merges the ones that decode. Nothing without a ladder. Waits for the stream once per rung (the retry's frame count).
 void launch_ladder(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
 void launch_zf_snr(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
+// The grouped span's own steps (combine.hip): the context's compact rows, made on first use; the sums of G groups of member rows (uniform
+// groups of D when d_first is null, else the CSR on the device) into d_out; the groups' decode back to the F rows of io.
+void diversity_workspaces(mgpu_ctx* c);
+void launch_llr_combine(const float* d_llr, int D, const int* d_first, const int* d_member, int G, float* d_out, hipStream_t s);
+void launch_group_scatter(mgpu_ctx* c, const SpanIo& io, int F, int D, hipStream_t s);
 // mgpu_explicit_params as the table builder takes them; false (and *rc, err) when they are refused (create.hip)
 bool explicit_params_from(const mgpu_explicit_params* in, mgpu::ExplicitParams& xp, std::string& err, int* rc);
 // F generated frames from frame0 on into d_bb (and their payloads into d_payload, if given). channel -1: the transmit path's clean frames,

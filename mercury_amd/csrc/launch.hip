@@ -1,5 +1,5 @@
 // The kernel launches the host-side translation units share (declared in ctx.hpp): the fused receive span (launch_span) and its parts -
-// front-end and decoder, untimed and timed, and zero-forcing SNR; the ladder's part is in ladder.hip -, the synchroniser's
+// front-end and decoder, untimed and timed, and zero-forcing SNR; the ladder's part is in ladder.hip, the grouped span's kernels in combine.hip -, the synchroniser's
 // metric / mixer / MFSK search kernels with the host halves of their searches, and the frame generator.
 #include <algorithm>
 #include <atomic>
@@ -72,7 +72,27 @@ void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int
     if (k.timing) { HIPCK(hipEventRecord(k.ev[slot][3], s)); ++k.ev_count; k.ev_fe[k.ev_count % k.kEvRing] = false; }
 }
 
+// io.group = D: the D branches of each group share one decode (include/mercury_diversity.h). D = 1 takes the same steps, so the scatter
+// is held against the plain span byte for byte. No ladder part: the entry points refuse a ladder with retries, and a one-rung ladder's
+// window is the front-end's.
+static void launch_group_span(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s, hipEvent_t input_free) {
+    const int D = io.group, G = F / D;
+    need(F % D == 0 && io.payload && io.stats && F <= c->max_batch, "a grouped span needs payload and stats arrays of G * D <= max_batch frames");
+    Diversity& dv = c->div;
+    diversity_workspaces(c);
+    launch_frontend(c, io, F, taps, s);
+    if (input_free) HIPCK(hipEventRecord(input_free, s));                  // the front-end is the only reader of the input
+    if (dv.done_recorded) HIPCK(hipStreamWaitEvent(s, dv.done, 0));       // the compact rows are the context's: one grouped span at a time
+    launch_llr_combine(io.llr, D, nullptr, nullptr, G, dv.d_llr, s);
+    launch_decoder(c, dv.d_llr, G, nullptr, nullptr, dv.d_payload, dv.d_stats, nullptr, nullptr, s);
+    launch_group_scatter(c, io, F, D, s);
+    HIPCK(hipEventRecord(dv.done, s));
+    dv.done_recorded = true;
+    if (io.zf_snr) launch_zf_snr(c, io, F, s);     // per row: the group's payload against the branch's own equalised symbols
+}
+
 void launch_span(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s, hipEvent_t input_free) {
+    if (io.group > 0) { launch_group_span(c, io, F, taps, s, input_free); return; }
     const bool retries = c->lad.n > 1;           // an estimator ladder's retries read the input again
     launch_frontend(c, io, F, taps, s);
     if (input_free && !retries) HIPCK(hipEventRecord(input_free, s));      // the front-end is the only reader of the input

@@ -101,6 +101,7 @@ def load_library():
                                             C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mgpu_destroy.argtypes = [C.c_void_p]
         _hf_argtypes(lib)
+        _div_argtypes(lib)
         _lib = lib
     return _lib
 
@@ -165,6 +166,54 @@ def host_ls_estimate(cfg, grid, width, height, explicit=None):
     out = np.zeros(int(np.count_nonzero(~np.isnan(count.real))), np.complex128)
     if lib.mgpu_host_ls_estimate(cfg, ref, int(width), int(height), _ptr(g), _ptr(out)) != 0:
         raise MgpuError("mgpu_host_ls_estimate failed")
+    return out
+
+
+# ---- diversity combining (include/mercury_diversity.h, DESIGN.md §3.8) ------------------------------------------------------------
+DIVERSITY_SYMBOLS = ["mgpu_rx_batch_div_dev", "mgpu_rx_batch_div", "mgpu_llr_combine_dev", "mgpu_host_llr_combine", "mgpu_baseband_test_esn0_div"]
+DIVERSITY_MAX = 8
+
+
+def _div_argtypes(lib):
+    if not hasattr(lib, "mgpu_rx_batch_div_dev"):       # an older build loaded through MERCURY_GPU_LIB (A/B runs): these calls raise AttributeError
+        return
+    lib.mgpu_rx_batch_div_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mgpu_rx_batch_div.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mgpu_llr_combine_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mgpu_host_llr_combine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.mgpu_baseband_test_esn0_div.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_uint64, C.c_uint64, C.POINTER(HfChannel), C.c_int,
+                                                C.c_void_p]
+
+
+def _csr(groups):
+    """[[member, ...], ...] -> (first int32 [G + 1], member int32 [sum]); an empty group stays empty (the library refuses it)"""
+    first = np.zeros(len(groups) + 1, np.int32)
+    first[1:] = np.cumsum([len(g) for g in groups])
+    member = np.array([m for g in groups for m in g] + [0], np.int32)       # one spare entry: never a zero-length buffer
+    return first, member
+
+
+def _group_args(F, D, groups):
+    """the (D, first, member, G, rows out) of a combine call: uniform groups of D, or `groups` as a list of member lists"""
+    if (D is None) == (groups is None):
+        raise MgpuError("give either D (uniform groups) or groups (lists of member rows)")
+    if groups is None:
+        D = int(D)
+        return D, None, None, 0, (F // D if D > 0 else 0)
+    first, member = _csr(groups)
+    return 0, first, member, len(groups), len(groups)
+
+
+def host_llr_combine(llr, D=None, groups=None):
+    """mgpu_host_llr_combine, no GPU: float32 [F, 1600] -> the groups' LLR rows added in member order, float32 [G, 1600]. D: uniform groups
+    of D consecutive rows; groups: [[row, ...], ...], 1..DIVERSITY_MAX rows each."""
+    lib = load_library()
+    l = np.ascontiguousarray(llr, np.float32).reshape(-1, 1600)
+    D, first, member, G, rows = _group_args(l.shape[0], D, groups)
+    out = np.zeros((rows, 1600), np.float32)
+    rc = lib.mgpu_host_llr_combine(_ptr(l), l.shape[0], D, _ptr(first), _ptr(member), G, _ptr(out))
+    if rc != 0:
+        raise MgpuError("mgpu_host_llr_combine refused the groups (%d)" % rc, rc)
     return out
 
 
@@ -259,7 +308,9 @@ def cfg_explicit(M, rate16, preamble_nsymb, estimator):
 
 
 class MgpuError(RuntimeError):
-    pass
+    def __init__(self, message, code=None):
+        super().__init__(message)
+        self.code = code         # the library's status (MGPU_ERR_*) where one was returned
 
 
 class DeviceProps(C.Structure):    # mgpu_device_props
@@ -338,7 +389,7 @@ class RxPhy:
 
     def _ck(self, rc):
         if rc != 0:
-            raise MgpuError("mgpu error %d: %s" % (rc, self.lib.mgpu_last_error(self.h).decode()))
+            raise MgpuError("mgpu error %d: %s" % (rc, self.lib.mgpu_last_error(self.h).decode()), rc)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -409,6 +460,53 @@ class RxPhy:
                 out["llr_ldpc"] = llr
         return out
 
+    # ---- diversity combining (include/mercury_diversity.h) -------------------------------------
+    def receive_div(self, baseband, D, want_llr=False):
+        """receive() for F = G * D frames of which each D consecutive ones are branches of one transmitted frame: every branch through the
+        front-end, one decode per group on the sum of its branches' LLRs, the group's payload and decode result in every member row (with the
+        branch's own variance and SNR). want_llr: the BRANCH LLRs, float32 [F, 1600]. D = 1 is receive()."""
+        bb = np.ascontiguousarray(baseband, np.complex128).reshape(-1, self.frame_samples)
+        F = bb.shape[0]
+        payload = np.zeros((F, self.payload_stride), np.uint8)
+        stats = np.zeros(F, STATS_DTYPE)
+        llr = np.zeros((F, 1600), np.float32) if want_llr else None
+        self._ck(self.lib.mgpu_rx_batch_div(self.h, _ptr(bb), F, int(D), _ptr(payload), _ptr(stats), _ptr(llr)))
+        out = {"payload": payload, "stats": stats}
+        if want_llr:
+            out["llr_ldpc"] = llr
+        return out
+
+    def receive_div_dev(self, d_baseband, F, D, d_payload, d_stats, d_llr=None, stream=None):
+        self._ck(self.lib.mgpu_rx_batch_div_dev(self.h, d_baseband, F, int(D), d_payload, d_stats, d_llr, stream))
+
+    def llr_combine_dev(self, d_llr, F, d_out, D=None, groups=None, stream=None):
+        """mgpu_llr_combine_dev on device pointers: the sums of uniform groups of D rows, or of `groups` ([[row, ...], ...]), into d_out."""
+        D, first, member, G, _ = _group_args(F, D, groups)
+        self._ck(self.lib.mgpu_llr_combine_dev(self.h, d_llr, F, D, _ptr(first), _ptr(member), G, d_out, stream))
+
+    def llr_combine(self, llr, D=None, groups=None):
+        """host_llr_combine() on the GPU: float32 [F, 1600] -> float32 [G, 1600]."""
+        l = np.ascontiguousarray(llr, np.float32).reshape(-1, 1600)
+        F = l.shape[0]
+        rows = _group_args(F, D, groups)[4]
+        out = np.zeros((rows, 1600), np.float32)
+        self.lib.mgpu_device_malloc.restype = C.c_void_p
+        self.lib.mgpu_device_malloc.argtypes = [C.c_void_p, C.c_size_t]
+        self.lib.mgpu_device_free.argtypes = [C.c_void_p, C.c_void_p]
+        self.lib.mgpu_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        self.lib.mgpu_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        d_in, d_out = self.lib.mgpu_device_malloc(self.h, max(l.nbytes, 16)), self.lib.mgpu_device_malloc(self.h, max(out.nbytes, 16))
+        try:
+            if not d_in or not d_out:
+                raise MgpuError("device allocation failed")
+            self._ck(self.lib.mgpu_copy_to_device(self.h, d_in, _ptr(l), l.nbytes, None))
+            self.llr_combine_dev(d_in, F, d_out, D=D, groups=groups)
+            self._ck(self.lib.mgpu_copy_to_host(self.h, _ptr(out), d_out, out.nbytes, None))
+        finally:
+            self.lib.mgpu_device_free(self.h, d_in)
+            self.lib.mgpu_device_free(self.h, d_out)
+        return out
+
     def ldpc_decode(self, llr):
         """llr: float32 [F,1600] -> (bits uint8 [F,K], iterations int32 [F])  (cl_ldpc::decode)."""
         l = np.ascontiguousarray(llr, np.float32).reshape(-1, 1600)
@@ -441,12 +539,19 @@ class RxPhy:
     def txgen_dev(self, seed, frame0, F, noise_amp, d_baseband, d_payload=None, channel=0, stream=None):
         self._ck(self.lib.mgpu_txgen_dev(self.h, seed, frame0, F, noise_amp, channel, d_baseband, d_payload, stream))
 
-    def baseband_test_esn0(self, esn0_db, frames_per_point, seed=1, frame0=0, channel=0, hf_channel=None):
+    def baseband_test_esn0(self, esn0_db, frames_per_point, seed=1, frame0=0, channel=0, hf_channel=None, diversity=None):
         """cl_telecom_system::baseband_test_EsN0 per Es/N0 point (BER_PLOT_baseband): list of dicts with cl_error_rate's counters.
-        hf_channel (HfChannel or preset name): the Watterson channel on each frame (mgpu_baseband_test_esn0_hf; `channel` must then be 0)."""
+        hf_channel (HfChannel or preset name): the Watterson channel on each frame (mgpu_baseband_test_esn0_hf; `channel` must then be 0).
+        diversity = D: D branches per payload, each with its own channel realisation and noise, decoded from their summed LLRs
+        (mgpu_baseband_test_esn0_div); frames_per_point then counts payloads, and no hf_channel means AWGN."""
         pts = np.ascontiguousarray(np.atleast_1d(esn0_db), np.float64)
         out = (ErrorRate * pts.size)()
-        if hf_channel is None:
+        if diversity is not None:
+            if channel != 0:
+                raise MgpuError("diversity runs on the HF channel loop: channel must be 0")
+            ch = _hf("awgn" if hf_channel is None else hf_channel)
+            self._ck(self.lib.mgpu_baseband_test_esn0_div(self.h, _ptr(pts), pts.size, frames_per_point, seed, frame0, C.byref(ch), int(diversity), out))
+        elif hf_channel is None:
             self._ck(self.lib.mgpu_baseband_test_esn0(self.h, _ptr(pts), C.c_int(pts.size), C.c_longlong(frames_per_point), C.c_uint64(seed),
                                                       C.c_uint64(frame0), C.c_int(channel), out))
         else:

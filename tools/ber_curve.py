@@ -10,7 +10,10 @@ prints EsN0;BER;FER lines like the reference does, for far more frames per point
 reference's AWGN FER < 0.1 value (include/common/common_defines.h:130-147) to 40 dB above it in 1 dB steps, in one call; one JSON line
 gives the first point of the first run of three with FER < 0.1 ("fer01_esn0_db", null if none) beside the AWGN value.
 --ladder 21x21,5x21 (any form): an estimator ladder (include/mercury_estimator.h; windows as carriers x symbols) on the context; the JSON
-line then carries the frames each rung decoded."""
+line then carries the frames each rung decoded.
+--diversity D (baseband form; with --channel and at most a one-rung --ladder): D branches per payload, each with its own channel realisation
+and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_per_point counts payloads, Es/N0 is per branch.
+--points LO:HI:STEP (baseband form): the Es/N0 points instead of the reference's 25."""
 import json
 import os
 import sys
@@ -71,9 +74,40 @@ def passband(argv, channel):
                       "frames_per_s": len(res) * n / dt, **_ladder_fields(rx)}), file=sys.stderr)
 
 
+def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, seed=2024, warm=True):
+    """the baseband loop's records for one mode: (list of per-point dicts, summary dict)"""
+    per = max(1, diversity or 1)
+    rx = RxPhy(cfg, max_batch=min(n * per, 65536), agc=0, variance_source=0, decoder=dec)          # the variant baseband_test_EsN0 runs
+    rx.set_estimator_ladder(LADDER)
+    if pts is None:
+        pts = np.arange(-12.0, 13.0, 1.0)[:25] + (0.0 if cfg >= 7 else -6.0)
+    if warm:
+        rx.baseband_test_esn0(pts[:1], min(n, 4096), hf_channel=channel, diversity=diversity)
+    t0 = time.perf_counter()
+    res = rx.baseband_test_esn0(pts, n, seed=seed, hf_channel=channel, diversity=diversity)
+    dt = time.perf_counter() - t0
+    # a grouped span does not run the ladder's marking pass: with --diversity only the window is reported
+    extra = {"diversity": diversity, "ladder": ["%dx%d" % r for r in rx.estimator_ladder]} if diversity else _ladder_fields(rx)
+    rx.close()
+    return res, {"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
+                 "frames_per_s": len(res) * n * per / dt, **extra}
+
+
+def _option(argv, name):
+    """the value of --name V / --name=V, removed from argv; None when absent"""
+    for i, a in enumerate(argv):
+        if a == name or a.startswith(name + "="):
+            value = a.split("=", 1)[1] if "=" in a else argv[i + 1]
+            del argv[i: i + (1 if "=" in a else 2)]
+            return value
+    return None
+
+
 def main():
     argv = sys.argv[1:]
     channel = None
+    diversity = _option(argv, "--diversity")
+    points = _option(argv, "--points")
     for i, a in enumerate(argv):
         if a == "--channel" or a.startswith("--channel="):
             channel = a.split("=", 1)[1] if "=" in a else argv[i + 1]
@@ -87,21 +121,22 @@ def main():
             del argv[i: i + (1 if "=" in a else 2)]
             break
     if argv and argv[0] == "--passband":
+        if diversity is not None:
+            sys.exit("--diversity runs on the baseband loop (the passband loop's synchroniser does not combine)")
         return passband(argv[1:], channel)
     cfg = int(argv[0]) if argv else 8
     n = int(argv[1]) if len(argv) > 1 else 65536
     dec = {"spa": pl.DEC_SPA, "spa_fast": pl.DEC_SPA_FAST, "minsum": pl.DEC_MINSUM}[argv[2] if len(argv) > 2 else "spa"]
-    rx = RxPhy(cfg, max_batch=min(n, 65536), agc=0, variance_source=0, decoder=dec)          # the variant baseband_test_EsN0 runs
-    rx.set_estimator_ladder(LADDER)
-    pts = np.arange(-12.0, 13.0, 1.0)[:25] + (0.0 if cfg >= 7 else -6.0)
-    rx.baseband_test_esn0(pts[:1], min(n, 4096), hf_channel=channel)
-    t0 = time.perf_counter()
-    res = rx.baseband_test_esn0(pts, n, seed=2024, hf_channel=channel)
-    dt = time.perf_counter() - t0
+    if diversity is not None and len(LADDER) > 1:
+        sys.exit("--diversity takes at most a one-rung --ladder (a ladder's retries do not combine)")
+    pts = None
+    if points:
+        lo, hi, step = (float(v) for v in points.split(":"))
+        pts = np.arange(lo, hi + step / 2, step)
+    res, summary = baseband(cfg, n, dec, channel, int(diversity) if diversity is not None else None, pts)
     for r in res:
         print("%.1f;%.3e;%.3e;%.2f" % (r["esn0_db"], r["BER"], r["FER"], r["avg_iterations"]))
-    print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt, "frames_per_s": len(res) * n / dt,
-                      **_ladder_fields(rx)}), file=sys.stderr)
+    print(json.dumps(summary), file=sys.stderr)
 
 
 if __name__ == "__main__":
