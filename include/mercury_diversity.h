@@ -19,7 +19,9 @@
  * What the sum is. The front-end's LLRs are already scaled by 1 / variance. In the PSK modes (amp_restore: CONFIG_0..14) the equalised
  * cell keeps |H|, so for BPSK and QPSK the sum of two branches' LLRs is maximal-ratio combining, and for 8PSK it is close to it (the
  * max-log demapper is not linear in the cell). In the QAM and zero-forcing modes (the cell is divided by H) and in the MFSK modes it is
- * plain post-detection combining of per-branch soft decisions: still a gain, not the optimum.
+ * plain post-detection combining of per-branch soft decisions: still a gain, not the optimum. With the channel-aware demapper
+ * (mercury_demapper.h: MGPU_DEMAP_CSI on the context) every branch's LLRs carry |H|^2 / sigma2 per cell, and the sum is maximal-ratio
+ * combining for every constellation.
  *
  * Out of scope here, each untouched by this header:
  *   - mgpu_receive_byte_batch, mgpu_capture_*, mgpu_linksim_* and the passband self-simulations do not combine: the synchroniser, not

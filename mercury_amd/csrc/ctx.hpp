@@ -17,6 +17,7 @@
 #include "../../include/mercury_channel.h"
 #include "../../include/mercury_estimator.h"
 #include "../../include/mercury_diversity.h"
+#include "../../include/mercury_demapper.h"
 #include "device_tables.h"
 #include "ls_rect.h"
 #include "tables.hpp"
@@ -25,6 +26,7 @@ extern "C" const unsigned char mgpu_ldpc_blob[];
 extern "C" const unsigned long mgpu_ldpc_blob_size;
 
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads);
+extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_spa_lds_bytes(int E, int N);
 extern "C" size_t mgpu_gbf_lds_bytes(int N);
 extern "C" size_t mgpu_spa_fast_lds_bytes(int Sg, int N);
@@ -34,6 +36,8 @@ extern "C" __global__ void mgpu_frontend_kernel(MgpuDev, const double*, int, flo
 extern "C" __global__ void mgpu_frontend_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
 extern "C" __global__ void mgpu_frontend_rect_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
 extern "C" __global__ void mgpu_frontend_rect_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
+extern "C" __global__ void mgpu_frontend_csi_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
+extern "C" __global__ void mgpu_frontend_csi_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
 extern "C" __global__ void mgpu_ladder_select_kernel(const MgpuStatsDev*, int, int, int*, int*, int*, unsigned long long*);
 extern "C" __global__ void mgpu_ladder_merge_kernel(const int*, int, int, int, int, const float*, const float*, const float*, const double*, const uint8_t*,
                                                     const MgpuStatsDev*, float*, float*, float*, double*, uint8_t*, MgpuStatsDev*, int*, unsigned long long*);
@@ -176,6 +180,15 @@ struct Diversity {
     bool done_recorded = false;
 };
 
+// The context's demapper (include/mercury_demapper.h; demapper.hip). MGPU_DEMAP_CSI: every front-end launch of the fused span is the CSI form.
+struct Demapper {
+    int mode = MGPU_DEMAP_MAXLOG;
+    size_t lds = 0;                                 // the CSI form's LDS carve
+    MgpuLsRect own{};                               // the context's own square window as that (rectangular) form takes it
+    MgpuCsi arg{};
+    DevArray<uint16_t> d_sym_data;                  // arg.sym_data; made with the first MGPU_DEMAP_CSI
+};
+
 // The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
 struct SpanIo {
     const double* bb = nullptr;         // input frames
@@ -240,6 +253,7 @@ struct mgpu_ctx {
     DevArray<double> d_pre_eq_buf;  // device copy of pre_eq
     Ladder lad;
     Diversity div;
+    Demapper dmp;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     // the blocking host-buffer entry points' chunk pipeline (rx_batch.hip rx_batch_pipelined)
@@ -287,6 +301,8 @@ using FrontendKernel = void (*)(MgpuDev, const double*, int, float*, float*, flo
 inline FrontendKernel fe_kernel(int threads) { return threads == 1024 ? mgpu_frontend_kernel_t1024 : mgpu_frontend_kernel; }
 using FrontendRectKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
 inline FrontendRectKernel fe_rect_kernel(int threads) { return threads == 1024 ? mgpu_frontend_rect_kernel_t1024 : mgpu_frontend_rect_kernel; }
+using FrontendCsiKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
+inline FrontendCsiKernel fe_csi_kernel(int threads) { return threads == 1024 ? mgpu_frontend_csi_kernel_t1024 : mgpu_frontend_csi_kernel; }
 
 // whether the caller wants a tap with a row per frame (a launch's kernel writes them from row 0: one launch per call then)
 inline bool wants_frame_taps(const MgpuTapsDev& t) { return t.grid || t.H || t.eq || t.syms || t.llr_demod || t.variance || t.agc_gain; }
@@ -310,6 +326,7 @@ void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int
                     const float* d_var, const float* d_snrvar, hipStream_t s);
 // The same launches without the timing events, as the ladder's retries run them: the kernel timings describe rung 0.
 // rect: null = rung 0 (the ladder's first window where it is not the context's own, else the default kernel); a retry's window otherwise,
+// (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included)
 // whose `frames` list names the frame each row of the compact outputs in io belongs to.
 void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s);
 void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,

@@ -7,7 +7,7 @@
 // libgcc (GCC 11) __divdc3 main path. The two cases (|c| < |d| or not) are the same five operations on swapped operands, so the
 // operands are selected and the operations done once: lanes of a wavefront take either case at random, and as two branches every
 // wavefront paid for both (six divisions instead of three).
-__device__ __forceinline__ c2 cdiv(c2 n, c2 d) {
+__host__ __device__ __forceinline__ c2 cdiv(c2 n, c2 d) {      // (the host twin of the channel-aware demapper divides with it too: demapper.hip)
     const double a = n.re, b = n.im, c = d.re, dd = d.im;
     const bool sw = fabs(c) < fabs(dd);
     const double p = sw ? c : dd, q = sw ? dd : c;

@@ -79,13 +79,14 @@ __device__ __forceinline__ double serial_sum(const double* red, int n) {
 // array: 40 KB in mode 8, 67 KB in the BPSK modes (92 KB with a second full grid: one workgroup per compute unit).
 // The FFT runs on as many wavefronts as work areas fit next to the grid without costing a workgroup per compute unit.
 struct FeCarve { int fft_waves; size_t rsz, work, total; };
-__host__ __device__ inline FeCarve fe_carve(int G, int nPilots, int nBits, int FE_WAVES) {
+// after: bytes of the work area kept behind Hp and rsz once the FFTs are done (none in the plain form)
+__host__ __device__ inline FeCarve fe_carve_with(int G, int nPilots, int nBits, int FE_WAVES, size_t after) {
     FeCarve c;
     c.rsz = size_t(16) * (nPilots + 8) > size_t(4) * nBits ? size_t(16) * (nPilots + 8) : size_t(4) * nBits;   // + 8: zero pad behind the signed pilots (LS row reads)
     c.rsz = (c.rsz + 15) & ~size_t(15);
     const size_t per_wave = size_t(FFT256_STRIDE) * 16, lds_cu = size_t(160) * 1024;
     const size_t aux0 = size_t((G + 15) & ~15) + 64, aux = aux0 > 2048 ? aux0 : 2048;
-    const size_t fixed = size_t(16) * G + aux, need = size_t(16) * nPilots + c.rsz;
+    const size_t fixed = size_t(16) * G + aux, need = size_t(16) * nPilots + c.rsz + after;
     const size_t minimal = fixed + (need > 4 * per_wave ? need : 4 * per_wave);
     // LDS is handed out in blocks of 1280 bytes (measured: three workgroups of 53,504 bytes run side by side on a compute unit, three of
     // 54,016 do not — the runtime's occupancy calculator says 3 for both), so a workgroup's share is a whole number of blocks
@@ -104,18 +105,33 @@ __host__ __device__ inline FeCarve fe_carve(int G, int nPilots, int nBits, int F
     c.total = fixed + c.work;
     return c;
 }
+__host__ __device__ inline FeCarve fe_carve(int G, int nPilots, int nBits, int FE_WAVES) { return fe_carve_with(G, nPilots, nBits, FE_WAVES, 0); }
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve(G, nPilots, nBits, threads / 64).total; }
+// The channel-aware demapper's form (CSI below; include/mercury_demapper.h) keeps two more arrays in the work area: the terms of its own
+// noise variance, one double per pilot, and |h|^2 of every data cell as a float, in de-framed order. Both are written after the FFTs, whose
+// work areas they share, so the carve grows only where Hp + rsz + these exceed the FFT areas: 5.6 KB in the BPSK modes (73.6 -> 79.4 KB, still
+// two workgroups per compute unit - with a float per CELL it would be 82.6 KB and one), nothing in the others.
+__host__ __device__ inline size_t fe_csi_var_bytes(int nPilots) { return (size_t(8) * nPilots + 15) & ~size_t(15); }
+__host__ __device__ inline FeCarve fe_carve_csi(int G, int nPilots, int nBits, int FE_WAVES) {
+    return fe_carve_with(G, nPilots, nBits, FE_WAVES, fe_csi_var_bytes(nPilots) + ((size_t(4) * (G - nPilots) + 15) & ~size_t(15)));
+}
+extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve_csi(G, nPilots, nBits, threads / 64).total; }
+// workgroups per compute unit the LDS lets a carve of `bytes` have, counted as fe_carve counts them (blocks of 1280 bytes, 256 of overhead)
+extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(160) * 1024 / ((bytes + 256 + 1279) / 1280 * 1280)); }
 
 // RECT: the LS window has a width and a height of its own (`win`, ls_rect.h) instead of T.lsw squared, and the workgroup may take its
 // frame from a list: the form the estimator ladder runs (ladder.hip). Everything else is the one body.
-template <int FE_THREADS, bool RECT>
+// CSI: the channel-aware demapper (include/mercury_demapper.h). Every cell is equalised with the full estimate h (no
+// restore_channel_amplitude), the LLRs are (|h|^2 / sigma2) (d1 - d0) with sigma2 = mean |g - h x|^2 over the pilots, and the H and eq taps
+// show that h and g / h. variance, SNR variance and mean_H are still the plain form's, term for term.
+template <int FE_THREADS, bool RECT, bool CSI>
 __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
                                          float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out,
-                                         const MgpuTapsDev& taps, const MgpuLsRect& win) {
+                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi) {
     constexpr int FE_WAVES = FE_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int G = T.G, Nc = 50, Ns = T.Nsymb;
-    const FeCarve carve = fe_carve(G, T.nPilots, T.nBits, FE_WAVES);
+    const FeCarve carve = CSI ? fe_carve_csi(G, T.nPilots, T.nBits, FE_WAVES) : fe_carve(G, T.nPilots, T.nBits, FE_WAVES);
     c2* grid = reinterpret_cast<c2*>(smem);
     c2* Hp = grid + G;                                              // channel estimate at the pilots, pilot order; Hp and red are the FFT work area first
     c2* fftb = Hp;
@@ -126,6 +142,9 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
     c2* tw = reinterpret_cast<c2*>(__builtin_assume_aligned(reinterpret_cast<unsigned char*>(Hp) + carve.work, 16));
     int8_t* type = reinterpret_cast<int8_t*>(tw);                   // 0 data, +1 / -1 pilot with that sign; takes the twiddles' place after the FFTs
     double* scal = reinterpret_cast<double*>(type + ((G + 15) & ~15));
+    // CSI: behind rsz, the terms of sigma2 in pilot order and |h|^2 per data cell in de-framed order
+    [[maybe_unused]] double* red3 = reinterpret_cast<double*>(__builtin_assume_aligned(reinterpret_cast<unsigned char*>(red) + carve.rsz, 16));
+    [[maybe_unused]] float* wf = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(red3) + fe_csi_var_bytes(T.nPilots));
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f = blockIdx.x;
@@ -321,7 +340,8 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         const int c = int(q.x & 0xfffu), pa = int((q.x >> 12) & 0x3ffu), pb = int(q.x >> 22);
         const int a = int(q.y & 0xffu), b = int((q.y >> 8) & 0xffu), i = int(q.y >> 16);
         c2 h = lerp(Hp[pa], double(a), Hp[pb], double(b), double(i));
-        if (T.amp_restore) h = unit_phasor(h);
+        if constexpr (CSI) wf[idx] = float(h.re * h.re + h.im * h.im);
+        else if (T.amp_restore) h = unit_phasor(h);
         if (taps.H) { taps.H[(size_t(f) * G + c) * 2] = h.re; taps.H[(size_t(f) * G + c) * 2 + 1] = h.im; }
         grid[c] = cdiv(grid[c], h);
     };
@@ -337,6 +357,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         const int c = T.pilot_cell[p];
         const c2 g = grid[c];
         c2 h = Hp[p];
+        [[maybe_unused]] const c2 h0 = h;
         const double x = type[c] < 0 ? -boost : boost;
         if (T.amp_restore) {                                         // measure_variance(equalized_data_without_amplitude_restoration)
             const c2 e0 = cdiv(g, h);
@@ -344,9 +365,16 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
             red[p] = dr * dr + di * di;
             h = unit_phasor(h);
         }
-        if (taps.H) { taps.H[(size_t(f) * G + c) * 2] = h.re; taps.H[(size_t(f) * G + c) * 2 + 1] = h.im; }
+        if constexpr (CSI) {
+            if (taps.H) { taps.H[(size_t(f) * G + c) * 2] = h0.re; taps.H[(size_t(f) * G + c) * 2 + 1] = h0.im; }
+            const double dr = g.re - h0.re * x, di = g.im - h0.im * x;
+            red3[p] = dr * dr + di * di;
+        } else {
+            if (taps.H) { taps.H[(size_t(f) * G + c) * 2] = h.re; taps.H[(size_t(f) * G + c) * 2 + 1] = h.im; }
+        }
         const c2 e = cdiv(g, h);
-        grid[c] = e;
+        if constexpr (CSI) grid[c] = cdiv(g, h0);
+        else grid[c] = e;
         const c2 v = T.var_eq ? e : g;
         const double dr = v.re - x, di = v.im - 0.0;
         red2[p] = dr * dr + di * di;
@@ -362,6 +390,13 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         double var = serial_sum(red2, T.nPilots);
         var /= double(T.nPilots);
         scal[1] = var;
+    }
+    if constexpr (CSI) {
+        if (tid == 64) {      // the third chain on a wavefront of its own
+            double var = serial_sum(red3, T.nPilots);
+            var /= double(T.nPilots);
+            scal[4] = var;
+        }
     }
     for (;;) {
         int base = 0;
@@ -384,7 +419,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 
     FE_STAMP();   // 6: equalise + variance done
     // ---- deframe + time/freq de-interleave + max-log demap -------------------------------------
-    const float inv_var = 1 / variance;
+    const float inv_var = CSI ? 1 / float(scal[4]) : 1 / variance;
     const int M = T.M, bps = T.bps;
     // cl_psk::demod (psk.cc:278-326): squared distance to every constellation point in double, narrowed to float; per bit the smallest
     // distance among the points with that bit set / clear; LLR = (d1 - d0) / variance in float. Specialised per constellation size so that
@@ -396,6 +431,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         constexpr int BPS = MM == 2 ? 1 : MM == 4 ? 2 : MM == 8 ? 3 : MM == 16 ? 4 : 5;
         for (int k = tid; k < T.nData; k += FE_THREADS) {
             const c2 s = eq[T.sym_src[k]];
+            const float scale = CSI ? inv_var * wf[csi.sym_data[k]] : inv_var;
             if (taps.syms) { taps.syms[(size_t(f) * T.nData + k) * 2] = s.re; taps.syms[(size_t(f) * T.nData + k) * 2 + 1] = s.im; }
             float d0[BPS], d1[BPS];
 #pragma unroll
@@ -411,7 +447,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
                 }
             }
 #pragma unroll
-            for (int b = 0; b < BPS; ++b) llr[k * BPS + (BPS - 1 - b)] = inv_var * (d1[b] - d0[b]);
+            for (int b = 0; b < BPS; ++b) llr[k * BPS + (BPS - 1 - b)] = scale * (d1[b] - d0[b]);
         }
     };
     if (M == 2 && bps == 1) demap_all(std::integral_constant<int, 2>());
@@ -422,6 +458,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
     else
     for (int k = tid; k < T.nData; k += FE_THREADS) {
         const c2 s = eq[T.sym_src[k]];
+        const float scale = CSI ? inv_var * wf[csi.sym_data[k]] : inv_var;
         if (taps.syms) { taps.syms[(size_t(f) * T.nData + k) * 2] = s.re; taps.syms[(size_t(f) * T.nData + k) * 2 + 1] = s.im; }
         float d0[5], d1[5];
 #pragma unroll
@@ -439,7 +476,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         }
 #pragma unroll
         for (int b = 0; b < 5; ++b)
-            if (b < bps) llr[k * bps + (bps - 1 - b)] = inv_var * (d1[b] - d0[b]);
+            if (b < bps) llr[k * bps + (bps - 1 - b)] = scale * (d1[b] - d0[b]);
     }
     __syncthreads();
     if (taps.llr_demod) for (int i = tid; i < T.nBits; i += FE_THREADS) taps.llr_demod[size_t(f) * T.nBits + i] = llr[i];
@@ -453,13 +490,13 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<512, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{});
+    fe_frame<512, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<1024, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{});
+    fe_frame<1024, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{});
 }
 
 // The same body with a rectangular LS window and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when
@@ -467,11 +504,25 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_rect_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<512, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win);
+    fe_frame<512, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<1024, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win);
+    fe_frame<1024, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{});
+}
+
+// The rectangular form with the channel-aware demapper (include/mercury_demapper.h): the plain span (the context's own window passed as a
+// rectangle), rung 0 and every retry of an estimator ladder while the context's demapper is MGPU_DEMAP_CSI.
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
+    fe_frame<512, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
+    fe_frame<1024, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi);
 }

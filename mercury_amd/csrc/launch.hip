@@ -36,13 +36,20 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
         return;
     }
     if (!rect && c->lad.n > 0 && !c->lad.rung0_is_default) rect = &c->lad.win[0];      // rung 0 of an estimator ladder with a window of its own
+    const bool csi = c->dmp.mode == MGPU_DEMAP_CSI;                                    // the channel-aware demapper: one kernel for every window
+    if (csi && !rect) rect = &c->dmp.own;
     for_frame_chunks(F, [&](int off, int n) {
         begin_chunk(off);
         const double* bb = io.bb + size_t(off) * stride * 2;
         float *llr = io.llr + size_t(off) * t.N, *var = io.var + off, *snrvar = at(io.snrvar, off);
         if (rect) {
             MgpuLsRect w = *rect;
+            const bool retry = w.frames != nullptr;
             if (w.frames) { w.frames += off; bb = io.bb; }       // a retry: workgroup b reads frame frames[b] and writes row b
+            if (csi)
+                hipLaunchKernelGGL(fe_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar,
+                                   retry ? static_cast<double*>(nullptr) : at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2), tp, w, c->dmp.arg);
+            else
             hipLaunchKernelGGL(fe_rect_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar,
                                static_cast<double*>(nullptr), tp, w);
         } else {

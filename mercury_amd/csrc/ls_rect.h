@@ -2,10 +2,16 @@
 // instantiation takes it (frontend.hip), and the frame list of a ladder retry (ladder.hip). A kernel argument of its own:
 // MgpuDev (device_tables.h) stays what the default kernels and the decoder are built from.
 #pragma once
+#include <stdint.h>
 
 struct MgpuLsRect {
     const double* weight;   // [width*height+1] boost / sum_n(boost^2) per window population n (tables.cpp ls_weight_table)
     const int* frames;      // workgroup b reads frame frames[b] and writes row b of compact outputs; NULL: frame b
     int hw_f, hw_t;         // half-widths: frequency (columns) and time (rows)
     int lattice;            // MgpuDev::regular_lattice evaluated for this width: 2 = every clipped window row holds >= 3 pilots of each column residue
+};
+
+// What the channel-aware demapper's front-end (frontend.hip CSI; include/mercury_demapper.h) needs beyond MgpuDev, again an argument of its own.
+struct MgpuCsi {
+    const uint16_t* sym_data;   // [nData] de-framed position of the cell MgpuDev::sym_src[k] names: where that cell's |h|^2 is kept
 };

@@ -169,6 +169,45 @@ def host_ls_estimate(cfg, grid, width, height, explicit=None):
     return out
 
 
+# ---- the channel-aware demapper (include/mercury_demapper.h) --------------------------------------------------------
+DEMAPPER_SYMBOLS = ["mgpu_set_demapper", "mgpu_get_demapper", "mgpu_host_demap_csi"]
+DEMAPPERS = {"maxlog": 0, "csi": 1}
+
+
+def _explicit_struct(explicit):
+    if not explicit:
+        return None
+    seeds = any(k in explicit for k in ("pilot_seed", "scrambler_seed", "preamble_seed"))
+    return ExplicitParams(float(explicit.get("pilot_boost", 0.0)), int(explicit.get("ls_window", 0)), 1 if seeds else 0,
+                          int(explicit.get("pilot_seed", 0)), int(explicit.get("scrambler_seed", 0)), int(explicit.get("preamble_seed", 1)),
+                          int(explicit.get("Nc", 0)), int(explicit.get("Nfft", 0)), int(explicit.get("Dx", 0)), int(explicit.get("Dy", 0)),
+                          int(explicit.get("Nsymb", 0)))
+
+
+def host_demap_csi(cfg, grid, H, explicit=None):
+    """mgpu_host_demap_csi, no GPU: one frame's cell grid (after the AGC) and channel estimate at every cell (complex128 [Nsymb * Nc] each)
+    -> (the demodulated LLRs in the demapper's order: float32 [nBits], sigma2). explicit: as RxPhy's."""
+    lib = load_library()
+    lib.mgpu_host_demap_csi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    g = np.ascontiguousarray(grid, np.complex128).ravel()
+    h = np.ascontiguousarray(H, np.complex128).ravel()
+    if g.size != h.size:
+        raise MgpuError("host_demap_csi: grid and H must have one entry per cell")
+    xp = _explicit_struct(explicit)
+    ref = C.byref(xp) if xp is not None else None
+    # nBits of the (possibly explicit) geometry: the entries a call on an all-zero grid with H = 1 writes
+    count = np.full(g.size * 5, np.nan, np.float32)
+    rc = lib.mgpu_host_demap_csi(int(cfg), ref, _ptr(np.zeros_like(g)), _ptr(np.ones_like(g)), _ptr(count), None)
+    if rc != 0:
+        raise MgpuError("mgpu_host_demap_csi failed (%d)" % rc, rc)
+    llr = np.zeros(int(np.count_nonzero(~np.isnan(count))), np.float32)
+    sigma2 = C.c_double()
+    rc = lib.mgpu_host_demap_csi(int(cfg), ref, _ptr(g), _ptr(h), _ptr(llr), C.byref(sigma2))
+    if rc != 0:
+        raise MgpuError("mgpu_host_demap_csi failed (%d)" % rc, rc)
+    return llr, float(sigma2.value)
+
+
 # ---- diversity combining (include/mercury_diversity.h, DESIGN.md §3.8) ------------------------------------------------------------
 DIVERSITY_SYMBOLS = ["mgpu_rx_batch_div_dev", "mgpu_rx_batch_div", "mgpu_llr_combine_dev", "mgpu_host_llr_combine", "mgpu_baseband_test_esn0_div"]
 DIVERSITY_MAX = 8
@@ -432,6 +471,22 @@ class RxPhy:
         self.lib.mgpu_estimator_ladder_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self._ck(self.lib.mgpu_estimator_ladder_counters(self.h, _ptr(by), C.byref(n), 1 if reset else 0))
         return by, int(n.value)
+
+    # ---- the channel-aware demapper (include/mercury_demapper.h) -------------------------------
+    def set_demapper(self, name):
+        """"maxlog": the reference's demapper (one variance per frame; the default). "csi": max-log LLRs weighted by |H|^2 per cell, in
+        every receive entry point of this context."""
+        if name not in DEMAPPERS:
+            raise MgpuError("demapper must be one of %s" % sorted(DEMAPPERS))
+        self.lib.mgpu_set_demapper.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.lib.mgpu_set_demapper(self.h, DEMAPPERS[name]))
+
+    @property
+    def demapper(self):
+        v = C.c_int()
+        self.lib.mgpu_get_demapper.argtypes = [C.c_void_p, C.c_void_p]
+        self._ck(self.lib.mgpu_get_demapper(self.h, C.byref(v)))
+        return {n: k for k, n in DEMAPPERS.items()}[v.value]
 
     # ---- host-buffer entry points -------------------------------------------------------------
     def receive(self, baseband, taps=False, want_llr=False):

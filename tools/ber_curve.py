@@ -13,7 +13,9 @@ gives the first point of the first run of three with FER < 0.1 ("fer01_esn0_db",
 line then carries the frames each rung decoded.
 --diversity D (baseband form; with --channel and at most a one-rung --ladder): D branches per payload, each with its own channel realisation
 and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_per_point counts payloads, Es/N0 is per branch.
---points LO:HI:STEP (baseband form): the Es/N0 points instead of the reference's 25."""
+--points LO:HI:STEP (baseband form): the Es/N0 points instead of the reference's 25.
+--demapper csi (any form, with any of the above): LLRs weighted by |H|^2 per cell (include/mercury_demapper.h) instead of the reference's
+demapper."""
 import json
 import os
 import sys
@@ -31,6 +33,7 @@ AWGN_FER01 = {0: -10.0, 1: -7.5, 2: -6.0, 3: -4.5, 4: -3.5, 5: -2.5, 6: -1.5, 7:
 
 
 LADDER = []          # --ladder
+DEMAPPER = ["maxlog"]   # --demapper
 
 
 def _ladder_fields(rx):
@@ -44,6 +47,7 @@ def threshold(cfg, n, channel):
     """One call over Es/N0 = AWGN value - 3 dB ... + 40 dB in 1 dB steps; the first point of the first run of three with FER < 0.1."""
     rx = RxPhy(cfg, max_batch=min(n, 1024))
     rx.set_estimator_ladder(LADDER)
+    rx.set_demapper(DEMAPPER[0])
     pts = AWGN_FER01.get(cfg, -20.0) - 3.0 + np.arange(44, dtype=np.float64)
     t0 = time.perf_counter()
     res = rx.passband_test_esn0(pts, n, 1500.0, seed=2024, output_power_watt=1.0, hf_channel=channel)
@@ -52,7 +56,7 @@ def threshold(cfg, n, channel):
     fer = [r["FER"] for r in res]
     first = next((float(pts[i]) for i in range(len(pts) - 2) if max(fer[i: i + 3]) < 0.1), None)
     print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "frames_per_point": n, "fer01_esn0_db": first,
-                      "awgn_reference_db": AWGN_FER01.get(cfg), "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
+                      "awgn_reference_db": AWGN_FER01.get(cfg), "demapper": DEMAPPER[0], "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
                       "seconds": round(time.perf_counter() - t0, 2), **extra}), flush=True)
 
 
@@ -63,6 +67,7 @@ def passband(argv, channel):
     n = int(argv[1]) if len(argv) > 1 else 4096
     rx = RxPhy(cfg, max_batch=min(n, 1024))
     rx.set_estimator_ladder(LADDER)
+    rx.set_demapper(DEMAPPER[0])
     pts = np.arange(31) * 1.0 - 25.0 if cfg >= 100 else np.arange(25) * 0.5 - 10.0
     rx.passband_test_esn0(pts[-1:], min(n, 1024), 1500.0, output_power_watt=1.0, hf_channel=channel)
     t0 = time.perf_counter()
@@ -71,7 +76,7 @@ def passband(argv, channel):
     for r in res:
         print("%.1f;%.3e;%.3e;%d" % (r["esn0_db"], r["BER"], r["FER"], r["crc_ok_frames"]))
     print(json.dumps({"cfg": cfg, "mode": "passband", "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
-                      "frames_per_s": len(res) * n / dt, **_ladder_fields(rx)}), file=sys.stderr)
+                      "frames_per_s": len(res) * n / dt, "demapper": DEMAPPER[0], **_ladder_fields(rx)}), file=sys.stderr)
 
 
 def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, seed=2024, warm=True):
@@ -79,6 +84,7 @@ def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, see
     per = max(1, diversity or 1)
     rx = RxPhy(cfg, max_batch=min(n * per, 65536), agc=0, variance_source=0, decoder=dec)          # the variant baseband_test_EsN0 runs
     rx.set_estimator_ladder(LADDER)
+    rx.set_demapper(DEMAPPER[0])
     if pts is None:
         pts = np.arange(-12.0, 13.0, 1.0)[:25] + (0.0 if cfg >= 7 else -6.0)
     if warm:
@@ -90,7 +96,7 @@ def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, see
     extra = {"diversity": diversity, "ladder": ["%dx%d" % r for r in rx.estimator_ladder]} if diversity else _ladder_fields(rx)
     rx.close()
     return res, {"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
-                 "frames_per_s": len(res) * n * per / dt, **extra}
+                 "frames_per_s": len(res) * n * per / dt, "demapper": DEMAPPER[0], **extra}
 
 
 def _option(argv, name):
@@ -108,6 +114,9 @@ def main():
     channel = None
     diversity = _option(argv, "--diversity")
     points = _option(argv, "--points")
+    DEMAPPER[0] = _option(argv, "--demapper") or "maxlog"
+    if DEMAPPER[0] not in pl.DEMAPPERS:
+        sys.exit("--demapper: one of " + ", ".join(pl.DEMAPPERS))
     for i, a in enumerate(argv):
         if a == "--channel" or a.startswith("--channel="):
             channel = a.split("=", 1)[1] if "=" in a else argv[i + 1]
