@@ -1,0 +1,147 @@
+// Pilot-aided residual carrier-offset correction (include/mercury_cfo.h): the context's setting, which selects the front-end's CFO forms in
+// launch.hip's front-end core, the stage's tables, and the host twin. The kernel is frontend.hip's; the twin's arithmetic is cfo_rule.cpp's.
+#include <cstring>
+#include <memory>
+#include <mutex>
+
+#include "ctx.hpp"
+
+extern "C" void mgpu_internal_cfo_rule(const double* grid, double* out, int Ns, int Nc, int Dy, const int8_t* sign, const uint16_t* pair,
+                                       const uint16_t* first, double* step_out);
+
+namespace {
+
+// Per carrier, its pilots in ascending symbol order; every consecutive pair whose symbol distance is Dy, carrier after carrier.
+struct CfoChains {
+    std::vector<uint16_t> pair, first;
+    std::vector<int8_t> sign;           // [G] 0 data, +1 / -1 pilot
+};
+CfoChains cfo_chains(const mgpu::ModeTables& t) {
+    CfoChains k;
+    const int G = t.Nsymb * t.Nc, Dy = t.xp.Dy;
+    if (G > 65535) throw std::runtime_error("frame geometry too large for the carrier-offset stage's tables");
+    k.sign.resize(size_t(G));
+    for (int i = 0; i < G; ++i) k.sign[size_t(i)] = t.cell_type[size_t(i)] ? (t.pilot_val[size_t(i)] < 0 ? int8_t(-1) : int8_t(1)) : int8_t(0);
+    for (int c = 0; c < t.Nc; ++c) {
+        k.first.push_back(uint16_t(k.pair.size() / 2));
+        int last = -1;
+        for (int s = 0; s < t.Nsymb; ++s) {
+            if (!t.cell_type[size_t(s * t.Nc + c)]) continue;
+            if (last >= 0 && s - last == Dy) { k.pair.push_back(uint16_t(last * t.Nc + c)); k.pair.push_back(uint16_t(s * t.Nc + c)); }
+            last = s;
+        }
+    }
+    k.first.push_back(uint16_t(k.pair.size() / 2));
+    return k;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgpu_set_cfo(mgpu_ctx* c, int cfo) {
+    if (!c) return MGPU_ERR_ARG;
+    if (cfo != MGPU_CFO_OFF && cfo != MGPU_CFO_PILOTS) {
+        c->err = "cfo must be MGPU_CFO_OFF or MGPU_CFO_PILOTS";
+        return MGPU_ERR_ARG;
+    }
+    const auto& t = c->tab;
+    if (t.mfsk_M > 0) {
+        if (cfo == MGPU_CFO_OFF) return MGPU_OK;
+        c->err = "the pilot-aided carrier-offset correction needs an OFDM mode (the MFSK modes have no pilots)";
+        return MGPU_ERR_UNSUPPORTED;
+    }
+    Cfo& K = c->cfo;
+    return guard(c, [&] {
+        // the stage's scratch - Nc carrier sums at the head of the work area, a phasor per symbol from entry 64 on - lies inside the
+        // four FFT work areas every carve has (frontend.hip)
+        need(t.Nc <= 64 && t.Nsymb <= 4 * 256 - 64, "frame geometry outside the carrier-offset stage's scratch");
+        HIPCK(hipStreamSynchronize(c->stream));
+        if (cfo == MGPU_CFO_PILOTS) {
+            if (!K.d_pair) {
+                const CfoChains k = cfo_chains(t);
+                DevArray<uint16_t> d_pair = upload(k.pair), d_first = upload(k.first);
+                DevArray<double> d_step(size_t(c->max_batch > 0 ? c->max_batch : 1) * sizeof(double));
+                K.d_pair = std::move(d_pair); K.d_first = std::move(d_first); K.d_step = std::move(d_step);
+                K.arg = MgpuCfo{};
+                K.arg.pair = K.d_pair; K.arg.first = K.d_first; K.arg.Dy = t.xp.Dy;
+                // the context's own square window as the rectangular form takes it
+                K.own = MgpuLsRect{};
+                K.own.weight = c->dev.ls_weight;
+                K.own.hw_f = K.own.hw_t = t.lsw / 2;
+                K.own.lattice = c->dev.regular_lattice;
+            }
+            // the new kernels' LDS limits: the plain carve for the one, the channel-aware demapper's for the other (where that fits at all:
+            // mgpu_set_demapper refuses a geometry for which it does not)
+            const size_t csi_lds = mgpu_frontend_csi_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads);
+            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_fe)));
+            if (csi_lds <= size_t(160) * 1024)
+                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_csi_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(csi_lds)));
+            HIPCK(hipMemset(K.d_step.p, 0, size_t(c->max_batch > 0 ? c->max_batch : 1) * sizeof(double)));
+        }
+        K.mode = cfo;
+    });
+}
+
+int mgpu_get_cfo(mgpu_ctx* c, int* cfo) {
+    if (!c || !cfo) return MGPU_ERR_ARG;
+    *cfo = c->cfo.mode;
+    return MGPU_OK;
+}
+
+int mgpu_get_cfo_steps(mgpu_ctx* c, int F, double* step) {
+    if (!c || !step || F < 0) return MGPU_ERR_ARG;
+    return guard(c, [&] {
+        need(F <= c->max_batch, "bad argument (F must be <= max_batch)");
+        need(bool(c->cfo.d_step.p), "no span has run with MGPU_CFO_PILOTS on this context");
+        HIPCK(hipStreamSynchronize(c->stream));
+        if (F) HIPCK(hipMemcpy(step, c->cfo.d_step.p, size_t(F) * sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+// What the twin needs of a mode's tables, kept for the last geometry asked for (a sweep over frames builds the tables once).
+namespace {
+struct CfoGeometry {
+    int cfg = -1;
+    mgpu::ExplicitParams xp;
+    bool ofdm = false;
+    int Ns = 0, Nc = 0, Dy = 0;
+    CfoChains chains;
+};
+std::mutex cfo_mutex;
+std::shared_ptr<const CfoGeometry> cfo_last;
+
+std::shared_ptr<const CfoGeometry> cfo_geometry(int cfg, const mgpu::ExplicitParams& xp) {
+    std::lock_guard<std::mutex> lock(cfo_mutex);
+    const auto same = [&](const CfoGeometry& g) {
+        return g.cfg == cfg && g.xp.pilot_boost == xp.pilot_boost && g.xp.ls_window == xp.ls_window && g.xp.pilot_seed == xp.pilot_seed &&
+               g.xp.scrambler_seed == xp.scrambler_seed && g.xp.preamble_seed == xp.preamble_seed && g.xp.Nsymb == xp.Nsymb && g.xp.Dy == xp.Dy;
+    };
+    if (cfo_last && same(*cfo_last)) return cfo_last;
+    const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
+    auto g = std::make_shared<CfoGeometry>();
+    g->cfg = cfg; g->xp = xp;
+    g->ofdm = t.mfsk_M == 0;
+    g->Ns = t.Nsymb; g->Nc = t.Nc; g->Dy = t.xp.Dy;
+    if (g->ofdm) g->chains = cfo_chains(t);
+    cfo_last = g;
+    return g;
+}
+}  // namespace
+
+int mgpu_host_cfo_pilots(int cfg, const mgpu_explicit_params* p, const double* grid_in, double* grid_out, double* step_out) {
+    if (!grid_in || !grid_out) return MGPU_ERR_ARG;
+    mgpu::ExplicitParams xp;
+    std::string err;
+    int rc = MGPU_OK;
+    if (!explicit_params_from(p, xp, err, &rc)) return rc;
+    try {
+        const std::shared_ptr<const CfoGeometry> geometry = cfo_geometry(cfg, xp);
+        const CfoGeometry& g = *geometry;
+        if (!g.ofdm) return MGPU_ERR_UNSUPPORTED;
+        mgpu_internal_cfo_rule(grid_in, grid_out, g.Ns, g.Nc, g.Dy, g.chains.sign.data(), g.chains.pair.data(), g.chains.first.data(), step_out);
+        return MGPU_OK;
+    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+}
+
+}  // extern "C"

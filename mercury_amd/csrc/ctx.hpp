@@ -18,6 +18,7 @@
 #include "../../include/mercury_estimator.h"
 #include "../../include/mercury_diversity.h"
 #include "../../include/mercury_demapper.h"
+#include "../../include/mercury_cfo.h"
 #include "device_tables.h"
 #include "ls_rect.h"
 #include "tables.hpp"
@@ -38,6 +39,10 @@ extern "C" __global__ void mgpu_frontend_rect_kernel(MgpuDev, const double*, int
 extern "C" __global__ void mgpu_frontend_rect_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
 extern "C" __global__ void mgpu_frontend_csi_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
 extern "C" __global__ void mgpu_frontend_csi_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
+extern "C" __global__ void mgpu_frontend_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
+extern "C" __global__ void mgpu_frontend_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
+extern "C" __global__ void mgpu_frontend_csi_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
+extern "C" __global__ void mgpu_frontend_csi_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
 extern "C" __global__ void mgpu_ladder_select_kernel(const MgpuStatsDev*, int, int, int*, int*, int*, unsigned long long*);
 extern "C" __global__ void mgpu_ladder_merge_kernel(const int*, int, int, int, int, const float*, const float*, const float*, const double*, const uint8_t*,
                                                     const MgpuStatsDev*, float*, float*, float*, double*, uint8_t*, MgpuStatsDev*, int*, unsigned long long*);
@@ -189,6 +194,16 @@ struct Demapper {
     DevArray<uint16_t> d_sym_data;                  // arg.sym_data; made with the first MGPU_DEMAP_CSI
 };
 
+// The context's residual carrier-offset correction (include/mercury_cfo.h; cfo.hip). MGPU_CFO_PILOTS: every front-end launch of the fused span
+// is a CFO form (with or without the channel-aware demapper).
+struct Cfo {
+    int mode = MGPU_CFO_OFF;
+    MgpuLsRect own{};                               // the context's own square window as the (rectangular) CFO forms take it
+    MgpuCfo arg{};                                  // pair, first, Dy; step / step_rows are set per launch
+    DevArray<uint16_t> d_pair, d_first;             // made with the first MGPU_CFO_PILOTS
+    DevArray<double> d_step;                        // [max_batch] radians per symbol, by the frame's row in the context's workspaces
+};
+
 // The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
 struct SpanIo {
     const double* bb = nullptr;         // input frames
@@ -254,6 +269,7 @@ struct mgpu_ctx {
     Ladder lad;
     Diversity div;
     Demapper dmp;
+    Cfo cfo;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     // the blocking host-buffer entry points' chunk pipeline (rx_batch.hip rx_batch_pipelined)
@@ -303,6 +319,10 @@ using FrontendRectKernel = void (*)(MgpuDev, const double*, int, float*, float*,
 inline FrontendRectKernel fe_rect_kernel(int threads) { return threads == 1024 ? mgpu_frontend_rect_kernel_t1024 : mgpu_frontend_rect_kernel; }
 using FrontendCsiKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
 inline FrontendCsiKernel fe_csi_kernel(int threads) { return threads == 1024 ? mgpu_frontend_csi_kernel_t1024 : mgpu_frontend_csi_kernel; }
+using FrontendCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
+inline FrontendCfoKernel fe_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_cfo_kernel_t1024 : mgpu_frontend_cfo_kernel; }
+using FrontendCsiCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
+inline FrontendCsiCfoKernel fe_csi_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_csi_cfo_kernel_t1024 : mgpu_frontend_csi_cfo_kernel; }
 
 // whether the caller wants a tap with a row per frame (a launch's kernel writes them from row 0: one launch per call then)
 inline bool wants_frame_taps(const MgpuTapsDev& t) { return t.grid || t.H || t.eq || t.syms || t.llr_demod || t.variance || t.agc_gain; }
@@ -326,7 +346,7 @@ void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int
                     const float* d_var, const float* d_snrvar, hipStream_t s);
 // The same launches without the timing events, as the ladder's retries run them: the kernel timings describe rung 0.
 // rect: null = rung 0 (the ladder's first window where it is not the context's own, else the default kernel); a retry's window otherwise,
-// (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included)
+// (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included; with MGPU_CFO_PILOTS all of them are a CFO kernel)
 // whose `frames` list names the frame each row of the compact outputs in io belongs to.
 void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s);
 void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,

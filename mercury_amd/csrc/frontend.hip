@@ -39,6 +39,14 @@ __device__ __attribute__((noinline)) c2 unit_phasor(c2 h) {
     return {1 * c, 1 * s};
 }
 
+// The two evaluations of the residual carrier-offset stage (CFO below), out of line for the same reason.
+__device__ __attribute__((noinline)) double cfo_angle(c2 r) { return get_angle(r); }
+__device__ __attribute__((noinline)) c2 cfo_phasor(double x) {
+    double s, c;
+    gl_sincos(x, &s, &c);
+    return {c, s};
+}
+
 }  // namespace
 
 // device probe of glibc_trig.h for tests: atan, sin and cos of n arguments
@@ -124,10 +132,14 @@ extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(16
 // CSI: the channel-aware demapper (include/mercury_demapper.h). Every cell is equalised with the full estimate h (no
 // restore_channel_amplitude), the LLRs are (|h|^2 / sigma2) (d1 - d0) with sigma2 = mean |g - h x|^2 over the pilots, and the H and eq taps
 // show that h and g / h. variance, SNR variance and mean_H are still the plain form's, term for term.
-template <int FE_THREADS, bool RECT, bool CSI>
+// CFO: pilot-aided residual carrier-offset correction (include/mercury_cfo.h) between the AGC and the estimate: the phase
+// of the summed lag-Dy products of same-carrier pilots, divided by Dy, is the turn per symbol; symbol s is turned back by s times that.
+// Its scratch (50 carrier sums, one phasor per symbol: at most (64 + 255) * 16 B) is the head of the work area, where the FFTs are done
+// and the estimate has not begun (>= four FFT work areas, 16 KB): no carve changes.
+template <int FE_THREADS, bool RECT, bool CSI, bool CFO>
 __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
                                          float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out,
-                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi) {
+                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi, const MgpuCfo& cfo) {
     constexpr int FE_WAVES = FE_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int G = T.G, Nc = 50, Ns = T.Nsymb;
@@ -201,9 +213,48 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         __syncthreads();
         if (taps.agc_gain && tid == 0) taps.agc_gain[f] = agc;
     }
+    if constexpr (CFO) {
+        c2* acc = Hp;                                               // [Nc] a_c
+        c2* rot = Hp + 64;                                          // [Ns] {cos, sin} of -step * s
+        if (tid < Nc) {                                             // one lane per carrier adds its chain (at most 15 pairs), in symbol order
+            double ar = 0, ai = 0;
+            for (int q = cfo.first[tid]; q < cfo.first[tid + 1]; ++q) {
+                const int q0 = cfo.pair[2 * q], q1 = cfo.pair[2 * q + 1];
+                c2 z0 = grid[q0], z1 = grid[q1];
+                if (type[q0] < 0) z0 = {-z0.re, -z0.im};
+                if (type[q1] < 0) z1 = {-z1.re, -z1.im};
+                ar += z1.re * z0.re + z1.im * z0.im;
+                ai += z1.im * z0.re - z1.re * z0.im;
+            }
+            acc[tid] = {ar, ai};
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double rr = 0, ri = 0;
+            for (int c = 0; c < Nc; ++c) { const c2 a = acc[c]; rr += a.re; ri += a.im; }
+            const bool ok = fabs(rr) < __builtin_inf() && fabs(ri) < __builtin_inf() && !(rr == 0 && ri == 0);
+            const double step = ok ? cfo_angle(c2{rr, ri}) / double(cfo.Dy) : 0.0;
+            scal[5] = step;
+            scal[6] = ok ? 1.0 : 0.0;
+            bool first_pass = true;                                 // a retry computes the same step and does not write it out
+            if constexpr (RECT) first_pass = win.frames == nullptr;
+            if (first_pass && cfo.step && f < cfo.step_rows) cfo.step[f] = step;
+        }
+        __syncthreads();
+        if (scal[6] != 0) {                                         // (the whole workgroup takes the same side)
+            const double step = scal[5];
+            if (tid < Ns) rot[tid] = cfo_phasor(-step * double(tid));
+            __syncthreads();
+            for (int c = tid; c < G; c += FE_THREADS) {
+                const c2 g = grid[c], r = rot[c / Nc];
+                grid[c] = {g.re * r.re - g.im * r.im, g.re * r.im + g.im * r.re};
+            }
+            __syncthreads();
+        }
+    }
     if (taps.grid) for (int c = tid; c < G; c += FE_THREADS) { taps.grid[(size_t(f) * G + c) * 2] = grid[c].re; taps.grid[(size_t(f) * G + c) * 2 + 1] = grid[c].im; }
 
-    FE_STAMP();   // 2: AGC done
+    FE_STAMP();   // 2: AGC done (in the CFO forms: AGC and the carrier-offset stage)
     // ---- channel estimate at the pilots -------------------------------------------------------
     const int hwt = RECT ? win.hw_t : T.lsw / 2, hwf = RECT ? win.hw_f : T.lsw / 2;      // half-widths in time (rows) and frequency (columns)
     const int lattice = RECT ? win.lattice : T.regular_lattice;
@@ -490,13 +541,13 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<512, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{});
+    fe_frame<512, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<1024, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{});
+    fe_frame<1024, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{});
 }
 
 // The same body with a rectangular LS window and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when
@@ -504,13 +555,13 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_rect_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<512, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{});
+    fe_frame<512, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<1024, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{});
+    fe_frame<1024, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{});
 }
 
 // The rectangular form with the channel-aware demapper (include/mercury_demapper.h): the plain span (the context's own window passed as a
@@ -518,11 +569,40 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<512, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi);
+    fe_frame<512, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<1024, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi);
+    fe_frame<1024, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{});
+}
+
+// The rectangular form with the residual carrier-offset stage (include/mercury_cfo.h), without and with the channel-aware demapper: the
+// plain span (the context's own window passed as a rectangle), rung 0 and every retry of an estimator ladder while the context's
+// correction is MGPU_CFO_PILOTS.
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_cfo_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
+    fe_frame<512, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_cfo_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
+    fe_frame<1024, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_cfo_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
+    MgpuCfo cfo) {
+    fe_frame<512, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_cfo_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
+    MgpuCfo cfo) {
+    fe_frame<1024, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo);
 }

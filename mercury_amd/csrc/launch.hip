@@ -38,6 +38,8 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
     if (!rect && c->lad.n > 0 && !c->lad.rung0_is_default) rect = &c->lad.win[0];      // rung 0 of an estimator ladder with a window of its own
     const bool csi = c->dmp.mode == MGPU_DEMAP_CSI;                                    // the channel-aware demapper: one kernel for every window
     if (csi && !rect) rect = &c->dmp.own;
+    const bool cfo = c->cfo.mode == MGPU_CFO_PILOTS;                                   // residual carrier-offset correction: again one kernel for every window
+    if (cfo && !rect) rect = &c->cfo.own;
     for_frame_chunks(F, [&](int off, int n) {
         begin_chunk(off);
         const double* bb = io.bb + size_t(off) * stride * 2;
@@ -46,7 +48,16 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
             MgpuLsRect w = *rect;
             const bool retry = w.frames != nullptr;
             if (w.frames) { w.frames += off; bb = io.bb; }       // a retry: workgroup b reads frame frames[b] and writes row b
-            if (csi)
+            double* eqd = retry ? static_cast<double*>(nullptr) : at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2);
+            MgpuCfo co = c->cfo.arg;                             // the steps go to the frames' rows in the context's array, as far as it reaches
+            const size_t row = size_t(io.frame0) + size_t(off);
+            co.step_rows = cfo && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
+            co.step = co.step_rows > 0 ? c->cfo.d_step + row : nullptr;
+            if (cfo && csi)
+                hipLaunchKernelGGL(fe_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co);
+            else if (cfo)
+                hipLaunchKernelGGL(fe_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co);
+            else if (csi)
                 hipLaunchKernelGGL(fe_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar,
                                    retry ? static_cast<double*>(nullptr) : at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2), tp, w, c->dmp.arg);
             else

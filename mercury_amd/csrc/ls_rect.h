@@ -15,3 +15,13 @@ struct MgpuLsRect {
 struct MgpuCsi {
     const uint16_t* sym_data;   // [nData] de-framed position of the cell MgpuDev::sym_src[k] names: where that cell's |h|^2 is kept
 };
+
+// What the pilot-aided residual carrier-offset stage (frontend.hip CFO; include/mercury_cfo.h) needs beyond MgpuDev, again an argument of
+// its own; made at mgpu_set_cfo (cfo.hip).
+struct MgpuCfo {
+    const uint16_t* pair;   // [pairs][2] earlier and later cell of every same-carrier pilot pair Dy symbols apart: carrier after carrier, ascending symbols
+    const uint16_t* first;  // [Nc + 1] a carrier's first pair; first[Nc] = pairs
+    double* step;           // row of the launch's first frame in the context's step array, or null
+    int step_rows;          // rows of `step` that may be written
+    int Dy;
+};

@@ -208,6 +208,40 @@ def host_demap_csi(cfg, grid, H, explicit=None):
     return llr, float(sigma2.value)
 
 
+# ---- pilot-aided residual carrier-offset correction (include/mercury_cfo.h) ----------------------------------------
+CFO_SYMBOLS = ["mgpu_set_cfo", "mgpu_get_cfo", "mgpu_get_cfo_steps", "mgpu_host_cfo_pilots"]
+CFO_MODES = {"off": 0, "pilots": 1}
+_CFO_CELLS = {}
+
+
+def host_cfo_pilots(cfg, grid, explicit=None):
+    """mgpu_host_cfo_pilots, no GPU: one frame's cell grid (complex128 [Nsymb * Nc], after the AGC) -> (the grid with symbol s turned back
+    by s steps: complex128 [Nsymb * Nc], the step in radians per symbol). explicit: as RxPhy's."""
+    lib = load_library()
+    lib.mgpu_host_cfo_pilots.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    g = np.ascontiguousarray(grid, np.complex128).ravel()
+    xp = _explicit_struct(explicit)
+    ref = C.byref(xp) if xp is not None else None
+    # the cells of the (possibly explicit) geometry: the entries a call on an all-zero grid writes (at most 255 symbols of 50 carriers);
+    # asked once per geometry
+    key = (int(cfg), tuple(sorted((explicit or {}).items())))
+    if key not in _CFO_CELLS:
+        count = np.full(255 * 50, np.nan + 0j, np.complex128)
+        rc = lib.mgpu_host_cfo_pilots(int(cfg), ref, _ptr(np.zeros_like(count)), _ptr(count), None)
+        if rc != 0:
+            raise MgpuError("mgpu_host_cfo_pilots failed (%d)" % rc, rc)
+        _CFO_CELLS[key] = int(np.count_nonzero(~np.isnan(count.real)))
+    cells = _CFO_CELLS[key]
+    if g.size != cells:
+        raise MgpuError("host_cfo_pilots: the grid must have one entry per cell (%d)" % cells)
+    out = np.zeros_like(g)
+    step = C.c_double()
+    rc = lib.mgpu_host_cfo_pilots(int(cfg), ref, _ptr(g), _ptr(out), C.byref(step))
+    if rc != 0:
+        raise MgpuError("mgpu_host_cfo_pilots failed (%d)" % rc, rc)
+    return out, float(step.value)
+
+
 # ---- diversity combining (include/mercury_diversity.h, DESIGN.md §3.8) ------------------------------------------------------------
 DIVERSITY_SYMBOLS = ["mgpu_rx_batch_div_dev", "mgpu_rx_batch_div", "mgpu_llr_combine_dev", "mgpu_host_llr_combine", "mgpu_baseband_test_esn0_div"]
 DIVERSITY_MAX = 8
@@ -487,6 +521,29 @@ class RxPhy:
         self.lib.mgpu_get_demapper.argtypes = [C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_demapper(self.h, C.byref(v)))
         return {n: k for k, n in DEMAPPERS.items()}[v.value]
+
+    # ---- pilot-aided residual carrier-offset correction (include/mercury_cfo.h) -----------------
+    def set_cfo(self, name):
+        """"off": the reference's front-end (the default). "pilots": every frame's grid is turned back by the per-symbol phase step its
+        own pilots measure, between the AGC and the channel estimate, in every receive entry point of this context."""
+        if name not in CFO_MODES:
+            raise MgpuError("cfo must be one of %s" % sorted(CFO_MODES))
+        self.lib.mgpu_set_cfo.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.lib.mgpu_set_cfo(self.h, CFO_MODES[name]))
+
+    @property
+    def cfo(self):
+        v = C.c_int()
+        self.lib.mgpu_get_cfo.argtypes = [C.c_void_p, C.c_void_p]
+        self._ck(self.lib.mgpu_get_cfo(self.h, C.byref(v)))
+        return {n: k for k, n in CFO_MODES.items()}[v.value]
+
+    def cfo_steps(self, F):
+        """the steps (radians per symbol; Hz = step * 12000 / (2 pi Nofdm)) of rows 0 .. F-1 of the last span that ran with the mode on"""
+        out = np.zeros(int(F), np.float64)
+        self.lib.mgpu_get_cfo_steps.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._ck(self.lib.mgpu_get_cfo_steps(self.h, int(F), _ptr(out)))
+        return out
 
     # ---- host-buffer entry points -------------------------------------------------------------
     def receive(self, baseband, taps=False, want_llr=False):

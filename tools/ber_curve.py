@@ -15,7 +15,8 @@ line then carries the frames each rung decoded.
 and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_per_point counts payloads, Es/N0 is per branch.
 --points LO:HI:STEP (baseband form): the Es/N0 points instead of the reference's 25.
 --demapper csi (any form, with any of the above): LLRs weighted by |H|^2 per cell (include/mercury_demapper.h) instead of the reference's
-demapper."""
+demapper.
+--cfo pilots (any form, with any of the above): every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)."""
 import json
 import os
 import sys
@@ -34,6 +35,7 @@ AWGN_FER01 = {0: -10.0, 1: -7.5, 2: -6.0, 3: -4.5, 4: -3.5, 5: -2.5, 6: -1.5, 7:
 
 LADDER = []          # --ladder
 DEMAPPER = ["maxlog"]   # --demapper
+CFO = ["off"]           # --cfo
 
 
 def _ladder_fields(rx):
@@ -48,6 +50,7 @@ def threshold(cfg, n, channel):
     rx = RxPhy(cfg, max_batch=min(n, 1024))
     rx.set_estimator_ladder(LADDER)
     rx.set_demapper(DEMAPPER[0])
+    rx.set_cfo(CFO[0])
     pts = AWGN_FER01.get(cfg, -20.0) - 3.0 + np.arange(44, dtype=np.float64)
     t0 = time.perf_counter()
     res = rx.passband_test_esn0(pts, n, 1500.0, seed=2024, output_power_watt=1.0, hf_channel=channel)
@@ -56,7 +59,7 @@ def threshold(cfg, n, channel):
     fer = [r["FER"] for r in res]
     first = next((float(pts[i]) for i in range(len(pts) - 2) if max(fer[i: i + 3]) < 0.1), None)
     print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "frames_per_point": n, "fer01_esn0_db": first,
-                      "awgn_reference_db": AWGN_FER01.get(cfg), "demapper": DEMAPPER[0], "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
+                      "awgn_reference_db": AWGN_FER01.get(cfg), "demapper": DEMAPPER[0], "cfo": CFO[0], "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
                       "seconds": round(time.perf_counter() - t0, 2), **extra}), flush=True)
 
 
@@ -68,6 +71,7 @@ def passband(argv, channel):
     rx = RxPhy(cfg, max_batch=min(n, 1024))
     rx.set_estimator_ladder(LADDER)
     rx.set_demapper(DEMAPPER[0])
+    rx.set_cfo(CFO[0])
     pts = np.arange(31) * 1.0 - 25.0 if cfg >= 100 else np.arange(25) * 0.5 - 10.0
     rx.passband_test_esn0(pts[-1:], min(n, 1024), 1500.0, output_power_watt=1.0, hf_channel=channel)
     t0 = time.perf_counter()
@@ -76,7 +80,7 @@ def passband(argv, channel):
     for r in res:
         print("%.1f;%.3e;%.3e;%d" % (r["esn0_db"], r["BER"], r["FER"], r["crc_ok_frames"]))
     print(json.dumps({"cfg": cfg, "mode": "passband", "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
-                      "frames_per_s": len(res) * n / dt, "demapper": DEMAPPER[0], **_ladder_fields(rx)}), file=sys.stderr)
+                      "frames_per_s": len(res) * n / dt, "demapper": DEMAPPER[0], "cfo": CFO[0], **_ladder_fields(rx)}), file=sys.stderr)
 
 
 def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, seed=2024, warm=True):
@@ -85,6 +89,7 @@ def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, see
     rx = RxPhy(cfg, max_batch=min(n * per, 65536), agc=0, variance_source=0, decoder=dec)          # the variant baseband_test_EsN0 runs
     rx.set_estimator_ladder(LADDER)
     rx.set_demapper(DEMAPPER[0])
+    rx.set_cfo(CFO[0])
     if pts is None:
         pts = np.arange(-12.0, 13.0, 1.0)[:25] + (0.0 if cfg >= 7 else -6.0)
     if warm:
@@ -96,7 +101,7 @@ def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, see
     extra = {"diversity": diversity, "ladder": ["%dx%d" % r for r in rx.estimator_ladder]} if diversity else _ladder_fields(rx)
     rx.close()
     return res, {"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
-                 "frames_per_s": len(res) * n * per / dt, "demapper": DEMAPPER[0], **extra}
+                 "frames_per_s": len(res) * n * per / dt, "demapper": DEMAPPER[0], "cfo": CFO[0], **extra}
 
 
 def _option(argv, name):
@@ -117,6 +122,9 @@ def main():
     DEMAPPER[0] = _option(argv, "--demapper") or "maxlog"
     if DEMAPPER[0] not in pl.DEMAPPERS:
         sys.exit("--demapper: one of " + ", ".join(pl.DEMAPPERS))
+    CFO[0] = _option(argv, "--cfo") or "off"
+    if CFO[0] not in pl.CFO_MODES:
+        sys.exit("--cfo: one of " + ", ".join(pl.CFO_MODES))
     for i, a in enumerate(argv):
         if a == "--channel" or a.startswith("--channel="):
             channel = a.split("=", 1)[1] if "=" in a else argv[i + 1]

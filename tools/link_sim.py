@@ -165,6 +165,7 @@ def main():
     ap.add_argument("--power", type=float, default=1.0, help="output_power_watt (1: Es/N0 is the signal's own, BER_PLOT_passband's convention)")
     ap.add_argument("--ladder", default="", help="estimator ladder, e.g. 21x21,5x21 (carriers x symbols; include/mercury_estimator.h)")
     ap.add_argument("--demapper", default="maxlog", choices=["maxlog", "csi"], help="csi: LLRs weighted by |H|^2 per cell (include/mercury_demapper.h)")
+    ap.add_argument("--cfo", default="off", choices=["off", "pilots"], help="pilots: every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--compare", action="store_true", help="simulator and baseline alternating, --repeats times each")
@@ -180,6 +181,7 @@ def main():
     pts, esn0 = ladder(a.esn0, a.links)
     rx = RxPhy(a.cfg, max_iters=a.max_iters, max_batch=a.max_batch or a.links)
     rx.set_demapper(a.demapper)
+    rx.set_cfo(a.cfo)
     if a.stream_bench:
         stream_bench(rx, a, info)
         rx.close()
@@ -203,7 +205,7 @@ def main():
                                       "delivered_share": d / max(1, int(c["frames_sent"][m].sum()))}))
             rates[which].append(sim_seconds / wall)
     out = {"cfg": a.cfg, "links": a.links, "channel": a.channel, "gap_hops": a.gap_hops, "simulated_seconds_per_link": hops * p["symbol_period"] / FS,
-           "max_iters": a.max_iters, "ladder": a.ladder, "demapper": a.demapper}
+           "max_iters": a.max_iters, "ladder": a.ladder, "demapper": a.demapper, "cfo": a.cfo}
     if a.ladder:
         by, frames = rx.ladder_counters()
         out["decoded_by_rung"], out["ladder_frames"] = [int(v) for v in by], frames
