@@ -27,6 +27,26 @@
  * telecom_system.cc:2802-2809 does. The width is bounded by the front-end, which reads at most 7 pilots of a window row. Anything else is
  * refused with MGPU_ERR_ARG and the context is left as it was. Only OFDM modes with the LS estimator take a ladder: the zero-forcing
  * modes (15, 16, explicit ZF) and the MFSK modes return MGPU_ERR_UNSUPPORTED.
+ *
+ * A rung may also be the separable Wiener estimator (MGPU_RUNG_WIENER, set through mgpu_set_estimator_ladder_ex). A flat
+ * window is a poor low-pass in the delay domain; this rung filters the sign-applied pilots with taps designed for a delay interval and
+ * a Doppler bound instead: along time per carrier (every carrier that has pilots has one every Dy symbols), then along frequency per
+ * symbol (one every Dy carriers). Everything behind the estimate at the pilots - column interpolation, amplitude restoration, equaliser,
+ * both variances, mean_H, either demapper, the taps - is unchanged. A one-rung ladder means "this estimator alone". Every ladder rule
+ * above holds for such a rung as written. This is NOT one of the reference's configurations: the reference has no such estimator.
+ *
+ * The rule (mgpu_host_wiener_estimate is normative; the kernel forms the same terms in the same order):
+ *   design: tau0, tau1 = the delay bounds in baseband samples (us * 12000 / 1e6), Ts = 272 / 12000 s, s2 = 10^(-snr_db / 10) / boost^2,
+ *           k(c) = carrier c's FFT bin relative to the empty DC bin: c - 25 below carrier 25, else c - 24; sinc(x) = sin(pi x) / (pi x).
+ *   time:   for each distinct set of pilot rows a carrier has, Rt[a][b] = sinc(2 doppler Ts (row_a - row_b)), A = Rt (Rt + s2 I)^-1 (real).
+ *   unit gain: row i of A is divided by sum_k A[i][k] Rt[k][i]; row i of B by Re sum_k B[i][k] Rf[k][i].
+ *   frequency: s2b = s2 times the mean, over the frame's pilots, of the sum of squares of the pilot's row of A at unit gain; for each
+ *           distinct set of pilot carriers a symbol has, d = k(c_a) - k(c_b), Rf[a][b] = sinc((tau1 - tau0) d / 256) exp(-j 2 pi d (tau0 + tau1) / 512),
+ *           B = Rf (Rf + s2b I)^-1 (complex). Last, every A is multiplied by 1 / boost.
+ *   per frame, on the grid after the AGC (and the carrier-offset stage where that is on), yp = the pilots times their sign:
+ *           t[p] = sum_k A[row of p][k] yp[k-th pilot of p's carrier], ascending symbols, real and imaginary sums separate from +0.0;
+ *           H[p] = sum_m B[row of p][m] t[m-th pilot of p's symbol], ascending carriers, hr += (b.re t.re - b.im t.im),
+ *           hi += (b.re t.im + b.im t.re); every product and the difference rounded on its own. Non-finite inputs give what IEEE gives.
  */
 #ifndef MERCURY_ESTIMATOR_H
 #define MERCURY_ESTIMATOR_H
@@ -40,10 +60,24 @@ extern "C" {
 typedef struct mgpu_ls_window { int width, height; } mgpu_ls_window;   /* cells: frequency x time */
 #define MGPU_LADDER_MAX 4
 
+#define MGPU_RUNG_LS 0          /* the LS mean over `window` */
+#define MGPU_RUNG_WIENER 1      /* the separable Wiener estimator designed by `design`; `window` is not used */
+/* The channel a Wiener rung is designed for: delays within [tau_min_us, tau_max_us] of the frame timing, Doppler within +-doppler_hz,
+ * pilots received at snr_db. The defaults (MGPU_WIENER_DESIGN_DEFAULT) cover -4 .. 28 baseband samples. tau_max_us <= tau_min_us,
+ * doppler_hz < 0, snr_db outside [-20, 40] or a non-finite field is refused with MGPU_ERR_ARG. */
+typedef struct mgpu_wiener_design { double tau_min_us, tau_max_us, doppler_hz, snr_db; } mgpu_wiener_design;
+#define MGPU_WIENER_DESIGN_DEFAULT { -333.33, 2333.33, 0.5, 0.0 }
+typedef struct mgpu_estimator_rung { int kind; mgpu_ls_window window; mgpu_wiener_design design; } mgpu_estimator_rung;
+
 /* n_rungs 0 (rungs may be NULL): no ladder. Waits for the context's stream; work queued on a caller's stream must have finished. */
 int mgpu_set_estimator_ladder(mgpu_ctx* ctx, const mgpu_ls_window* rungs, int n_rungs);
-/* the rungs as they are applied (odd); rungs: room for MGPU_LADDER_MAX */
+/* the rungs as they are applied (odd); rungs: room for MGPU_LADDER_MAX. A Wiener rung is reported as {0, 0}. */
 int mgpu_get_estimator_ladder(mgpu_ctx* ctx, mgpu_ls_window* rungs, int* n_rungs);
+/* The same with a kind per rung; mgpu_set_estimator_ladder is its all-LS case. rung_size: sizeof(mgpu_estimator_rung) as the caller was
+ * compiled; anything else is refused with MGPU_ERR_ARG, like a kind that is neither of the two or a design out of range. A refusal leaves
+ * the context as it was. The getter reports LS rungs with a zero design and Wiener rungs with a {0, 0} window. */
+int mgpu_set_estimator_ladder_ex(mgpu_ctx* ctx, const mgpu_estimator_rung* rungs, int n_rungs, size_t rung_size);
+int mgpu_get_estimator_ladder_ex(mgpu_ctx* ctx, mgpu_estimator_rung* rungs /*[MGPU_LADDER_MAX]*/, int* n_rungs, size_t rung_size);
 /* of the last fused-span call (for mgpu_receive_byte_batch: the last trial's decode, in the order of the windows it decoded): the winning
  * rung of each of its F frames, -1 where no rung decoded. Waits for the context's stream. MGPU_ERR_ARG without a ladder or when F exceeds
  * that call's frames. */
@@ -55,6 +89,16 @@ int mgpu_estimator_ladder_counters(mgpu_ctx* ctx, long long decoded_by_rung[MGPU
  * width x height window. Same terms in the same order as the kernel. */
 int mgpu_host_ls_estimate(int cfg, const mgpu_explicit_params* p_or_null, int width, int height, const double* grid_c128 /*[Nsymb*Nc]*/,
                           double* H_pilots_c128 /*[nPilots]*/);
+/* Host twin of the Wiener estimate, no GPU, and the normative statement of the rule above: the estimate at the nPilots pilot cells of one
+ * frame grid for the mode `cfg` and a design (d_or_null: the defaults). */
+int mgpu_host_wiener_estimate(int cfg, const mgpu_explicit_params* p_or_null, const mgpu_wiener_design* d_or_null,
+                              const double* grid_c128 /*[Nsymb*Nc]*/, double* H_pilots_c128 /*[nPilots]*/);
+/* The design's class matrices, for tests. which 0: the time classes (one per distinct set of pilot rows a carrier has, in the order the
+ * carriers meet them; real), 1: the frequency classes (per distinct set of pilot carriers a symbol has, in the order the symbols meet
+ * them; complex). Every output may be NULL: the number of classes; for class `cls` (MGPU_ERR_ARG when there is none and one of the
+ * following is asked for) its size n, its n rows / carriers, and its n x n row-major matrix (n*n doubles / n*n c128) as the kernel reads it. */
+int mgpu_host_wiener_tables(int cfg, const mgpu_explicit_params* p_or_null, const mgpu_wiener_design* d_or_null, int which, int cls,
+                            int* n_classes, int* n, int* members, double* matrix);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ extern "C" const unsigned long mgpu_ldpc_blob_size;
 
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads);
+extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi);
 extern "C" size_t mgpu_spa_lds_bytes(int E, int N);
 extern "C" size_t mgpu_gbf_lds_bytes(int N);
 extern "C" size_t mgpu_spa_fast_lds_bytes(int Sg, int N);
@@ -43,6 +44,14 @@ extern "C" __global__ void mgpu_frontend_cfo_kernel(MgpuDev, const double*, int,
 extern "C" __global__ void mgpu_frontend_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
 extern "C" __global__ void mgpu_frontend_csi_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
 extern "C" __global__ void mgpu_frontend_csi_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
+extern "C" __global__ void mgpu_frontend_wiener_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_csi_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_csi_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_csi_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_csi_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
 extern "C" __global__ void mgpu_ladder_select_kernel(const MgpuStatsDev*, int, int, int*, int*, int*, unsigned long long*);
 extern "C" __global__ void mgpu_ladder_merge_kernel(const int*, int, int, int, int, const float*, const float*, const float*, const double*, const uint8_t*,
                                                     const MgpuStatsDev*, float*, float*, float*, double*, uint8_t*, MgpuStatsDev*, int*, unsigned long long*);
@@ -161,6 +170,12 @@ struct Ladder {
     MgpuLsRect win[MGPU_LADDER_MAX]{};              // rung r as the rectangular front-end takes it (frames = NULL)
     DevArray<double> weight[MGPU_LADDER_MAX];       // win[r].weight
     bool rung0_is_default = false;                  // rung 0 is the context's own square window: the default kernel runs it
+    int kind[MGPU_LADDER_MAX]{};                    // MGPU_RUNG_LS / MGPU_RUNG_WIENER; a Wiener rung's `rung` is {0, 0} and its `win` carries no window
+    mgpu_wiener_design design[MGPU_LADDER_MAX]{};   // of the Wiener rungs
+    MgpuWiener wiener[MGPU_LADDER_MAX]{};           // a Wiener rung as its front-end takes it
+    DevArray<double> wiener_A[MGPU_LADDER_MAX], wiener_B[MGPU_LADDER_MAX];
+    DevArray<int> wiener_off[MGPU_LADDER_MAX];      // a_off, then b_off
+    DevArray<uint16_t> wiener_idx[MGPU_LADDER_MAX]; // pilot, then col_list
     DevArray<int> d_rung;                           // [max_batch] winning rung per frame of the last call, -1 = none
     DevArray<unsigned long long> d_counters;        // [MGPU_LADDER_MAX + 1] frames decoded by rung r; frames seen
     // a retry's compact workspaces, [max_batch] each, created with the first ladder of more than one rung
@@ -324,6 +339,16 @@ inline FrontendCfoKernel fe_cfo_kernel(int threads) { return threads == 1024 ? m
 using FrontendCsiCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
 inline FrontendCsiCfoKernel fe_csi_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_csi_cfo_kernel_t1024 : mgpu_frontend_csi_cfo_kernel; }
 
+// the Wiener forms (frontend.hip WIENER): plain, with the carrier-offset stage, with the channel-aware demapper, with both
+using FrontendWienerKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuWiener);
+inline FrontendWienerKernel fe_wiener_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_kernel_t1024 : mgpu_frontend_wiener_kernel; }
+using FrontendWienerCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo, MgpuWiener);
+inline FrontendWienerCfoKernel fe_wiener_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_cfo_kernel_t1024 : mgpu_frontend_wiener_cfo_kernel; }
+using FrontendWienerCsiKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
+inline FrontendWienerCsiKernel fe_wiener_csi_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_csi_kernel_t1024 : mgpu_frontend_wiener_csi_kernel; }
+using FrontendWienerCsiCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
+inline FrontendWienerCsiCfoKernel fe_wiener_csi_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_csi_cfo_kernel_t1024 : mgpu_frontend_wiener_csi_cfo_kernel; }
+
 // whether the caller wants a tap with a row per frame (a launch's kernel writes them from row 0: one launch per call then)
 inline bool wants_frame_taps(const MgpuTapsDev& t) { return t.grid || t.H || t.eq || t.syms || t.llr_demod || t.variance || t.agc_gain; }
 
@@ -347,8 +372,9 @@ void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int
 // The same launches without the timing events, as the ladder's retries run them: the kernel timings describe rung 0.
 // rect: null = rung 0 (the ladder's first window where it is not the context's own, else the default kernel); a retry's window otherwise,
 // (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included; with MGPU_CFO_PILOTS all of them are a CFO kernel)
-// whose `frames` list names the frame each row of the compact outputs in io belongs to.
-void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s);
+// whose `frames` list names the frame each row of the compact outputs in io belongs to. rung: the ladder's rung the launch is (0 without a
+// ladder): its kind, which the ladder keeps, picks the LS or the Wiener forms.
+void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s, int rung = 0);
 void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
                      const float* d_var, const float* d_snrvar, hipStream_t s);
 // The estimator ladder behind rung 0 (ladder.hip), called by launch_span alone: marks each frame's rung and, rung by rung, re-runs the

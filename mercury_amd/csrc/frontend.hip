@@ -124,6 +124,11 @@ __host__ __device__ inline FeCarve fe_carve_csi(int G, int nPilots, int nBits, i
     return fe_carve_with(G, nPilots, nBits, FE_WAVES, fe_csi_var_bytes(nPilots) + ((size_t(4) * (G - nPilots) + 15) & ~size_t(15)));
 }
 extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve_csi(G, nPilots, nBits, threads / 64).total; }
+// The Wiener forms (WIENER below; include/mercury_estimator.h MGPU_RUNG_WIENER) keep nothing of their own: the time pass writes Hp, the
+// frequency pass the signed pilots' area (16 nPilots bytes of rsz), so their carve is the rectangular form's, or the CSI form's with that demapper.
+extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi) {
+    return (csi ? fe_carve_csi(G, nPilots, nBits, threads / 64) : fe_carve(G, nPilots, nBits, threads / 64)).total;
+}
 // workgroups per compute unit the LDS lets a carve of `bytes` have, counted as fe_carve counts them (blocks of 1280 bytes, 256 of overhead)
 extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(160) * 1024 / ((bytes + 256 + 1279) / 1280 * 1280)); }
 
@@ -136,10 +141,12 @@ extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(16
 // of the summed lag-Dy products of same-carrier pilots, divided by Dy, is the turn per symbol; symbol s is turned back by s times that.
 // Its scratch (50 carrier sums, one phasor per symbol: at most (64 + 255) * 16 B) is the head of the work area, where the FFTs are done
 // and the estimate has not begun (>= four FFT work areas, 16 KB): no carve changes.
-template <int FE_THREADS, bool RECT, bool CSI, bool CFO>
+// WIENER: the estimate at the pilots is the separable Wiener filter's (include/mercury_estimator.h MGPU_RUNG_WIENER) instead
+// of the window mean; `win` only carries the frame list. Its two passes live in Hp and the signed pilots' area: no carve changes.
+template <int FE_THREADS, bool RECT, bool CSI, bool CFO, bool WIENER>
 __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
                                          float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out,
-                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi, const MgpuCfo& cfo) {
+                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi, const MgpuCfo& cfo, const MgpuWiener& wn) {
     constexpr int FE_WAVES = FE_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int G = T.G, Nc = 50, Ns = T.Nsymb;
@@ -256,116 +263,157 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 
     FE_STAMP();   // 2: AGC done (in the CFO forms: AGC and the carrier-offset stage)
     // ---- channel estimate at the pilots -------------------------------------------------------
-    const int hwt = RECT ? win.hw_t : T.lsw / 2, hwf = RECT ? win.hw_f : T.lsw / 2;      // half-widths in time (rows) and frequency (columns)
-    const int lattice = RECT ? win.lattice : T.regular_lattice;
-    const double* __restrict__ ls_weight = RECT ? win.weight : T.ls_weight;
-    const bool ls_fast = T.estimator != 0 && lattice;
-    int ls_rows = 0;     // 1: every window row holds >= 3 pilots and every pilot of the frame is finite -> the branch-free row loop below
-    if (ls_fast) {       // x*y for the LS sums: the pilot's sign applied once ((-w)*y == w*(-y) exactly), in pilot order
-        int finite = 1;
-        for (int p = tid; p < T.nPilots + 8; p += FE_THREADS) {
-            if (p >= T.nPilots) { yp[p] = {0.0, 0.0}; continue; }
+    if constexpr (WIENER) {
+        // The separable Wiener estimate: the signed pilots filtered along time per carrier (real taps, one matrix row per
+        // pilot), then along frequency per symbol (complex taps); one lane per pilot in both passes, the sums in ascending symbol and
+        // ascending carrier order as mgpu_host_wiener_estimate forms them. The second pass writes where the signed pilots were.
+        for (int p = tid; p < T.nPilots; p += FE_THREADS) {
             const int q = T.pilot_cell[p];
             const c2 y = grid[q];
             yp[p] = type[q] < 0 ? c2{-y.re, -y.im} : y;
-            finite &= (fabs(y.re) < __builtin_inf()) & (fabs(y.im) < __builtin_inf());
         }
-        ls_rows = __syncthreads_and(finite) && lattice == 2;
-    }
-    for (int p = tid; p < T.nPilots; p += FE_THREADS) {
-        const int c = T.pilot_cell[p], i = c / Nc, j = c - i * Nc;
-        if (T.estimator == 0) {            // ZF: Y / (x + 0i) reduces to two real divisions in __divdc3
-            const double x = type[c] < 0 ? -boost : boost;
-            Hp[p] = {grid[c].re / x, grid[c].im / x};
-        } else {                           // LS over the (clipped) window - 21x21 unless RECT -, row-major order
-            const int k0 = max(i - hwt, 0), k1 = min(i + hwt, Ns - 1), l0 = max(j - hwf, 0), l1 = min(j + hwf, Nc - 1);
+        __syncthreads();
+        const uint4* __restrict__ wpilot = reinterpret_cast<const uint4*>(wn.pilot);
+        for (int p = tid; p < T.nPilots; p += FE_THREADS) {
+            const uint4 q = wpilot[p];
+            const int n = int(q.y & 0xffffu);
+            const double* __restrict__ a = wn.A + wn.a_off[q.x & 0xffffu] + int(q.x >> 16) * n;
+            const uint16_t* __restrict__ list = wn.col_list + (q.y >> 16);
             double hr = 0, hi = 0;
-            if (ls_fast) {
-                // pilots of row k sit at columns == k (mod 3); rows hold 17,17,16 pilots cyclically, so the pilot
-                // index of (k, l) is 50*(k/3) + {0,17,34}[k%3] + (l - k%3)/3 and a row's window pilots are contiguous
-                // per column residue r = k % 3: first window column == r (mod 3), how many pilots, and the offset of
-                // that first pilot inside its row; computed once per pilot, then rows just cycle through r
-                int cntr[3], offr[3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const int first = l0 + ((r - l0) % 3 + 3) % 3;
-                    cntr[r] = first <= l1 ? (l1 - first) / 3 + 1 : 0;
-                    offr[r] = (r == 0 ? 0 : r == 1 ? 17 : 34) + (first - r) / 3;
-                }
-                int n = 0;
-                {
-                    int r = k0 % 3;
-                    for (int k = k0; k <= k1; ++k) { n += r == 0 ? cntr[0] : r == 1 ? cntr[1] : cntr[2]; r = r == 2 ? 0 : r + 1; }
-                }
-                const double w = ls_weight[n];
-                if (ls_rows) {
-                    // Rows k0, k0+1, k0+2, k0+3, ... cycle through the three column residues, so a lane's (pilot count, first pilot) pair of a
-                    // row depends only on the row's place in that cycle. A row's first three pilots are always inside the window; pilots
-                    // four to seven are added with the weight w or +0.0: x + (+-0 * y) == x exactly for finite y, and the sums start at +0.0
-                    // and can therefore never be -0.0. Same terms in the same order as the loop below, without its per-term branches.
-                    const int r0 = k0 % 3;
-                    int ptr[3];
-                    double wq[3][4];
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) {
-                        const int r = r0 + q >= 3 ? r0 + q - 3 : r0 + q;
-                        const int cn = r == 0 ? cntr[0] : r == 1 ? cntr[1] : cntr[2];
-                        ptr[q] = 50 * ((k0 + q) / 3) + (r == 0 ? offr[0] : r == 1 ? offr[1] : offr[2]);
-#pragma unroll
-                        for (int m = 0; m < 4; ++m) wq[q][m] = m + 3 < cn ? w : 0.0;
-                    }
-                    auto add_row = [&](int q) {
-                        const c2* row = yp + ptr[q];
-                        const c2 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3], v4 = row[4], v5 = row[5], v6 = row[6];
-                        hr += w * v0.re; hi += w * v0.im;
-                        hr += w * v1.re; hi += w * v1.im;
-                        hr += w * v2.re; hi += w * v2.im;
-                        hr += wq[q][0] * v3.re; hi += wq[q][0] * v3.im;
-                        hr += wq[q][1] * v4.re; hi += wq[q][1] * v4.im;
-                        hr += wq[q][2] * v5.re; hi += wq[q][2] * v5.im;
-                        hr += wq[q][3] * v6.re; hi += wq[q][3] * v6.im;
-                        ptr[q] += 50;
-                    };
-                    for (int k = k0; k <= k1; k += 3) {
-                        add_row(0);
-                        if (k + 1 <= k1) add_row(1);
-                        if (k + 2 <= k1) add_row(2);
-                    }
-                    Hp[p] = {hr, hi};
-                    continue;
-                }
-                int km = k0 % 3, rowbase = 50 * (k0 / 3);
-                for (int k = k0; k <= k1; ++k) {
-                    const int cnt = km == 0 ? cntr[0] : km == 1 ? cntr[1] : cntr[2];
-                    const c2* row = yp + rowbase + (km == 0 ? offr[0] : km == 1 ? offr[1] : offr[2]);
-                    if (km == 2) { km = 0; rowbase += 50; } else ++km;
-                    if (cnt == 0) continue;
-                    // a window row holds at most 7 pilots: fetch all seven at once (one LDS latency per row; reading past
-                    // the row's end stays inside the LDS carve), add the first cnt in order
-                    const c2 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3], v4 = row[4], v5 = row[5], v6 = row[6];
-                    hr += w * v0.re; hi += w * v0.im;
-                    if (cnt > 1) { hr += w * v1.re; hi += w * v1.im; }
-                    if (cnt > 2) { hr += w * v2.re; hi += w * v2.im; }
-                    if (cnt > 3) { hr += w * v3.re; hi += w * v3.im; }
-                    if (cnt > 4) { hr += w * v4.re; hi += w * v4.im; }
-                    if (cnt > 5) { hr += w * v5.re; hi += w * v5.im; }
-                    if (cnt > 6) { hr += w * v6.re; hi += w * v6.im; }
-                }
-            } else {
-                int n = 0;
-                for (int k = k0; k <= k1; ++k)
-                    for (int l = l0; l <= l1; ++l) n += type[k * Nc + l] != 0;
-                const double w = ls_weight[n];
-                for (int k = k0; k <= k1; ++k)
-                    for (int l = l0; l <= l1; ++l) {
-                        const int q = k * Nc + l;
-                        if (!type[q]) continue;
-                        const double xw = type[q] < 0 ? -w : w;
-                        hr += xw * grid[q].re;
-                        hi += xw * grid[q].im;
-                    }
+            for (int k = 0; k < n; ++k) {
+                const c2 v = yp[list[k]];
+                hr += a[k] * v.re; hi += a[k] * v.im;
             }
             Hp[p] = {hr, hi};
+        }
+        __syncthreads();
+        for (int p = tid; p < T.nPilots; p += FE_THREADS) {
+            const uint4 q = wpilot[p];
+            const int n = int(q.w & 0xffffu);
+            const c2* __restrict__ b = reinterpret_cast<const c2*>(wn.B) + wn.b_off[q.z & 0xffffu] + int(q.z >> 16) * n;
+            const c2* t = Hp + (q.w >> 16);
+            double hr = 0, hi = 0;
+            for (int m = 0; m < n; ++m) {
+                const c2 w = b[m], v = t[m];
+                hr += w.re * v.re - w.im * v.im;
+                hi += w.re * v.im + w.im * v.re;
+            }
+            yp[p] = {hr, hi};
+        }
+        __syncthreads();
+        for (int p = tid; p < T.nPilots; p += FE_THREADS) Hp[p] = yp[p];
+    } else {
+        const int hwt = RECT ? win.hw_t : T.lsw / 2, hwf = RECT ? win.hw_f : T.lsw / 2;      // half-widths in time (rows) and frequency (columns)
+        const int lattice = RECT ? win.lattice : T.regular_lattice;
+        const double* __restrict__ ls_weight = RECT ? win.weight : T.ls_weight;
+        const bool ls_fast = T.estimator != 0 && lattice;
+        int ls_rows = 0;     // 1: every window row holds >= 3 pilots and every pilot of the frame is finite -> the branch-free row loop below
+        if (ls_fast) {       // x*y for the LS sums: the pilot's sign applied once ((-w)*y == w*(-y) exactly), in pilot order
+            int finite = 1;
+            for (int p = tid; p < T.nPilots + 8; p += FE_THREADS) {
+                if (p >= T.nPilots) { yp[p] = {0.0, 0.0}; continue; }
+                const int q = T.pilot_cell[p];
+                const c2 y = grid[q];
+                yp[p] = type[q] < 0 ? c2{-y.re, -y.im} : y;
+                finite &= (fabs(y.re) < __builtin_inf()) & (fabs(y.im) < __builtin_inf());
+            }
+            ls_rows = __syncthreads_and(finite) && lattice == 2;
+        }
+        for (int p = tid; p < T.nPilots; p += FE_THREADS) {
+            const int c = T.pilot_cell[p], i = c / Nc, j = c - i * Nc;
+            if (T.estimator == 0) {            // ZF: Y / (x + 0i) reduces to two real divisions in __divdc3
+                const double x = type[c] < 0 ? -boost : boost;
+                Hp[p] = {grid[c].re / x, grid[c].im / x};
+            } else {                           // LS over the (clipped) window - 21x21 unless RECT -, row-major order
+                const int k0 = max(i - hwt, 0), k1 = min(i + hwt, Ns - 1), l0 = max(j - hwf, 0), l1 = min(j + hwf, Nc - 1);
+                double hr = 0, hi = 0;
+                if (ls_fast) {
+                    // pilots of row k sit at columns == k (mod 3); rows hold 17,17,16 pilots cyclically, so the pilot
+                    // index of (k, l) is 50*(k/3) + {0,17,34}[k%3] + (l - k%3)/3 and a row's window pilots are contiguous
+                    // per column residue r = k % 3: first window column == r (mod 3), how many pilots, and the offset of
+                    // that first pilot inside its row; computed once per pilot, then rows just cycle through r
+                    int cntr[3], offr[3];
+    #pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+                        const int first = l0 + ((r - l0) % 3 + 3) % 3;
+                        cntr[r] = first <= l1 ? (l1 - first) / 3 + 1 : 0;
+                        offr[r] = (r == 0 ? 0 : r == 1 ? 17 : 34) + (first - r) / 3;
+                    }
+                    int n = 0;
+                    {
+                        int r = k0 % 3;
+                        for (int k = k0; k <= k1; ++k) { n += r == 0 ? cntr[0] : r == 1 ? cntr[1] : cntr[2]; r = r == 2 ? 0 : r + 1; }
+                    }
+                    const double w = ls_weight[n];
+                    if (ls_rows) {
+                        // Rows k0, k0+1, k0+2, k0+3, ... cycle through the three column residues, so a lane's (pilot count, first pilot) pair of a
+                        // row depends only on the row's place in that cycle. A row's first three pilots are always inside the window; pilots
+                        // four to seven are added with the weight w or +0.0: x + (+-0 * y) == x exactly for finite y, and the sums start at +0.0
+                        // and can therefore never be -0.0. Same terms in the same order as the loop below, without its per-term branches.
+                        const int r0 = k0 % 3;
+                        int ptr[3];
+                        double wq[3][4];
+    #pragma unroll
+                        for (int q = 0; q < 3; ++q) {
+                            const int r = r0 + q >= 3 ? r0 + q - 3 : r0 + q;
+                            const int cn = r == 0 ? cntr[0] : r == 1 ? cntr[1] : cntr[2];
+                            ptr[q] = 50 * ((k0 + q) / 3) + (r == 0 ? offr[0] : r == 1 ? offr[1] : offr[2]);
+    #pragma unroll
+                            for (int m = 0; m < 4; ++m) wq[q][m] = m + 3 < cn ? w : 0.0;
+                        }
+                        auto add_row = [&](int q) {
+                            const c2* row = yp + ptr[q];
+                            const c2 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3], v4 = row[4], v5 = row[5], v6 = row[6];
+                            hr += w * v0.re; hi += w * v0.im;
+                            hr += w * v1.re; hi += w * v1.im;
+                            hr += w * v2.re; hi += w * v2.im;
+                            hr += wq[q][0] * v3.re; hi += wq[q][0] * v3.im;
+                            hr += wq[q][1] * v4.re; hi += wq[q][1] * v4.im;
+                            hr += wq[q][2] * v5.re; hi += wq[q][2] * v5.im;
+                            hr += wq[q][3] * v6.re; hi += wq[q][3] * v6.im;
+                            ptr[q] += 50;
+                        };
+                        for (int k = k0; k <= k1; k += 3) {
+                            add_row(0);
+                            if (k + 1 <= k1) add_row(1);
+                            if (k + 2 <= k1) add_row(2);
+                        }
+                        Hp[p] = {hr, hi};
+                        continue;
+                    }
+                    int km = k0 % 3, rowbase = 50 * (k0 / 3);
+                    for (int k = k0; k <= k1; ++k) {
+                        const int cnt = km == 0 ? cntr[0] : km == 1 ? cntr[1] : cntr[2];
+                        const c2* row = yp + rowbase + (km == 0 ? offr[0] : km == 1 ? offr[1] : offr[2]);
+                        if (km == 2) { km = 0; rowbase += 50; } else ++km;
+                        if (cnt == 0) continue;
+                        // a window row holds at most 7 pilots: fetch all seven at once (one LDS latency per row; reading past
+                        // the row's end stays inside the LDS carve), add the first cnt in order
+                        const c2 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3], v4 = row[4], v5 = row[5], v6 = row[6];
+                        hr += w * v0.re; hi += w * v0.im;
+                        if (cnt > 1) { hr += w * v1.re; hi += w * v1.im; }
+                        if (cnt > 2) { hr += w * v2.re; hi += w * v2.im; }
+                        if (cnt > 3) { hr += w * v3.re; hi += w * v3.im; }
+                        if (cnt > 4) { hr += w * v4.re; hi += w * v4.im; }
+                        if (cnt > 5) { hr += w * v5.re; hi += w * v5.im; }
+                        if (cnt > 6) { hr += w * v6.re; hi += w * v6.im; }
+                    }
+                } else {
+                    int n = 0;
+                    for (int k = k0; k <= k1; ++k)
+                        for (int l = l0; l <= l1; ++l) n += type[k * Nc + l] != 0;
+                    const double w = ls_weight[n];
+                    for (int k = k0; k <= k1; ++k)
+                        for (int l = l0; l <= l1; ++l) {
+                            const int q = k * Nc + l;
+                            if (!type[q]) continue;
+                            const double xw = type[q] < 0 ? -w : w;
+                            hr += xw * grid[q].re;
+                            hi += xw * grid[q].im;
+                        }
+                }
+                Hp[p] = {hr, hi};
+            }
         }
     }
     __syncthreads();
@@ -541,13 +589,13 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<512, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{});
+    fe_frame<512, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<1024, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{});
+    fe_frame<1024, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
 }
 
 // The same body with a rectangular LS window and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when
@@ -555,13 +603,13 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_rect_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<512, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{});
+    fe_frame<512, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<1024, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{});
+    fe_frame<1024, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
 }
 
 // The rectangular form with the channel-aware demapper (include/mercury_demapper.h): the plain span (the context's own window passed as a
@@ -569,13 +617,13 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<512, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{});
+    fe_frame<512, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<1024, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{});
+    fe_frame<1024, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{});
 }
 
 // The rectangular form with the residual carrier-offset stage (include/mercury_cfo.h), without and with the channel-aware demapper: the
@@ -584,25 +632,83 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_cfo_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
-    fe_frame<512, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo);
+    fe_frame<512, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_cfo_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
-    fe_frame<1024, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo);
+    fe_frame<1024, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{});
 }
 
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_cfo_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
     MgpuCfo cfo) {
-    fe_frame<512, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo);
+    fe_frame<512, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_cfo_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
     MgpuCfo cfo) {
-    fe_frame<1024, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo);
+    fe_frame<1024, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{});
+}
+
+// The rectangular forms with the separable Wiener estimate in place of the window mean (include/mercury_estimator.h MGPU_RUNG_WIENER): a
+// Wiener rung of an estimator ladder, as rung 0 or as a retry, for each combination of the context's demapper and carrier-offset setting.
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win,
+    MgpuWiener wn) {
+    fe_frame<512, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win,
+    MgpuWiener wn) {
+    fe_frame<1024, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_cfo_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo,
+    MgpuWiener wn) {
+    fe_frame<512, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_cfo_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo,
+    MgpuWiener wn) {
+    fe_frame<1024, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_csi_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
+    MgpuWiener wn) {
+    fe_frame<512, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_csi_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
+    MgpuWiener wn) {
+    fe_frame<1024, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_csi_cfo_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuCfo cfo,
+    MgpuWiener wn) {
+    fe_frame<512, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_csi_cfo_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuCfo cfo,
+    MgpuWiener wn) {
+    fe_frame<1024, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn);
 }

@@ -1,5 +1,5 @@
 // The estimator ladder (include/mercury_estimator.h): the two small kernels around a retry, the host loop over the rungs, the setters and
-// the host twin of the LS estimate. The retry itself is the rectangular front-end (frontend.hip; launched by launch.hip's front-end core)
+// the host twins of the LS and of the Wiener estimate. The retry itself is the rectangular front-end (frontend.hip; launched by launch.hip's front-end core)
 // on a frame list and the unchanged decoder on compact buffers.
 #include <algorithm>
 #include <cstring>
@@ -93,7 +93,7 @@ void launch_ladder(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s) {
         MgpuLsRect w = L.win[r];
         w.frames = L.d_idx;
         // untimed: the kernel timings describe rung 0
-        frontend_untimed(c, k, n, MgpuTapsDev{}, &w, s);
+        frontend_untimed(c, k, n, MgpuTapsDev{}, &w, s, r);
         decoder_untimed(c, k.llr, n, nullptr, nullptr, k.payload, k.stats, k.var, k.snrvar, s);
         for_frame_chunks(n, [&](int off, int m) {
             hipLaunchKernelGGL(mgpu_ladder_merge_kernel, dim3(m), dim3(256), 0, s, L.d_idx + off, m, r, t.N, t.payload_stride, k.llr + size_t(off) * t.N,
@@ -117,8 +117,12 @@ static int window_side(int v) {
 
 extern "C" {
 
-int mgpu_set_estimator_ladder(mgpu_ctx* c, const mgpu_ls_window* rungs, int n_rungs) {
+int mgpu_set_estimator_ladder_ex(mgpu_ctx* c, const mgpu_estimator_rung* rungs, int n_rungs, size_t rung_size) {
     if (!c) return MGPU_ERR_ARG;
+    if (rung_size != sizeof(mgpu_estimator_rung)) {
+        c->err = "estimator ladder: rung_size is not this library's sizeof(mgpu_estimator_rung)";
+        return MGPU_ERR_ARG;
+    }
     const auto& t = c->tab;
     if (n_rungs == 0 && c->lad.n == 0) return MGPU_OK;      // nothing set, nothing to clear: fine on every mode
     if (t.mfsk_M > 0 || t.estimator != MGPU_EST_LS) {
@@ -128,14 +132,59 @@ int mgpu_set_estimator_ladder(mgpu_ctx* c, const mgpu_ls_window* rungs, int n_ru
     return guard(c, [&] {
         need(n_rungs >= 0 && n_rungs <= MGPU_LADDER_MAX && (rungs || n_rungs == 0), "estimator ladder: 0..MGPU_LADDER_MAX rungs");
         mgpu_ls_window win[MGPU_LADDER_MAX]{};
+        bool any_wiener = false;
         for (int r = 0; r < n_rungs; ++r) {
-            win[r].width = window_side(rungs[r].width);
-            win[r].height = window_side(rungs[r].height);
+            need(rungs[r].kind == MGPU_RUNG_LS || rungs[r].kind == MGPU_RUNG_WIENER, "estimator ladder: a rung is MGPU_RUNG_LS or MGPU_RUNG_WIENER");
+            if (rungs[r].kind == MGPU_RUNG_WIENER) {
+                const mgpu_wiener_design& d = rungs[r].design;
+                need(mgpu::wiener_design_ok(mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db}),
+                     "estimator ladder: a Wiener design needs tau_max > tau_min, doppler_hz >= 0 and snr_db in -20..40, all finite");
+                any_wiener = true;
+                continue;
+            }
+            win[r].width = window_side(rungs[r].window.width);
+            win[r].height = window_side(rungs[r].window.height);
             need(win[r].width && win[r].height, "estimator ladder: a window is 1..21 cells wide (the front-end reads at most 7 pilots of a window row) and 1..21 high");
         }
         // everything that can fail comes before the context changes
-        DevArray<double> weight[MGPU_LADDER_MAX];
-        for (int r = 0; r < n_rungs; ++r) weight[r] = upload(mgpu::ls_weight_table(t.pilot_boost, win[r].width * win[r].height));
+        DevArray<double> weight[MGPU_LADDER_MAX], wA[MGPU_LADDER_MAX], wB[MGPU_LADDER_MAX];
+        DevArray<int> woff[MGPU_LADDER_MAX];
+        DevArray<uint16_t> widx[MGPU_LADDER_MAX];
+        MgpuWiener wiener[MGPU_LADDER_MAX]{};
+        for (int r = 0; r < n_rungs; ++r) {
+            if (rungs[r].kind == MGPU_RUNG_LS) { weight[r] = upload(mgpu::ls_weight_table(t.pilot_boost, win[r].width * win[r].height)); continue; }
+            const mgpu_wiener_design& d = rungs[r].design;
+            const mgpu::WienerTables w = mgpu::build_wiener_tables(t.cell_type, t.Nsymb, t.Nc, t.pilot_boost, mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db});
+            // the tables as MgpuWiener (ls_rect.h) names them
+            std::vector<double> A, B;
+            std::vector<int> off;
+            for (const auto& m : w.A) { off.push_back(int(A.size())); A.insert(A.end(), m.begin(), m.end()); }
+            const size_t b_off = off.size();
+            for (const auto& m : w.B) { off.push_back(int(B.size() / 2)); for (const mgpu::Cplx& v : m) { B.push_back(v.re); B.push_back(v.im); } }
+            const size_t nP = w.time_class.size();
+            need(nP == size_t(t.nPilots), "estimator ladder: the Wiener tables' pilots are not the mode's");
+            std::vector<uint16_t> idx(nP * 8), col_start(size_t(t.Nc), 0);
+            size_t at_list = 0;
+            for (int cc = 0; cc < t.Nc; ++cc) {
+                col_start[size_t(cc)] = uint16_t(at_list);
+                for (uint16_t p : w.col_pilots[size_t(cc)]) { idx.push_back(p); ++at_list; }
+            }
+            for (int cc = 0; cc < t.Nc; ++cc)
+                for (uint16_t p : w.col_pilots[size_t(cc)]) {
+                    uint16_t* e = &idx[size_t(p) * 8];
+                    e[0] = w.time_class[p]; e[1] = w.time_row[p]; e[2] = uint16_t(w.time_members[w.time_class[p]].size()); e[3] = col_start[size_t(cc)];
+                }
+            for (int sy = 0; sy < t.Nsymb; ++sy)
+                for (uint16_t p : w.row_pilots[size_t(sy)]) {
+                    uint16_t* e = &idx[size_t(p) * 8];
+                    e[4] = w.freq_class[p]; e[5] = w.freq_row[p]; e[6] = uint16_t(w.freq_members[w.freq_class[p]].size()); e[7] = w.row_pilots[size_t(sy)].front();
+                    need(p == e[7] + e[5], "estimator ladder: a symbol's pilots are not consecutive in pilot order");
+                }
+            wA[r] = upload(A); wB[r] = upload(B); woff[r] = upload(off); widx[r] = upload(idx);
+            wiener[r].A = wA[r]; wiener[r].B = wB[r];
+            wiener[r].a_off = woff[r]; wiener[r].b_off = woff[r] + b_off;
+            wiener[r].pilot = widx[r]; wiener[r].col_list = widx[r] + nP * 8;
+        }
         const size_t B = size_t(c->max_batch);
         Ladder& L = c->lad;
         HIPCK(hipStreamSynchronize(c->stream));
@@ -145,6 +194,18 @@ int mgpu_set_estimator_ladder(mgpu_ctx* c, const mgpu_ls_window* rungs, int n_ru
             L.d_rung.grow(B * sizeof(int));
             L.d_counters.grow((MGPU_LADDER_MAX + 1) * sizeof(unsigned long long));
             HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_rect_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_fe)));
+        }
+        if (any_wiener) {
+            // the Wiener kernels' LDS limits: the plain carve, and the channel-aware demapper's for its forms (where that fits at all:
+            // mgpu_set_demapper refuses a geometry for which it does not)
+            const size_t lds = mgpu_frontend_wiener_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads, 0);
+            const size_t csi_lds = mgpu_frontend_wiener_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads, 1);
+            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+            if (csi_lds <= size_t(160) * 1024) {
+                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_csi_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(csi_lds)));
+                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_csi_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(csi_lds)));
+            }
         }
         if (n_rungs > 1) {
             L.d_idx.grow(B * sizeof(int)); L.d_count.grow(sizeof(int));
@@ -157,23 +218,43 @@ int mgpu_set_estimator_ladder(mgpu_ctx* c, const mgpu_ls_window* rungs, int n_ru
             L.rung[r] = r < n_rungs ? win[r] : mgpu_ls_window{0, 0};
             L.weight[r] = r < n_rungs ? std::move(weight[r]) : DevArray<double>();
             L.win[r] = MgpuLsRect{};
-            if (r >= n_rungs) continue;
+            L.kind[r] = r < n_rungs ? rungs[r].kind : MGPU_RUNG_LS;
+            L.design[r] = r < n_rungs && L.kind[r] == MGPU_RUNG_WIENER ? rungs[r].design : mgpu_wiener_design{};
+            L.wiener_A[r] = std::move(wA[r]); L.wiener_B[r] = std::move(wB[r]); L.wiener_off[r] = std::move(woff[r]); L.wiener_idx[r] = std::move(widx[r]);
+            L.wiener[r] = wiener[r];
+            if (r >= n_rungs || L.kind[r] == MGPU_RUNG_WIENER) continue;
             const int hw_f = win[r].width / 2;
             L.win[r].weight = L.weight[r];
             L.win[r].hw_f = hw_f; L.win[r].hw_t = win[r].height / 2;
             // as create.hip does for the square window: 2 when every (clipped) window row holds >= 3 pilots of each column residue
             L.win[r].lattice = c->dev.regular_lattice ? (std::min(hw_f + 1, t.Nc) >= 9 ? 2 : 1) : 0;
         }
-        L.rung0_is_default = n_rungs > 0 && win[0].width == t.lsw && win[0].height == t.lsw;
+        L.rung0_is_default = n_rungs > 0 && L.kind[0] == MGPU_RUNG_LS && win[0].width == t.lsw && win[0].height == t.lsw;
         L.n = n_rungs;
         L.last_F = 0;
     });
+}
+
+int mgpu_set_estimator_ladder(mgpu_ctx* c, const mgpu_ls_window* rungs, int n_rungs) {      // the all-LS case
+    if (!c) return MGPU_ERR_ARG;
+    mgpu_estimator_rung ex[MGPU_LADDER_MAX]{};
+    const bool countable = n_rungs >= 0 && n_rungs <= MGPU_LADDER_MAX && (rungs || n_rungs == 0);
+    for (int r = 0; countable && r < n_rungs; ++r) { ex[r].kind = MGPU_RUNG_LS; ex[r].window = rungs[r]; }
+    // a count the rungs cannot be read for is refused by the call below before it reads any
+    return mgpu_set_estimator_ladder_ex(c, countable && n_rungs > 0 ? ex : nullptr, countable ? n_rungs : -1, sizeof(mgpu_estimator_rung));
 }
 
 int mgpu_get_estimator_ladder(mgpu_ctx* c, mgpu_ls_window* rungs, int* n_rungs) {
     if (!c || !n_rungs || !rungs) return MGPU_ERR_ARG;
     *n_rungs = c->lad.n;
     for (int r = 0; r < c->lad.n; ++r) rungs[r] = c->lad.rung[r];
+    return MGPU_OK;
+}
+
+int mgpu_get_estimator_ladder_ex(mgpu_ctx* c, mgpu_estimator_rung* rungs, int* n_rungs, size_t rung_size) {
+    if (!c || !n_rungs || !rungs || rung_size != sizeof(mgpu_estimator_rung)) return MGPU_ERR_ARG;
+    *n_rungs = c->lad.n;
+    for (int r = 0; r < c->lad.n; ++r) rungs[r] = mgpu_estimator_rung{c->lad.kind[r], c->lad.rung[r], c->lad.design[r]};
     return MGPU_OK;
 }
 
@@ -270,6 +351,107 @@ int mgpu_host_ls_estimate(int cfg, const mgpu_explicit_params* p, int width, int
             H[2 * pilot] = hr; H[2 * pilot + 1] = hi;
             ++pilot;
         }
+        return MGPU_OK;
+    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+}
+
+namespace {
+// the tables of the last (geometry, design) asked for: a sweep over frames builds them once
+struct TwinWiener {
+    std::shared_ptr<const TwinGeometry> geometry;
+    mgpu_wiener_design design{};
+    mgpu::WienerTables tables;
+};
+std::mutex wiener_mutex;
+std::shared_ptr<const TwinWiener> wiener_last;
+
+// null with *rc set where the mode or the design is refused
+std::shared_ptr<const TwinWiener> twin_wiener(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d_or_null, int* rc) {
+    const mgpu_wiener_design d = d_or_null ? *d_or_null : mgpu_wiener_design MGPU_WIENER_DESIGN_DEFAULT;
+    *rc = MGPU_ERR_ARG;
+    if (!mgpu::wiener_design_ok(mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db})) return nullptr;
+    mgpu::ExplicitParams xp;
+    std::string err;
+    if (!explicit_params_from(p, xp, err, rc)) return nullptr;
+    xp.ls_window = mgpu::ExplicitParams().ls_window;
+    const std::shared_ptr<const TwinGeometry> geometry = twin_geometry(cfg, xp);
+    if (!geometry->ls) { *rc = MGPU_ERR_UNSUPPORTED; return nullptr; }
+    *rc = MGPU_OK;
+    std::lock_guard<std::mutex> lock(wiener_mutex);
+    if (wiener_last && wiener_last->geometry == geometry && std::memcmp(&wiener_last->design, &d, sizeof(d)) == 0) return wiener_last;
+    auto w = std::make_shared<TwinWiener>();
+    w->geometry = geometry; w->design = d;
+    w->tables = mgpu::build_wiener_tables(geometry->cell_type, geometry->Nsymb, geometry->Nc, geometry->pilot_boost,
+                                          mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db});
+    wiener_last = w;
+    return w;
+}
+}  // namespace
+
+int mgpu_host_wiener_estimate(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d, const double* grid, double* H) {
+    if (!grid || !H) return MGPU_ERR_ARG;
+    try {
+        int rc = MGPU_OK;
+        const std::shared_ptr<const TwinWiener> twin = twin_wiener(cfg, p, d, &rc);
+        if (!twin) return rc;
+        const TwinGeometry& t = *twin->geometry;
+        const mgpu::WienerTables& w = twin->tables;
+        const size_t nP = w.time_class.size();
+        std::vector<double> yp(2 * nP), tp(2 * nP);
+        size_t pilot = 0;
+        for (int q = 0; q < t.Nsymb * t.Nc; ++q) {      // the pilots times their sign, in pilot order
+            if (!t.cell_type[size_t(q)]) continue;
+            const bool neg = t.pilot_val[size_t(q)] < 0;
+            yp[2 * pilot] = neg ? -grid[2 * q] : grid[2 * q];
+            yp[2 * pilot + 1] = neg ? -grid[2 * q + 1] : grid[2 * q + 1];
+            ++pilot;
+        }
+        for (int cc = 0; cc < t.Nc; ++cc) {             // along time, per carrier
+            const auto& list = w.col_pilots[size_t(cc)];
+            const size_t n = list.size();
+            for (size_t i = 0; i < n; ++i) {
+                const double* a = &w.A[w.time_class[list[i]]][i * n];
+                double hr = 0, hi = 0;
+                for (size_t k = 0; k < n; ++k) { hr += a[k] * yp[2 * list[k]]; hi += a[k] * yp[2 * list[k] + 1]; }
+                tp[2 * list[i]] = hr; tp[2 * list[i] + 1] = hi;
+            }
+        }
+        for (int sy = 0; sy < t.Nsymb; ++sy) {          // along frequency, per symbol
+            const auto& list = w.row_pilots[size_t(sy)];
+            const size_t n = list.size();
+            for (size_t i = 0; i < n; ++i) {
+                const mgpu::Cplx* b = &w.B[w.freq_class[list[i]]][i * n];
+                double hr = 0, hi = 0;
+                for (size_t m = 0; m < n; ++m) {
+                    const double tr = tp[2 * list[m]], ti = tp[2 * list[m] + 1];
+                    hr += b[m].re * tr - b[m].im * ti;
+                    hi += b[m].re * ti + b[m].im * tr;
+                }
+                H[2 * list[i]] = hr; H[2 * list[i] + 1] = hi;
+            }
+        }
+        return MGPU_OK;
+    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+}
+
+int mgpu_host_wiener_tables(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d, int which, int cls, int* n_classes, int* n,
+                            int* members, double* matrix) {
+    if (which != 0 && which != 1) return MGPU_ERR_ARG;
+    try {
+        int rc = MGPU_OK;
+        const std::shared_ptr<const TwinWiener> twin = twin_wiener(cfg, p, d, &rc);
+        if (!twin) return rc;
+        const mgpu::WienerTables& w = twin->tables;
+        const auto& sets = which == 0 ? w.time_members : w.freq_members;
+        if (n_classes) *n_classes = int(sets.size());
+        if (!n && !members && !matrix) return MGPU_OK;
+        if (cls < 0 || size_t(cls) >= sets.size()) return MGPU_ERR_ARG;
+        const size_t m = sets[size_t(cls)].size();
+        if (n) *n = int(m);
+        if (members) std::copy(sets[size_t(cls)].begin(), sets[size_t(cls)].end(), members);
+        if (matrix && which == 0) std::copy(w.A[size_t(cls)].begin(), w.A[size_t(cls)].end(), matrix);
+        if (matrix && which == 1)
+            for (size_t i = 0; i < m * m; ++i) { matrix[2 * i] = w.B[size_t(cls)][i].re; matrix[2 * i + 1] = w.B[size_t(cls)][i].im; }
         return MGPU_OK;
     } catch (const std::exception&) { return MGPU_ERR_ARG; }
 }

@@ -9,7 +9,7 @@
 
 namespace mgpu_detail {
 
-void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s) {
+void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s, int rung) {
     const auto& t = c->tab;
     MgpuDev dev = c->dev;                        // kernel argument; the frame stride can differ from the frame length
     if (io.frame_stride > 0) dev.frame_samples = io.frame_stride;
@@ -36,6 +36,7 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
         return;
     }
     if (!rect && c->lad.n > 0 && !c->lad.rung0_is_default) rect = &c->lad.win[0];      // rung 0 of an estimator ladder with a window of its own
+    const MgpuWiener* wiener = rung < c->lad.n && c->lad.kind[rung] == MGPU_RUNG_WIENER ? &c->lad.wiener[rung] : nullptr;   // a Wiener rung: `rect` carries the frame list alone
     const bool csi = c->dmp.mode == MGPU_DEMAP_CSI;                                    // the channel-aware demapper: one kernel for every window
     if (csi && !rect) rect = &c->dmp.own;
     const bool cfo = c->cfo.mode == MGPU_CFO_PILOTS;                                   // residual carrier-offset correction: again one kernel for every window
@@ -53,7 +54,17 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
             const size_t row = size_t(io.frame0) + size_t(off);
             co.step_rows = cfo && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
             co.step = co.step_rows > 0 ? c->cfo.d_step + row : nullptr;
-            if (cfo && csi)
+            const size_t lds_wiener = wiener ? mgpu_frontend_wiener_lds_bytes(dev.G, dev.nPilots, dev.nBits, c->fe_threads, csi ? 1 : 0) : 0;
+            if (wiener && cfo && csi)
+                hipLaunchKernelGGL(fe_wiener_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co, *wiener);
+            else if (wiener && cfo)
+                hipLaunchKernelGGL(fe_wiener_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co, *wiener);
+            else if (wiener && csi)
+                hipLaunchKernelGGL(fe_wiener_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, *wiener);
+            else if (wiener)
+                hipLaunchKernelGGL(fe_wiener_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar,
+                                   static_cast<double*>(nullptr), tp, w, *wiener);
+            else if (cfo && csi)
                 hipLaunchKernelGGL(fe_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co);
             else if (cfo)
                 hipLaunchKernelGGL(fe_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co);

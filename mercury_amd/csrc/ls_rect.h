@@ -25,3 +25,16 @@ struct MgpuCfo {
     int step_rows;          // rows of `step` that may be written
     int Dy;
 };
+
+// What the separable Wiener estimator (frontend.hip WIENER; include/mercury_estimator.h MGPU_RUNG_WIENER) needs beyond MgpuDev, again an
+// argument of its own; made at mgpu_set_estimator_ladder_ex (ladder.hip) from wiener_tables.cpp's tables. The matrices stay in global
+// memory: a few per mode, shared by every workgroup.
+struct MgpuWiener {
+    const double* A;            // the time classes' matrices one after the other, each row-major n x n
+    const double* B;            // the frequency classes' matrices one after the other, each row-major n x n complex (re, im)
+    const int* a_off;           // [time classes] a class's first double in A
+    const int* b_off;           // [frequency classes] a class's first complex in B
+    const uint16_t* pilot;      // [nPilots][8] time class, row in it, its size n, first entry of the carrier's list in col_list;
+                                //              frequency class, row in it, its size n, the symbol's first pilot (a symbol's pilots are consecutive)
+    const uint16_t* col_list;   // every carrier's pilots in ascending symbols, carrier after carrier
+};

@@ -120,6 +120,24 @@ ModeTables build_mode_tables(int cfg, int mfsk_ctrl_mode, const uint8_t* ldpc_bl
 // (misc.cc:73-91). ModeTables::ls_weight is this for lsw*lsw; an estimator ladder keeps one per rung, for width*height
 std::vector<double> ls_weight_table(double pilot_boost, int max_population);
 
+// The separable Wiener estimator's design and tables (include/mercury_estimator.h: mgpu_wiener_design; wiener_tables.cpp). A time class is a
+// distinct set of pilot rows (symbols) a carrier has, a frequency class a distinct set of pilot carriers a symbol has, both in the order
+// they are first met; a class of n members has one n x n row-major matrix.
+struct WienerDesign { double tau_min_us = -333.33, tau_max_us = 2333.33, doppler_hz = 0.5, snr_db = 0.0; };
+struct WienerTables {
+    std::vector<std::vector<int>> time_members, freq_members;   // the classes' rows / carriers, ascending
+    std::vector<std::vector<double>> A;                         // per time class: Rt (Rt + s2 I)^-1, rows at unit gain, times 1 / boost
+    std::vector<std::vector<Cplx>> B;                           // per frequency class: Rf (Rf + s2b I)^-1, rows at unit gain
+    // per pilot (row-major pilot order): its carrier's time class and its place among that carrier's pilots, its symbol's frequency class
+    // and its place among that symbol's pilots
+    std::vector<uint16_t> time_class, time_row, freq_class, freq_row;
+    std::vector<std::vector<uint16_t>> col_pilots;              // [Nc] a carrier's pilots (pilot indices), ascending symbols
+    std::vector<std::vector<uint16_t>> row_pilots;              // [Nsymb] a symbol's pilots, ascending carriers: consecutive indices
+    double s2 = 0, s2b = 0;                                     // the noise terms of the time and of the frequency design
+};
+bool wiener_design_ok(const WienerDesign& d);                  // tau_max > tau_min, doppler >= 0, snr_db in [-20, 40], all finite
+WienerTables build_wiener_tables(const std::vector<uint8_t>& cell_type, int Nsymb, int Nc, double pilot_boost, const WienerDesign& d);
+
 uint16_t crc16_modbus(const uint8_t* bytes, int n);
 
 // pre_equalization_channel of a freshly loaded configuration for a given carrier (telecom_system.cc:3108-3145): [Nc]

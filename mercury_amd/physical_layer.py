@@ -129,19 +129,118 @@ EXPORTED_SYMBOLS = [
 
 # ---- rectangular LS windows and the estimator ladder (include/mercury_estimator.h) -------------------------------
 ESTIMATOR_SYMBOLS = ["mgpu_set_estimator_ladder", "mgpu_get_estimator_ladder", "mgpu_estimator_rungs_last", "mgpu_estimator_ladder_counters",
-                     "mgpu_host_ls_estimate"]
+                     "mgpu_host_ls_estimate", "mgpu_set_estimator_ladder_ex", "mgpu_get_estimator_ladder_ex", "mgpu_host_wiener_estimate",
+                     "mgpu_host_wiener_tables"]
 LADDER_MAX = 4
+RUNG_LS, RUNG_WIENER = 0, 1
+WIENER_DESIGN_DEFAULT = dict(tau_min_us=-333.33, tau_max_us=2333.33, doppler_hz=0.5, snr_db=0.0)
 
 
 class LsWindow(C.Structure):      # mgpu_ls_window
     _fields_ = [("width", C.c_int), ("height", C.c_int)]
 
 
+class WienerDesign(C.Structure):  # mgpu_wiener_design
+    _fields_ = [("tau_min_us", C.c_double), ("tau_max_us", C.c_double), ("doppler_hz", C.c_double), ("snr_db", C.c_double)]
+
+
+class EstimatorRung(C.Structure):  # mgpu_estimator_rung
+    _fields_ = [("kind", C.c_int), ("window", LsWindow), ("design", WienerDesign)]
+
+
+def _wiener_design(design):
+    d = dict(WIENER_DESIGN_DEFAULT)
+    for k, v in (design or {}).items():
+        if k not in d:
+            raise MgpuError("a Wiener design has %s, not %r" % (sorted(d), k))
+        d[k] = float(v)
+    return WienerDesign(d["tau_min_us"], d["tau_max_us"], d["doppler_hz"], d["snr_db"])
+
+
 def parse_ladder(text):
-    """'21x21,5x21' -> [(21, 21), (5, 21)] (width = carriers, height = symbols); '' or None -> []"""
+    """'21x21,5x21' -> [(21, 21), (5, 21)] (width = carriers, height = symbols); '' or None -> []. A Wiener rung (include/mercury_estimator.h:
+    MGPU_RUNG_WIENER) is 'wiener' or 'wiener:tau=-333/2333,fd=0.5,snr=5' (delay bounds in us, Doppler in Hz, design SNR in dB; what is left
+    out keeps its default) -> ("wiener", {the fields given, named as mgpu_wiener_design's})."""
     if not text:
         return []
-    return [tuple(int(v) for v in rung.lower().split("x")) for rung in text.split(",")]
+    rungs = []
+    for item in text.split(","):
+        item = item.strip().lower()
+        if rungs and isinstance(rungs[-1][1], dict) and "=" in item and "x" not in item.split("=")[0] and not item.startswith("wiener"):
+            key, value = item.split("=", 1)          # a further field of the Wiener rung before it: the fields are comma-separated too
+        elif item.startswith("wiener"):
+            rungs.append(("wiener", {}))
+            if item == "wiener":
+                continue
+            if not item.startswith("wiener:") or "=" not in item:
+                raise MgpuError("a Wiener rung is 'wiener' or 'wiener:tau=MIN/MAX,fd=HZ,snr=DB', not %r" % item)
+            key, value = item[len("wiener:"):].split("=", 1)
+        else:
+            rungs.append(tuple(int(v) for v in item.split("x")))
+            continue
+        d = rungs[-1][1]
+        if key == "tau":
+            lo, hi = value.split("/")
+            d["tau_min_us"], d["tau_max_us"] = float(lo), float(hi)
+        elif key in ("fd", "snr"):
+            d["doppler_hz" if key == "fd" else "snr_db"] = float(value)
+        else:
+            raise MgpuError("a Wiener rung's fields are tau, fd and snr, not %r" % key)
+    return rungs
+
+
+def _is_wiener(rung):
+    return rung == "wiener" or (isinstance(rung, (tuple, list)) and len(rung) == 2 and rung[0] == "wiener")
+
+
+def host_wiener_estimate(cfg, grid, design=None, explicit=None):
+    """mgpu_host_wiener_estimate: the separable Wiener estimate at the pilot cells (row-major pilot order, complex128 [nPilots]) of one frame
+    grid (complex128 [Nsymb * Nc], after the AGC); no GPU. design: dict with any of tau_min_us, tau_max_us, doppler_hz, snr_db (None: the
+    defaults). explicit: as RxPhy's."""
+    lib = load_library()
+    lib.mgpu_host_wiener_estimate.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    g = np.ascontiguousarray(grid, np.complex128).ravel()
+    xp = _explicit_struct(explicit)
+    ref = C.byref(xp) if xp is not None else None
+    d = _wiener_design(design)
+    # nPilots of the (possibly explicit) geometry: the entries a call on an all-zero grid writes
+    count = np.full(g.size, np.nan + 0j, np.complex128)
+    rc = lib.mgpu_host_wiener_estimate(int(cfg), ref, C.byref(d), _ptr(np.zeros_like(g)), _ptr(count))
+    if rc != 0:
+        raise MgpuError("mgpu_host_wiener_estimate failed (%d)" % rc, rc)
+    out = np.zeros(int(np.count_nonzero(~np.isnan(count.real))), np.complex128)
+    rc = lib.mgpu_host_wiener_estimate(int(cfg), ref, C.byref(d), _ptr(g), _ptr(out))
+    if rc != 0:
+        raise MgpuError("mgpu_host_wiener_estimate failed (%d)" % rc, rc)
+    return out
+
+
+def host_wiener_tables(cfg, design=None, explicit=None):
+    """mgpu_host_wiener_tables: (time classes, frequency classes) of a design, each a list of (members: int32 [n] - the pilot rows a carrier
+    has / the pilot carriers a symbol has -, matrix [n, n]: float64 / complex128, as the kernel reads it); no GPU."""
+    lib = load_library()
+    lib.mgpu_host_wiener_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    xp = _explicit_struct(explicit)
+    ref = C.byref(xp) if xp is not None else None
+    d = _wiener_design(design)
+    out = []
+    for which in (0, 1):
+        count = C.c_int()
+        rc = lib.mgpu_host_wiener_tables(int(cfg), ref, C.byref(d), which, 0, C.byref(count), None, None, None)
+        if rc != 0:
+            raise MgpuError("mgpu_host_wiener_tables failed (%d)" % rc, rc)
+        classes = []
+        for cls in range(count.value):
+            n = C.c_int()
+            lib.mgpu_host_wiener_tables(int(cfg), ref, C.byref(d), which, cls, None, C.byref(n), None, None)
+            members = np.zeros(n.value, np.int32)
+            matrix = np.zeros((n.value, n.value), np.complex128 if which else np.float64)
+            rc = lib.mgpu_host_wiener_tables(int(cfg), ref, C.byref(d), which, cls, None, None, _ptr(members), _ptr(matrix))
+            if rc != 0:
+                raise MgpuError("mgpu_host_wiener_tables failed (%d)" % rc, rc)
+            classes.append((members, matrix))
+        out.append(classes)
+    return tuple(out)
 
 
 def host_ls_estimate(cfg, grid, width, height, explicit=None):
@@ -478,8 +577,19 @@ class RxPhy:
     # ---- estimator ladder (include/mercury_estimator.h) ----------------------------------------
     def set_estimator_ladder(self, rungs):
         """rungs: [(width, height), ...] in cells (carriers x symbols), at most LADDER_MAX; [] or None: no ladder. Frames whose CRC fails are
-        re-estimated and decoded again with the next rung, on the device, in every receive entry point of this context."""
+        re-estimated and decoded again with the next rung, on the device, in every receive entry point of this context. A rung may also be
+        "wiener" or ("wiener", {design fields}) as parse_ladder gives it: the separable Wiener estimator (MGPU_RUNG_WIENER)."""
         rungs = list(rungs or [])
+        if any(_is_wiener(r) for r in rungs):
+            arr = (EstimatorRung * len(rungs))()
+            for i, r in enumerate(rungs):
+                if _is_wiener(r):
+                    arr[i] = EstimatorRung(RUNG_WIENER, LsWindow(0, 0), _wiener_design(None if r == "wiener" else r[1]))
+                else:
+                    arr[i] = EstimatorRung(RUNG_LS, LsWindow(int(r[0]), int(r[1])), WienerDesign())
+            self.lib.mgpu_set_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
+            self._ck(self.lib.mgpu_set_estimator_ladder_ex(self.h, arr, len(rungs), C.sizeof(EstimatorRung)))
+            return
         arr = (LsWindow * max(len(rungs), 1))(*[LsWindow(int(w), int(h)) for w, h in rungs])
         self.lib.mgpu_set_estimator_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self._ck(self.lib.mgpu_set_estimator_ladder(self.h, arr if rungs else None, len(rungs)))
@@ -491,6 +601,15 @@ class RxPhy:
         self.lib.mgpu_get_estimator_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_estimator_ladder(self.h, arr, C.byref(n)))
         return [(arr[r].width, arr[r].height) for r in range(n.value)]
+
+    @property
+    def estimator_ladder_ex(self):
+        """the rungs with their kind: (width, height) for an LS rung, ("wiener", {design}) for a Wiener rung"""
+        arr, n = (EstimatorRung * LADDER_MAX)(), C.c_int()
+        self.lib.mgpu_get_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        self._ck(self.lib.mgpu_get_estimator_ladder_ex(self.h, arr, C.byref(n), C.sizeof(EstimatorRung)))
+        return [("wiener", {k: getattr(arr[r].design, k) for k in WIENER_DESIGN_DEFAULT}) if arr[r].kind == RUNG_WIENER
+                else (arr[r].window.width, arr[r].window.height) for r in range(n.value)]
 
     def last_rungs(self, F):
         """winning rung of each of the first F frames of the last receive call, -1 where no rung decoded: int32 [F]"""
@@ -1245,7 +1364,7 @@ class RxCapture:
 
     def __init__(self, rx, S, carrier_hz, trials_max=2, use_last_good_time_sync=1, use_last_good_freq_offset=1, coarse_freq_sync=0,
                  initial_windows=None, max_hops=0, ladder=None):
-        """ladder: [(width, height), ...] set on the context `rx` (RxPhy.set_estimator_ladder) before the capture is made; None: as it is"""
+        """ladder: rungs as RxPhy.set_estimator_ladder takes them, set on the context `rx` (RxPhy.set_estimator_ladder) before the capture is made; None: as it is"""
         self.rx, self.lib, self.S = rx, rx.lib, S
         if ladder is not None:
             rx.set_estimator_ladder(ladder)
@@ -1447,7 +1566,7 @@ class LinkSim:
     (include/mercury_linksim.h). config: linksim_config(...); esn0_db: None (no noise), a number or [S]."""
 
     def __init__(self, rx, config, esn0_db=None, ladder=None):
-        """ladder: [(width, height), ...] set on the context `rx` (RxPhy.set_estimator_ladder) before the simulator is made; None: as it is"""
+        """ladder: rungs as RxPhy.set_estimator_ladder takes them, set on the context `rx` (RxPhy.set_estimator_ladder) before the simulator is made; None: as it is"""
         self.rx, self.lib, self.S, self.config = rx, rx.lib, config.S, config
         if ladder is not None:
             rx.set_estimator_ladder(ladder)

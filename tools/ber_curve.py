@@ -9,7 +9,8 @@ prints EsN0;BER;FER lines like the reference does, for far more frames per point
 --threshold (with --passband: ber_curve.py --passband [--channel C] --threshold cfg [frames_per_point]): Es/N0 from 3 dB below the
 reference's AWGN FER < 0.1 value (include/common/common_defines.h:130-147) to 40 dB above it in 1 dB steps, in one call; one JSON line
 gives the first point of the first run of three with FER < 0.1 ("fer01_esn0_db", null if none) beside the AWGN value.
---ladder 21x21,5x21 (any form): an estimator ladder (include/mercury_estimator.h; windows as carriers x symbols) on the context; the JSON
+--ladder 21x21,5x21 (any form): an estimator ladder (include/mercury_estimator.h; windows as carriers x symbols, or `wiener` /
+`wiener:tau=-333/2333,fd=0.5,snr=5` for the separable Wiener estimator) on the context; the JSON
 line then carries the frames each rung decoded.
 --diversity D (baseband form; with --channel and at most a one-rung --ladder): D branches per payload, each with its own channel realisation
 and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_per_point counts payloads, Es/N0 is per branch.
@@ -38,11 +39,15 @@ DEMAPPER = ["maxlog"]   # --demapper
 CFO = ["off"]           # --cfo
 
 
+def _rung_names(rx):
+    return ["wiener" if r[0] == "wiener" else "%dx%d" % r for r in rx.estimator_ladder_ex]
+
+
 def _ladder_fields(rx):
     if not LADDER:
         return {}
     by, frames = rx.ladder_counters()
-    return {"ladder": ["%dx%d" % r for r in rx.estimator_ladder], "decoded_by_rung": [int(v) for v in by[: len(LADDER)]], "ladder_frames": frames}
+    return {"ladder": _rung_names(rx), "decoded_by_rung": [int(v) for v in by[: len(LADDER)]], "ladder_frames": frames}
 
 
 def threshold(cfg, n, channel):
@@ -98,7 +103,7 @@ def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, see
     res = rx.baseband_test_esn0(pts, n, seed=seed, hf_channel=channel, diversity=diversity)
     dt = time.perf_counter() - t0
     # a grouped span does not run the ladder's marking pass: with --diversity only the window is reported
-    extra = {"diversity": diversity, "ladder": ["%dx%d" % r for r in rx.estimator_ladder]} if diversity else _ladder_fields(rx)
+    extra = {"diversity": diversity, "ladder": _rung_names(rx)} if diversity else _ladder_fields(rx)
     rx.close()
     return res, {"cfg": cfg, "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
                  "frames_per_s": len(res) * n * per / dt, "demapper": DEMAPPER[0], "cfo": CFO[0], **extra}
