@@ -29,6 +29,7 @@ extern "C" const unsigned long mgpu_ldpc_blob_size;
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi);
+extern "C" size_t mgpu_frontend_nmap_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_spa_lds_bytes(int E, int N);
 extern "C" size_t mgpu_gbf_lds_bytes(int N);
 extern "C" size_t mgpu_spa_fast_lds_bytes(int Sg, int N);
@@ -52,6 +53,14 @@ extern "C" __global__ void mgpu_frontend_wiener_csi_kernel(MgpuDev, const double
 extern "C" __global__ void mgpu_frontend_wiener_csi_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
 extern "C" __global__ void mgpu_frontend_wiener_csi_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
 extern "C" __global__ void mgpu_frontend_wiener_csi_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_nmap_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap);
+extern "C" __global__ void mgpu_frontend_nmap_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap);
+extern "C" __global__ void mgpu_frontend_nmap_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo);
+extern "C" __global__ void mgpu_frontend_nmap_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo);
+extern "C" __global__ void mgpu_frontend_wiener_nmap_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_nmap_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_nmap_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo, MgpuWiener);
+extern "C" __global__ void mgpu_frontend_wiener_nmap_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo, MgpuWiener);
 extern "C" __global__ void mgpu_ladder_select_kernel(const MgpuStatsDev*, int, int, int*, int*, int*, unsigned long long*);
 extern "C" __global__ void mgpu_ladder_merge_kernel(const int*, int, int, int, int, const float*, const float*, const float*, const double*, const uint8_t*,
                                                     const MgpuStatsDev*, float*, float*, float*, double*, uint8_t*, MgpuStatsDev*, int*, unsigned long long*);
@@ -206,7 +215,13 @@ struct Demapper {
     size_t lds = 0;                                 // the CSI form's LDS carve
     MgpuLsRect own{};                               // the context's own square window as that (rectangular) form takes it
     MgpuCsi arg{};
-    DevArray<uint16_t> d_sym_data;                  // arg.sym_data; made with the first MGPU_DEMAP_CSI
+    DevArray<uint16_t> d_sym_data;                  // arg.sym_data; made with the first MGPU_DEMAP_CSI or MGPU_DEMAP_NMAP
+    // MGPU_DEMAP_NMAP: every front-end launch of the fused span is a noise-map form (a CSI form with per-carrier and per-symbol noise factors)
+    mgpu_demapper_params params{2.0, 1};            // as set; the defaults until then
+    size_t nmap_lds = 0;                            // the noise-map forms' LDS carve
+    MgpuNmap nmap{};                                // lists, band, smooth; fc / fs / rows are set per launch
+    DevArray<uint16_t> d_nmap_idx;                  // car_list, car_first, sym_first; made with the first MGPU_DEMAP_NMAP
+    DevArray<double> d_fc, d_fs;                    // [max_batch][Nc], [max_batch][Nsymb] the factors of the last call's frames, by the frame's row
 };
 
 // The context's residual carrier-offset correction (include/mercury_cfo.h; cfo.hip). MGPU_CFO_PILOTS: every front-end launch of the fused span
@@ -349,6 +364,16 @@ inline FrontendWienerCsiKernel fe_wiener_csi_kernel(int threads) { return thread
 using FrontendWienerCsiCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
 inline FrontendWienerCsiCfoKernel fe_wiener_csi_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_csi_cfo_kernel_t1024 : mgpu_frontend_wiener_csi_cfo_kernel; }
 
+// the noise-map demapper's forms (frontend.hip NMAP): plain, with the carrier-offset stage, and both again with the Wiener estimate
+using FrontendNmapKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap);
+inline FrontendNmapKernel fe_nmap_kernel(int threads) { return threads == 1024 ? mgpu_frontend_nmap_kernel_t1024 : mgpu_frontend_nmap_kernel; }
+using FrontendNmapCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo);
+inline FrontendNmapCfoKernel fe_nmap_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_nmap_cfo_kernel_t1024 : mgpu_frontend_nmap_cfo_kernel; }
+using FrontendWienerNmapKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuWiener);
+inline FrontendWienerNmapKernel fe_wiener_nmap_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_nmap_kernel_t1024 : mgpu_frontend_wiener_nmap_kernel; }
+using FrontendWienerNmapCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo, MgpuWiener);
+inline FrontendWienerNmapCfoKernel fe_wiener_nmap_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_nmap_cfo_kernel_t1024 : mgpu_frontend_wiener_nmap_cfo_kernel; }
+
 // whether the caller wants a tap with a row per frame (a launch's kernel writes them from row 0: one launch per call then)
 inline bool wants_frame_taps(const MgpuTapsDev& t) { return t.grid || t.H || t.eq || t.syms || t.llr_demod || t.variance || t.agc_gain; }
 
@@ -371,7 +396,7 @@ void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int
                     const float* d_var, const float* d_snrvar, hipStream_t s);
 // The same launches without the timing events, as the ladder's retries run them: the kernel timings describe rung 0.
 // rect: null = rung 0 (the ladder's first window where it is not the context's own, else the default kernel); a retry's window otherwise,
-// (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included; with MGPU_CFO_PILOTS all of them are a CFO kernel)
+// (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included, with MGPU_DEMAP_NMAP a noise-map kernel; with MGPU_CFO_PILOTS all of them are a CFO kernel)
 // whose `frames` list names the frame each row of the compact outputs in io belongs to. rung: the ladder's rung the launch is (0 without a
 // ladder): its kind, which the ladder keeps, picks the LS or the Wiener forms.
 void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s, int rung = 0);

@@ -129,6 +129,16 @@ extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int
 extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi) {
     return (csi ? fe_carve_csi(G, nPilots, nBits, threads / 64) : fe_carve(G, nPilots, nBits, threads / 64)).total;
 }
+// The noise-map demapper's form (NMAP below; include/mercury_demapper.h MGPU_DEMAP_NMAP) is the CSI form with one more piece behind |h|^2: the
+// carrier sums S_c (64 doubles), the symbol sums U_s (Nsymb doubles) and the two scales a_c (64 floats) and b_s (Nsymb floats). Everything
+// before it in the work area is in use when it is written (Hp by the data cells, the three term arrays by their sums, |h|^2 being filled) and
+// the LLRs take the terms' place while a_c and b_s are read, so it is a piece of its own: 1,056 bytes in mode 8, where the FFT work areas
+// cover it, 1,344 more than the CSI carve in the BPSK modes (79,392 -> 80,736 bytes: still two workgroups per compute unit).
+__host__ __device__ inline size_t fe_nmap_bytes(int G) { return (size_t(64) * 12 + size_t(G / 50) * 12 + 15) & ~size_t(15); }
+__host__ __device__ inline FeCarve fe_carve_nmap(int G, int nPilots, int nBits, int FE_WAVES) {
+    return fe_carve_with(G, nPilots, nBits, FE_WAVES, fe_csi_var_bytes(nPilots) + ((size_t(4) * (G - nPilots) + 15) & ~size_t(15)) + fe_nmap_bytes(G));
+}
+extern "C" size_t mgpu_frontend_nmap_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve_nmap(G, nPilots, nBits, threads / 64).total; }
 // workgroups per compute unit the LDS lets a carve of `bytes` have, counted as fe_carve counts them (blocks of 1280 bytes, 256 of overhead)
 extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(160) * 1024 / ((bytes + 256 + 1279) / 1280 * 1280)); }
 
@@ -143,14 +153,19 @@ extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(16
 // and the estimate has not begun (>= four FFT work areas, 16 KB): no carve changes.
 // WIENER: the estimate at the pilots is the separable Wiener filter's (include/mercury_estimator.h MGPU_RUNG_WIENER) instead
 // of the window mean; `win` only carries the frame list. Its two passes live in Hp and the signed pilots' area: no carve changes.
-template <int FE_THREADS, bool RECT, bool CSI, bool CFO, bool WIENER>
+// NMAP (with CSI): the noise-map demapper (include/mercury_demapper.h MGPU_DEMAP_NMAP). The CSI form's pilot residuals are
+// also averaged per carrier and per symbol; the LLRs of a cell are scaled by a_c b_s |h|^2 with a_c = 1 / (sigma2 fc(c)), b_s = 1 / fs(s)
+// in place of |h|^2 / sigma2, fc and fs being those means over sigma2, 1 inside the dead band. Its scratch is a piece of the carve of its own.
+template <int FE_THREADS, bool RECT, bool CSI, bool CFO, bool WIENER, bool NMAP>
 __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
                                          float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out,
-                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi, const MgpuCfo& cfo, const MgpuWiener& wn) {
+                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi, const MgpuCfo& cfo, const MgpuWiener& wn,
+                                         const MgpuNmap& nm) {
+    static_assert(!NMAP || (CSI && RECT), "the noise-map demapper is a form of the channel-aware one");
     constexpr int FE_WAVES = FE_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int G = T.G, Nc = 50, Ns = T.Nsymb;
-    const FeCarve carve = CSI ? fe_carve_csi(G, T.nPilots, T.nBits, FE_WAVES) : fe_carve(G, T.nPilots, T.nBits, FE_WAVES);
+    const FeCarve carve = NMAP ? fe_carve_nmap(G, T.nPilots, T.nBits, FE_WAVES) : CSI ? fe_carve_csi(G, T.nPilots, T.nBits, FE_WAVES) : fe_carve(G, T.nPilots, T.nBits, FE_WAVES);
     c2* grid = reinterpret_cast<c2*>(smem);
     c2* Hp = grid + G;                                              // channel estimate at the pilots, pilot order; Hp and red are the FFT work area first
     c2* fftb = Hp;
@@ -164,6 +179,11 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
     // CSI: behind rsz, the terms of sigma2 in pilot order and |h|^2 per data cell in de-framed order
     [[maybe_unused]] double* red3 = reinterpret_cast<double*>(__builtin_assume_aligned(reinterpret_cast<unsigned char*>(red) + carve.rsz, 16));
     [[maybe_unused]] float* wf = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(red3) + fe_csi_var_bytes(T.nPilots));
+    // NMAP: behind |h|^2, the carrier sums, the symbol sums (their means later), the carrier scales, the symbol scales
+    [[maybe_unused]] double* nm_S = reinterpret_cast<double*>(__builtin_assume_aligned(reinterpret_cast<unsigned char*>(wf) + ((size_t(4) * (G - T.nPilots) + 15) & ~size_t(15)), 16));
+    [[maybe_unused]] double* nm_U = nm_S + 64;
+    [[maybe_unused]] float* nm_a = reinterpret_cast<float*>(nm_U + Ns);
+    [[maybe_unused]] float* nm_b = nm_a + 64;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int f = blockIdx.x;
@@ -497,6 +517,20 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
             scal[4] = var;
         }
     }
+    if constexpr (NMAP) {
+        // the same terms once more per carrier (ascending symbols) and per symbol (ascending carriers), a lane each on wavefronts 2 and 3 to 6
+        if (tid >= 128 && tid < 128 + Nc) {
+            const int c = tid - 128;
+            double acc = 0;
+            for (int q = nm.car_first[c]; q < nm.car_first[c + 1]; ++q) acc += red3[nm.car_list[q]];
+            nm_S[c] = acc;
+        } else if (tid >= 192 && tid < 192 + Ns) {
+            const int sy = tid - 192;
+            double acc = 0;
+            for (int p = nm.sym_first[sy]; p < nm.sym_first[sy + 1]; ++p) acc += red3[p];
+            nm_U[sy] = acc;
+        }
+    }
     for (;;) {
         int base = 0;
         if (lane == 0) base = atomicAdd(queue, 64);
@@ -505,6 +539,33 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         if (base + lane < T.nData) equalise_data(base + lane);
     }
     __syncthreads();
+    if constexpr (NMAP) {
+        // The factors (mgpu_host_demap_nmap is the normative statement): a mean over sigma2, exactly 1 when it is NaN, has no pilot, sigma2
+        // is 0 or not finite, or it lies inside the dead band. A retry computes its own map and does not write it out.
+        const double sigma2 = scal[4], band = nm.band;
+        const bool usable = sigma2 != 0 && fabs(sigma2) < __builtin_inf();
+        const bool report = win.frames == nullptr && nm.fc && f < nm.rows;
+        auto banded = [&](double v, int n) {
+            const double fr = v / sigma2;
+            return (usable && n > 0 && (fr > band || fr * band < 1)) ? fr : 1.0;
+        };
+        if (tid < Nc) {
+            const int lo = max(tid - nm.smooth, 0), hi = min(tid + nm.smooth, Nc - 1);
+            double sum = 0;
+            for (int c = lo; c <= hi; ++c) sum += nm_S[c];
+            const int n = int(nm.car_first[hi + 1]) - int(nm.car_first[lo]);
+            const double fc = banded(sum / double(n), n);
+            nm_a[tid] = 1.0f / float(sigma2 * fc);
+            if (report) nm.fc[size_t(f) * Nc + tid] = fc;
+        } else if (tid >= 64 && tid < 64 + Ns) {
+            const int sy = tid - 64;
+            const int n = int(nm.sym_first[sy + 1]) - int(nm.sym_first[sy]);
+            const double fs = banded(nm_U[sy] / double(n), n);
+            nm_b[sy] = 1.0f / float(fs);
+            if (report) nm.fs[size_t(f) * Ns + sy] = fs;
+        }
+        __syncthreads();
+    }
     c2* eq = grid;
     if (taps.eq) for (int c = tid; c < G; c += FE_THREADS) { taps.eq[(size_t(f) * G + c) * 2] = eq[c].re; taps.eq[(size_t(f) * G + c) * 2 + 1] = eq[c].im; }
     if (eqdata_out)   // de-framed equalised symbols, kept for the zero-forcing modes' post-decode SNR (ofdm_deframed_data)
@@ -518,7 +579,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 
     FE_STAMP();   // 6: equalise + variance done
     // ---- deframe + time/freq de-interleave + max-log demap -------------------------------------
-    const float inv_var = CSI ? 1 / float(scal[4]) : 1 / variance;
+    [[maybe_unused]] const float inv_var = CSI ? 1 / float(scal[4]) : 1 / variance;
     const int M = T.M, bps = T.bps;
     // cl_psk::demod (psk.cc:278-326): squared distance to every constellation point in double, narrowed to float; per bit the smallest
     // distance among the points with that bit set / clear; LLR = (d1 - d0) / variance in float. Specialised per constellation size so that
@@ -530,7 +591,9 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         constexpr int BPS = MM == 2 ? 1 : MM == 4 ? 2 : MM == 8 ? 3 : MM == 16 ? 4 : 5;
         for (int k = tid; k < T.nData; k += FE_THREADS) {
             const c2 s = eq[T.sym_src[k]];
-            const float scale = CSI ? inv_var * wf[csi.sym_data[k]] : inv_var;
+            float scale;
+            if constexpr (NMAP) { const int cell = T.sym_src[k], sy = cell / Nc; scale = (nm_a[cell - sy * Nc] * nm_b[sy]) * wf[csi.sym_data[k]]; }
+            else scale = CSI ? inv_var * wf[csi.sym_data[k]] : inv_var;
             if (taps.syms) { taps.syms[(size_t(f) * T.nData + k) * 2] = s.re; taps.syms[(size_t(f) * T.nData + k) * 2 + 1] = s.im; }
             float d0[BPS], d1[BPS];
 #pragma unroll
@@ -557,7 +620,9 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
     else
     for (int k = tid; k < T.nData; k += FE_THREADS) {
         const c2 s = eq[T.sym_src[k]];
-        const float scale = CSI ? inv_var * wf[csi.sym_data[k]] : inv_var;
+        float scale;
+        if constexpr (NMAP) { const int cell = T.sym_src[k], sy = cell / Nc; scale = (nm_a[cell - sy * Nc] * nm_b[sy]) * wf[csi.sym_data[k]]; }
+        else scale = CSI ? inv_var * wf[csi.sym_data[k]] : inv_var;
         if (taps.syms) { taps.syms[(size_t(f) * T.nData + k) * 2] = s.re; taps.syms[(size_t(f) * T.nData + k) * 2 + 1] = s.im; }
         float d0[5], d1[5];
 #pragma unroll
@@ -589,13 +654,13 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<512, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
+    fe_frame<512, false, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<1024, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
+    fe_frame<1024, false, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
 }
 
 // The same body with a rectangular LS window and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when
@@ -603,13 +668,13 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_rect_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<512, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
+    fe_frame<512, true, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<1024, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{});
+    fe_frame<1024, true, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
 }
 
 // The rectangular form with the channel-aware demapper (include/mercury_demapper.h): the plain span (the context's own window passed as a
@@ -617,13 +682,13 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<512, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{});
+    fe_frame<512, true, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<1024, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{});
+    fe_frame<1024, true, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
 }
 
 // The rectangular form with the residual carrier-offset stage (include/mercury_cfo.h), without and with the channel-aware demapper: the
@@ -632,27 +697,27 @@ extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_cfo_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
-    fe_frame<512, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{});
+    fe_frame<512, true, false, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{}, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_cfo_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
-    fe_frame<1024, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{});
+    fe_frame<1024, true, false, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{}, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_cfo_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
     MgpuCfo cfo) {
-    fe_frame<512, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{});
+    fe_frame<512, true, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_cfo_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
     MgpuCfo cfo) {
-    fe_frame<1024, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{});
+    fe_frame<1024, true, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, MgpuNmap{});
 }
 
 // The rectangular forms with the separable Wiener estimate in place of the window mean (include/mercury_estimator.h MGPU_RUNG_WIENER): a
@@ -661,54 +726,104 @@ extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_kernel
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win,
     MgpuWiener wn) {
-    fe_frame<512, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn);
+    fe_frame<512, true, false, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win,
     MgpuWiener wn) {
-    fe_frame<1024, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn);
+    fe_frame<1024, true, false, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_cfo_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo,
     MgpuWiener wn) {
-    fe_frame<512, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn);
+    fe_frame<512, true, false, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_cfo_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo,
     MgpuWiener wn) {
-    fe_frame<1024, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn);
+    fe_frame<1024, true, false, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_csi_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
     MgpuWiener wn) {
-    fe_frame<512, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn);
+    fe_frame<512, true, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_csi_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
     MgpuWiener wn) {
-    fe_frame<1024, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn);
+    fe_frame<1024, true, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_csi_cfo_kernel(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuCfo cfo,
     MgpuWiener wn) {
-    fe_frame<512, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn);
+    fe_frame<512, true, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, MgpuNmap{});
 }
 
 extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_csi_cfo_kernel_t1024(
     MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
     float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuCfo cfo,
     MgpuWiener wn) {
-    fe_frame<1024, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn);
+    fe_frame<1024, true, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, MgpuNmap{});
+}
+
+// The rectangular forms with the noise-map demapper (include/mercury_demapper.h MGPU_DEMAP_NMAP): the plain span, rung 0 and every retry of
+// an estimator ladder while the context's demapper is that one, for each combination of the carrier-offset setting and the rung's kind.
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_nmap_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm) {
+    fe_frame<512, true, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, nm);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_nmap_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm) {
+    fe_frame<1024, true, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, nm);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_nmap_cfo_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo) {
+    fe_frame<512, true, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, nm);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_nmap_cfo_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo) {
+    fe_frame<1024, true, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, nm);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_nmap_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuWiener wn) {
+    fe_frame<512, true, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, nm);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_nmap_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuWiener wn) {
+    fe_frame<1024, true, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, nm);
+}
+
+extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_nmap_cfo_kernel(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo, MgpuWiener wn) {
+    fe_frame<512, true, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, nm);
+}
+
+extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_nmap_cfo_kernel_t1024(
+    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
+    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo, MgpuWiener wn) {
+    fe_frame<1024, true, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, nm);
 }

@@ -37,7 +37,8 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
     }
     if (!rect && c->lad.n > 0 && !c->lad.rung0_is_default) rect = &c->lad.win[0];      // rung 0 of an estimator ladder with a window of its own
     const MgpuWiener* wiener = rung < c->lad.n && c->lad.kind[rung] == MGPU_RUNG_WIENER ? &c->lad.wiener[rung] : nullptr;   // a Wiener rung: `rect` carries the frame list alone
-    const bool csi = c->dmp.mode == MGPU_DEMAP_CSI;                                    // the channel-aware demapper: one kernel for every window
+    const bool nmap = c->dmp.mode == MGPU_DEMAP_NMAP;                                  // the noise-map demapper: a CSI form with a map of its own
+    const bool csi = c->dmp.mode == MGPU_DEMAP_CSI || nmap;                            // the channel-aware demapper: one kernel for every window
     if (csi && !rect) rect = &c->dmp.own;
     const bool cfo = c->cfo.mode == MGPU_CFO_PILOTS;                                   // residual carrier-offset correction: again one kernel for every window
     if (cfo && !rect) rect = &c->cfo.own;
@@ -54,8 +55,20 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
             const size_t row = size_t(io.frame0) + size_t(off);
             co.step_rows = cfo && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
             co.step = co.step_rows > 0 ? c->cfo.d_step + row : nullptr;
+            MgpuNmap nm = c->dmp.nmap;                           // the factors go to the frames' rows in the context's arrays, as far as they reach
+            nm.rows = nmap && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
+            nm.fc = nm.rows > 0 ? c->dmp.d_fc + row * size_t(t.Nc) : nullptr;
+            nm.fs = nm.rows > 0 ? c->dmp.d_fs + row * size_t(t.Nsymb) : nullptr;
             const size_t lds_wiener = wiener ? mgpu_frontend_wiener_lds_bytes(dev.G, dev.nPilots, dev.nBits, c->fe_threads, csi ? 1 : 0) : 0;
-            if (wiener && cfo && csi)
+            if (nmap && wiener && cfo)
+                hipLaunchKernelGGL(fe_wiener_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co, *wiener);
+            else if (nmap && wiener)
+                hipLaunchKernelGGL(fe_wiener_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, *wiener);
+            else if (nmap && cfo)
+                hipLaunchKernelGGL(fe_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co);
+            else if (nmap)
+                hipLaunchKernelGGL(fe_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm);
+            else if (wiener && cfo && csi)
                 hipLaunchKernelGGL(fe_wiener_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co, *wiener);
             else if (wiener && cfo)
                 hipLaunchKernelGGL(fe_wiener_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co, *wiener);

@@ -38,3 +38,16 @@ struct MgpuWiener {
                                 //              frequency class, row in it, its size n, the symbol's first pilot (a symbol's pilots are consecutive)
     const uint16_t* col_list;   // every carrier's pilots in ascending symbols, carrier after carrier
 };
+
+// What the noise-map demapper's front-end (frontend.hip NMAP; include/mercury_demapper.h MGPU_DEMAP_NMAP) needs beyond MgpuDev and MgpuCsi,
+// again an argument of its own; made at mgpu_set_demapper_ex (demapper.hip).
+struct MgpuNmap {
+    const uint16_t* car_list;   // every carrier's pilots as indices into pilot order, in ascending symbols, carrier after carrier
+    const uint16_t* car_first;  // [Nc + 1] a carrier's first entry in car_list; car_first[Nc] = nPilots
+    const uint16_t* sym_first;  // [Nsymb + 1] a symbol's first pilot in pilot order (its pilots are consecutive); sym_first[Nsymb] = nPilots
+    double band;                // the dead band, >= 1 (+Inf: no factor ever leaves it)
+    double* fc;                 // [rows][Nc] row of the launch's first frame in the context's factor arrays, or null
+    double* fs;                 // [rows][Nsymb]
+    int rows;                   // rows of fc / fs that may be written
+    int smooth;                 // carriers on either side that share a carrier's mean, 0..4
+};

@@ -269,8 +269,34 @@ def host_ls_estimate(cfg, grid, width, height, explicit=None):
 
 
 # ---- the channel-aware demapper (include/mercury_demapper.h) --------------------------------------------------------
-DEMAPPER_SYMBOLS = ["mgpu_set_demapper", "mgpu_get_demapper", "mgpu_host_demap_csi"]
-DEMAPPERS = {"maxlog": 0, "csi": 1}
+DEMAPPER_SYMBOLS = ["mgpu_set_demapper", "mgpu_get_demapper", "mgpu_host_demap_csi", "mgpu_set_demapper_ex", "mgpu_get_demapper_ex",
+                    "mgpu_get_noise_map", "mgpu_host_demap_nmap"]
+DEMAPPERS = {"maxlog": 0, "csi": 1, "nmap": 2}
+NMAP_DEFAULT = {"dead_band": 2.0, "smooth": 1}
+
+
+class DemapperParams(C.Structure):
+    """mgpu_demapper_params (include/mercury_demapper.h)"""
+    _fields_ = [("dead_band", C.c_double), ("smooth", C.c_int)]
+
+
+def parse_demapper(text):
+    """"maxlog", "csi", "nmap" or "nmap:band=2,smooth=1" (the tools' --demapper) -> (name, {dead_band, smooth} or None)"""
+    name, _, rest = str(text).partition(":")
+    if name not in DEMAPPERS or (rest and name != "nmap"):
+        raise ValueError("demapper: one of %s, nmap with :band=B,smooth=W" % ", ".join(DEMAPPERS))
+    if name != "nmap":
+        return name, None
+    prm = dict(NMAP_DEFAULT)
+    for item in filter(None, rest.split(",")):
+        key, _, value = item.partition("=")
+        if key == "band":
+            prm["dead_band"] = float(value)
+        elif key == "smooth":
+            prm["smooth"] = int(value)
+        else:
+            raise ValueError("demapper nmap: band=B and smooth=W are what it takes, not %r" % item)
+    return name, prm
 
 
 def _explicit_struct(explicit):
@@ -305,6 +331,33 @@ def host_demap_csi(cfg, grid, H, explicit=None):
     if rc != 0:
         raise MgpuError("mgpu_host_demap_csi failed (%d)" % rc, rc)
     return llr, float(sigma2.value)
+
+
+def host_demap_nmap(cfg, grid, H, dead_band=2.0, smooth=1, explicit=None):
+    """mgpu_host_demap_nmap, no GPU: as host_demap_csi with the noise map -> (llr_demod float32 [nBits], sigma2,
+    fc float64 [Nc], fs float64 [Nsymb]); the factors are those after the dead band."""
+    lib = load_library()
+    lib.mgpu_host_demap_nmap.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    g = np.ascontiguousarray(grid, np.complex128).ravel()
+    h = np.ascontiguousarray(H, np.complex128).ravel()
+    if g.size != h.size:
+        raise MgpuError("host_demap_nmap: grid and H must have one entry per cell")
+    xp = _explicit_struct(explicit)
+    ref = C.byref(xp) if xp is not None else None
+    prm = DemapperParams(float(dead_band), int(smooth))
+    # nBits and Nsymb of the (possibly explicit) geometry: the entries a call on an all-zero grid with H = 1 writes
+    count, rows = np.full(g.size * 5, np.nan, np.float32), np.full(g.size, np.nan, np.float64)
+    rc = lib.mgpu_host_demap_nmap(int(cfg), ref, _ptr(np.zeros_like(g)), _ptr(np.ones_like(g)), C.byref(prm), C.sizeof(prm), _ptr(count), None, None, _ptr(rows))
+    if rc != 0:
+        raise MgpuError("mgpu_host_demap_nmap failed (%d)" % rc, rc)
+    llr = np.zeros(int(np.count_nonzero(~np.isnan(count))), np.float32)
+    fs = np.zeros(int(np.count_nonzero(~np.isnan(rows))), np.float64)
+    fc = np.zeros(g.size // fs.size, np.float64)
+    sigma2 = C.c_double()
+    rc = lib.mgpu_host_demap_nmap(int(cfg), ref, _ptr(g), _ptr(h), C.byref(prm), C.sizeof(prm), _ptr(llr), C.byref(sigma2), _ptr(fc), _ptr(fs))
+    if rc != 0:
+        raise MgpuError("mgpu_host_demap_nmap failed (%d)" % rc, rc)
+    return llr, float(sigma2.value), fc, fs
 
 
 # ---- pilot-aided residual carrier-offset correction (include/mercury_cfo.h, DESIGN.md §3.10) ----------------------------------------
@@ -626,13 +679,42 @@ class RxPhy:
         return by, int(n.value)
 
     # ---- the channel-aware demapper (include/mercury_demapper.h) -------------------------------
-    def set_demapper(self, name):
+    def set_demapper(self, name, dead_band=None, smooth=None):
         """"maxlog": the reference's demapper (one variance per frame; the default). "csi": max-log LLRs weighted by |H|^2 per cell, in
-        every receive entry point of this context."""
-        if name not in DEMAPPERS:
+        every receive entry point of this context. "nmap": those divided by a noise factor per carrier and per symbol measured at the
+        pilots (dead_band, default 2.0: factors within [1 / dead_band, dead_band] are 1; smooth, default 1: carriers on either side that
+        share a carrier's mean). name may also be the tools' form, "nmap:band=2,smooth=1" (parse_demapper)."""
+        try:
+            name, spec = parse_demapper(name)
+        except ValueError:
             raise MgpuError("demapper must be one of %s" % sorted(DEMAPPERS))
-        self.lib.mgpu_set_demapper.argtypes = [C.c_void_p, C.c_int]
-        self._ck(self.lib.mgpu_set_demapper(self.h, DEMAPPERS[name]))
+        if spec and spec != NMAP_DEFAULT:
+            dead_band = spec["dead_band"] if dead_band is None else dead_band
+            smooth = spec["smooth"] if smooth is None else smooth
+        if dead_band is None and smooth is None:
+            self.lib.mgpu_set_demapper.argtypes = [C.c_void_p, C.c_int]
+            self._ck(self.lib.mgpu_set_demapper(self.h, DEMAPPERS[name]))
+            return
+        prm = DemapperParams(float(NMAP_DEFAULT["dead_band"] if dead_band is None else dead_band), int(NMAP_DEFAULT["smooth"] if smooth is None else smooth))
+        self.lib.mgpu_set_demapper_ex.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        self._ck(self.lib.mgpu_set_demapper_ex(self.h, DEMAPPERS[name], C.byref(prm), C.sizeof(prm)))
+
+    @property
+    def demapper_ex(self):
+        """(name, {dead_band, smooth}): the demapper and the noise map's parameters as last set (the defaults before)"""
+        v, prm = C.c_int(), DemapperParams()
+        self.lib.mgpu_get_demapper_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        self._ck(self.lib.mgpu_get_demapper_ex(self.h, C.byref(v), C.byref(prm), C.sizeof(prm)))
+        return {n: k for k, n in DEMAPPERS.items()}[v.value], {"dead_band": prm.dead_band, "smooth": prm.smooth}
+
+    def noise_map(self, first=0, count=None):
+        """(fc float64 [count, Nc], fs float64 [count, Nsymb]): the noise factors, after the dead band, of rows first .. first + count - 1
+        (default: to max_batch) of the last call that ran with the "nmap" demapper; rung 0's under an estimator ladder."""
+        count = self.max_batch - int(first) if count is None else int(count)
+        fc, fs = np.zeros((count, self.Nc), np.float64), np.zeros((count, self.Nsymb), np.float64)
+        self.lib.mgpu_get_noise_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        self._ck(self.lib.mgpu_get_noise_map(self.h, int(first), count, _ptr(fc), _ptr(fs)))
+        return fc, fs
 
     @property
     def demapper(self):

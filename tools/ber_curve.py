@@ -16,7 +16,7 @@ line then carries the frames each rung decoded.
 and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_per_point counts payloads, Es/N0 is per branch.
 --points LO:HI:STEP (baseband form): the Es/N0 points instead of the reference's 25.
 --demapper csi (any form, with any of the above): LLRs weighted by |H|^2 per cell (include/mercury_demapper.h) instead of the reference's
-demapper.
+demapper; --demapper nmap[:band=2,smooth=1]: those divided by a noise factor per carrier and per symbol measured at the pilots.
 --cfo pilots (any form, with any of the above): every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)."""
 import json
 import os
@@ -125,8 +125,10 @@ def main():
     diversity = _option(argv, "--diversity")
     points = _option(argv, "--points")
     DEMAPPER[0] = _option(argv, "--demapper") or "maxlog"
-    if DEMAPPER[0] not in pl.DEMAPPERS:
-        sys.exit("--demapper: one of " + ", ".join(pl.DEMAPPERS))
+    try:
+        pl.parse_demapper(DEMAPPER[0])
+    except ValueError as e:
+        sys.exit("--" + str(e))
     CFO[0] = _option(argv, "--cfo") or "off"
     if CFO[0] not in pl.CFO_MODES:
         sys.exit("--cfo: one of " + ", ".join(pl.CFO_MODES))

@@ -35,6 +35,16 @@ def ladder(text, S):
     return pts, np.array([pts[s * len(pts) // S] for s in range(S)])
 
 
+def _demapper(text):
+    """--demapper: the spec as RxPhy.set_demapper takes it, checked by the library's one parser"""
+    from mercury_amd import parse_demapper
+    try:
+        parse_demapper(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def carrier_of(info):
     return 48000.0 / 4 * info.Nc / info.Nfft / 2 + 300          # physical_config.cc:84: bandwidth / 2 + 300
 
@@ -164,7 +174,8 @@ def main():
     ap.add_argument("--max-batch", type=int, default=0, help="receive_byte windows per call (0: the number of links)")
     ap.add_argument("--power", type=float, default=1.0, help="output_power_watt (1: Es/N0 is the signal's own, BER_PLOT_passband's convention)")
     ap.add_argument("--ladder", default="", help="estimator ladder, e.g. 21x21,5x21 (carriers x symbols) or 21x21,wiener (include/mercury_estimator.h)")
-    ap.add_argument("--demapper", default="maxlog", choices=["maxlog", "csi"], help="csi: LLRs weighted by |H|^2 per cell (include/mercury_demapper.h)")
+    ap.add_argument("--demapper", default="maxlog", type=_demapper,
+                    help="csi: LLRs weighted by |H|^2 per cell; nmap[:band=2,smooth=1]: those divided by a noise factor per carrier and per symbol (include/mercury_demapper.h)")
     ap.add_argument("--cfo", default="off", choices=["off", "pilots"], help="pilots: every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--baseline", action="store_true")
