@@ -16,6 +16,7 @@
 #include "../../include/mercury_rxloop.h"
 #include "../../include/mercury_channel.h"
 #include "../../include/mercury_estimator.h"
+#include "../../include/mercury_wiener_bank.h"
 #include "../../include/mercury_diversity.h"
 #include "../../include/mercury_demapper.h"
 #include "../../include/mercury_cfo.h"
@@ -185,6 +186,17 @@ struct Ladder {
     DevArray<double> wiener_A[MGPU_LADDER_MAX], wiener_B[MGPU_LADDER_MAX];
     DevArray<int> wiener_off[MGPU_LADDER_MAX];      // a_off, then b_off
     DevArray<uint16_t> wiener_idx[MGPU_LADDER_MAX]; // pilot, then col_list
+    // a Wiener rung's bank (include/mercury_wiener_bank.h): with n > 0 wiener[r] reads these tables instead of wiener_A / wiener_B
+    struct Bank {
+        int n = 0;
+        mgpu_wiener_bank_entry e[MGPU_WIENER_BANK_MAX]{};   // the thresholds as applied
+        DevArray<double> A, B;                      // the designs' blocks one after the other
+        DevArray<MgpuWienerBank> arg;               // wiener[r].bank: strides, pair lists, the entries' test constants
+        DevArray<uint16_t> idx;                     // pair, then sym_first
+        int n1 = 0, n2 = 0;
+    } bank[MGPU_LADDER_MAX];
+    DevArray<int> d_choice;                         // [max_batch] rung 0's choice per frame of the last call, by the frame's row
+    DevArray<double> d_corr;                        // [max_batch][4] the sums it chose from
     DevArray<int> d_rung;                           // [max_batch] winning rung per frame of the last call, -1 = none
     DevArray<unsigned long long> d_counters;        // [MGPU_LADDER_MAX + 1] frames decoded by rung r; frames seen
     // a retry's compact workspaces, [max_batch] each, created with the first ladder of more than one rung

@@ -293,11 +293,58 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
             yp[p] = type[q] < 0 ? c2{-y.re, -y.im} : y;
         }
         __syncthreads();
+        const double* __restrict__ wA = wn.A;
+        const double* __restrict__ wB = wn.B;
+        if (wn.n_designs > 1) {                                     // (uniform) a bank: the frame chooses its design (include/mercury_wiener_bank.h)
+            // One lane per symbol adds the terms conj(yp[a]) yp[b] of its symbol's 1-pairs and 2-pairs in ascending a; its four sums go to
+            // Hp, which is free until the time pass. Lanes 0..3 of the first wavefront then add the symbols' sums in ascending symbols, one
+            // component each, and lane 0 applies the tests: the same terms in the same order as mgpu_host_wiener_select.
+            const MgpuWienerBank& bk = *wn.bank;
+            double* part = reinterpret_cast<double*>(Hp);           // [Ns][4]: 32 Ns <= 16 nPilots bytes (checked where the bank is set)
+            for (int s = tid; s < Ns; s += FE_THREADS) {
+                double r1r = 0, r1i = 0, r2r = 0, r2i = 0;
+                for (int p = bk.sym_first[s], p1 = bk.sym_first[s + 1]; p < p1; ++p) {
+                    const unsigned fl = bk.pair[p];
+                    const c2 a = yp[p];
+                    if (fl & 1u) { const c2 b = yp[p + 1]; r1r += (a.re * b.re) + (a.im * b.im); r1i += (a.re * b.im) - (a.im * b.re); }
+                    if (fl & 2u) { const c2 b = yp[p + 2]; r2r += (a.re * b.re) + (a.im * b.im); r2i += (a.re * b.im) - (a.im * b.re); }
+                }
+                part[4 * s] = r1r; part[4 * s + 1] = r1i; part[4 * s + 2] = r2r; part[4 * s + 3] = r2i;
+            }
+            __syncthreads();
+            if (wave == 0) {
+                double acc = 0;
+                if (lane < 4) for (int s = 0; s < Ns; ++s) acc += part[4 * s + lane];
+                const double R1r = __shfl(acc, 0), R1i = __shfl(acc, 1), R2r = __shfl(acc, 2), R2i = __shfl(acc, 3);
+                if (lane == 0) {
+                    const double q2 = (R2r * R2r + R2i * R2i) * bk.n1sq, q1 = (R1r * R1r + R1i * R1i) * bk.n2sq;
+                    int ch = wn.n_designs - 1;                      // the fallback; the first eligible entry in bank order otherwise
+                    for (int d = wn.n_designs - 2; d >= 0; --d) {
+                        const double rho2 = bk.sel[d][0], ur = bk.sel[d][1], ui = bk.sel[d][2], t = bk.sel[d][3];
+                        bool ok = q2 >= rho2 * q1;                  // every comparison fails on a NaN
+                        if (t >= 0) {
+                            const double zr = R1r * ur + R1i * ui, zi = R1i * ur - R1r * ui;
+                            ok = ok && zr > 0 && fabs(zi) <= t * zr;
+                        }
+                        if (ok) ch = d;
+                    }
+                    scal[7] = double(ch);
+                    if (wn.choice && f < wn.rows) {                 // rung 0 alone: a retry measures the same and does not write it out
+                        wn.choice[f] = ch;
+                        wn.corr[4 * size_t(f)] = R1r; wn.corr[4 * size_t(f) + 1] = R1i; wn.corr[4 * size_t(f) + 2] = R2r; wn.corr[4 * size_t(f) + 3] = R2i;
+                    }
+                }
+            }
+            __syncthreads();
+            const int ch = __builtin_amdgcn_readfirstlane(int(scal[7]));      // the same in every lane: the table bases stay scalar
+            wA += size_t(ch) * size_t(bk.a_stride);
+            wB += size_t(ch) * size_t(bk.b_stride) * 2;
+        }
         const uint4* __restrict__ wpilot = reinterpret_cast<const uint4*>(wn.pilot);
         for (int p = tid; p < T.nPilots; p += FE_THREADS) {
             const uint4 q = wpilot[p];
             const int n = int(q.y & 0xffffu);
-            const double* __restrict__ a = wn.A + wn.a_off[q.x & 0xffffu] + int(q.x >> 16) * n;
+            const double* __restrict__ a = wA + wn.a_off[q.x & 0xffffu] + int(q.x >> 16) * n;
             const uint16_t* __restrict__ list = wn.col_list + (q.y >> 16);
             double hr = 0, hi = 0;
             for (int k = 0; k < n; ++k) {
@@ -310,7 +357,7 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
         for (int p = tid; p < T.nPilots; p += FE_THREADS) {
             const uint4 q = wpilot[p];
             const int n = int(q.w & 0xffffu);
-            const c2* __restrict__ b = reinterpret_cast<const c2*>(wn.B) + wn.b_off[q.z & 0xffffu] + int(q.z >> 16) * n;
+            const c2* __restrict__ b = reinterpret_cast<const c2*>(wB) + wn.b_off[q.z & 0xffffu] + int(q.z >> 16) * n;
             const c2* t = Hp + (q.w >> 16);
             double hr = 0, hi = 0;
             for (int m = 0; m < n; ++m) {

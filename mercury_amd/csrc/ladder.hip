@@ -2,6 +2,7 @@
 // the host twins of the LS and of the Wiener estimate. The retry itself is the rectangular front-end (frontend.hip; launched by launch.hip's front-end core)
 // on a frame list and the unchanged decoder on compact buffers.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -184,6 +185,7 @@ int mgpu_set_estimator_ladder_ex(mgpu_ctx* c, const mgpu_estimator_rung* rungs, 
             wiener[r].A = wA[r]; wiener[r].B = wB[r];
             wiener[r].a_off = woff[r]; wiener[r].b_off = woff[r] + b_off;
             wiener[r].pilot = widx[r]; wiener[r].col_list = widx[r] + nP * 8;
+            wiener[r].n_designs = 1;
         }
         const size_t B = size_t(c->max_batch);
         Ladder& L = c->lad;
@@ -222,6 +224,7 @@ int mgpu_set_estimator_ladder_ex(mgpu_ctx* c, const mgpu_estimator_rung* rungs, 
             L.design[r] = r < n_rungs && L.kind[r] == MGPU_RUNG_WIENER ? rungs[r].design : mgpu_wiener_design{};
             L.wiener_A[r] = std::move(wA[r]); L.wiener_B[r] = std::move(wB[r]); L.wiener_off[r] = std::move(woff[r]); L.wiener_idx[r] = std::move(widx[r]);
             L.wiener[r] = wiener[r];
+            L.bank[r] = Ladder::Bank{};              // a new ladder carries no bank (include/mercury_wiener_bank.h)
             if (r >= n_rungs || L.kind[r] == MGPU_RUNG_WIENER) continue;
             const int hw_f = win[r].width / 2;
             L.win[r].weight = L.weight[r];
@@ -256,6 +259,99 @@ int mgpu_get_estimator_ladder_ex(mgpu_ctx* c, mgpu_estimator_rung* rungs, int* n
     *n_rungs = c->lad.n;
     for (int r = 0; r < c->lad.n; ++r) rungs[r] = mgpu_estimator_rung{c->lad.kind[r], c->lad.rung[r], c->lad.design[r]};
     return MGPU_OK;
+}
+
+// ---- a Wiener rung's bank of designs (include/mercury_wiener_bank.h) ----
+namespace {
+// the bank as wiener_tables.cpp takes it; throws std::invalid_argument where it is refused
+mgpu::WienerBankRule bank_rule(const std::vector<uint8_t>& cell_type, int Nsymb, int Nc, const mgpu_wiener_bank_entry* e, int n, mgpu::WienerDesign* designs) {
+    double rho[MGPU_WIENER_BANK_MAX]{};
+    need(n >= 1 && n <= MGPU_WIENER_BANK_MAX && e, "Wiener bank: 1..MGPU_WIENER_BANK_MAX entries");
+    for (int d = 0; d < n; ++d) {
+        designs[d] = mgpu::WienerDesign{e[d].design.tau_min_us, e[d].design.tau_max_us, e[d].design.doppler_hz, e[d].design.snr_db};
+        rho[d] = e[d].rho_min;
+    }
+    return mgpu::build_wiener_bank_rule(cell_type, Nsymb, Nc, designs, rho, n);
+}
+}  // namespace
+
+int mgpu_set_wiener_bank(mgpu_ctx* c, int rung, const mgpu_wiener_bank_entry* e, int n, size_t entry_size) {
+    if (!c) return MGPU_ERR_ARG;
+    if (entry_size != sizeof(mgpu_wiener_bank_entry)) {
+        c->err = "Wiener bank: entry_size is not this library's sizeof(mgpu_wiener_bank_entry)";
+        return MGPU_ERR_ARG;
+    }
+    return guard(c, [&] {
+        const auto& t = c->tab;
+        Ladder& L = c->lad;
+        need(rung >= 0 && rung < L.n && L.kind[rung] == MGPU_RUNG_WIENER, "Wiener bank: the ladder in force has no Wiener rung of that number");
+        need(n >= 0 && n <= MGPU_WIENER_BANK_MAX && (e || n == 0), "Wiener bank: 0..MGPU_WIENER_BANK_MAX entries");
+        // everything that can fail comes before the context changes
+        Ladder::Bank nb;
+        MgpuWiener w = L.wiener[rung];
+        w.A = L.wiener_A[rung]; w.B = L.wiener_B[rung];
+        w.n_designs = 1; w.bank = nullptr;
+        if (n > 0) {
+            mgpu::WienerDesign designs[MGPU_WIENER_BANK_MAX];
+            const mgpu::WienerBankRule rule = bank_rule(t.cell_type, t.Nsymb, t.Nc, e, n, designs);
+            need(t.nPilots >= 2 * t.Nsymb, "Wiener bank: the symbols' partial sums do not fit the pilots' area");
+            std::vector<double> A, B;
+            size_t a_stride = 0, b_stride = 0;
+            for (int d = 0; d < n; ++d) {
+                const mgpu::WienerTables wt = mgpu::build_wiener_tables(t.cell_type, t.Nsymb, t.Nc, t.pilot_boost, designs[d]);
+                const size_t a0 = A.size(), b0 = B.size();
+                for (const auto& m : wt.A) A.insert(A.end(), m.begin(), m.end());
+                for (const auto& m : wt.B) for (const mgpu::Cplx& v : m) { B.push_back(v.re); B.push_back(v.im); }
+                if (d == 0) { a_stride = A.size(); b_stride = B.size() / 2; }
+                need(A.size() - a0 == a_stride && B.size() - b0 == 2 * b_stride, "Wiener bank: the designs' tables differ in shape");
+            }
+            std::vector<uint16_t> idx = rule.pair;
+            idx.insert(idx.end(), rule.sym_first.begin(), rule.sym_first.end());
+            nb.n = n; nb.n1 = rule.n1; nb.n2 = rule.n2;
+            for (int d = 0; d < n; ++d) { nb.e[d] = e[d]; if (d + 1 < n) nb.e[d].rho_min = rule.rho_min[size_t(d)]; }
+            nb.A = upload(A); nb.B = upload(B); nb.idx = upload(idx);
+            std::vector<MgpuWienerBank> arg(1);
+            arg[0].a_stride = int(a_stride); arg[0].b_stride = int(b_stride);
+            arg[0].pair = nb.idx; arg[0].sym_first = nb.idx + rule.pair.size();
+            arg[0].n1sq = double(rule.n1) * double(rule.n1); arg[0].n2sq = double(rule.n2) * double(rule.n2);
+            for (size_t i = 0; i < sizeof(arg[0].sel) / sizeof(double); ++i) arg[0].sel[i / 4][i % 4] = i < rule.sel.size() ? rule.sel[i] : 0.0;
+            nb.arg = upload(arg);
+            w.A = nb.A; w.B = nb.B;
+            w.n_designs = n; w.bank = nb.arg;
+        }
+        const size_t B = size_t(c->max_batch);
+        HIPCK(hipStreamSynchronize(c->stream));
+        if (L.done_recorded) HIPCK(hipEventSynchronize(L.done));
+        if (n > 0 && rung == 0) {
+            L.d_choice.grow(B * sizeof(int)); L.d_corr.grow(B * 4 * sizeof(double));
+            HIPCK(hipMemset(L.d_choice, 0, B * sizeof(int)));
+            HIPCK(hipMemset(L.d_corr, 0, B * 4 * sizeof(double)));
+        }
+        L.bank[rung] = std::move(nb);
+        L.wiener[rung] = w;
+    });
+}
+
+int mgpu_get_wiener_bank(mgpu_ctx* c, int rung, mgpu_wiener_bank_entry* e, int* n, size_t entry_size) {
+    if (!c || !n || !e || entry_size != sizeof(mgpu_wiener_bank_entry)) return MGPU_ERR_ARG;
+    if (rung < 0 || rung >= c->lad.n || c->lad.kind[rung] != MGPU_RUNG_WIENER) return MGPU_ERR_ARG;
+    *n = c->lad.bank[rung].n;
+    for (int d = 0; d < *n; ++d) e[d] = c->lad.bank[rung].e[d];
+    return MGPU_OK;
+}
+
+int mgpu_get_wiener_choice(mgpu_ctx* c, int first, int count, int* design, double* corr, int* n1, int* n2) {
+    if (!c) return MGPU_ERR_ARG;
+    return guard(c, [&] {
+        const Ladder& L = c->lad;
+        need(L.n > 0 && L.kind[0] == MGPU_RUNG_WIENER && L.bank[0].n > 0, "rung 0 has no Wiener bank");
+        need(first >= 0 && count >= 0 && size_t(first) + size_t(count) <= size_t(c->max_batch), "bad argument (first + count must be <= max_batch)");
+        HIPCK(hipStreamSynchronize(c->stream));
+        if (design && count) HIPCK(hipMemcpy(design, L.d_choice + first, size_t(count) * sizeof(int), hipMemcpyDeviceToHost));
+        if (corr && count) HIPCK(hipMemcpy(corr, L.d_corr + size_t(first) * 4, size_t(count) * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        if (n1) *n1 = L.bank[0].n1;
+        if (n2) *n2 = L.bank[0].n2;
+    });
 }
 
 int mgpu_estimator_rungs_last(mgpu_ctx* c, int* rung, int F) {
@@ -430,6 +526,86 @@ int mgpu_host_wiener_estimate(int cfg, const mgpu_explicit_params* p, const mgpu
                 H[2 * list[i]] = hr; H[2 * list[i] + 1] = hi;
             }
         }
+        return MGPU_OK;
+    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+}
+
+namespace {
+// the mode's geometry for the bank's twins; null with *rc set where the mode is refused
+std::shared_ptr<const TwinGeometry> bank_geometry(int cfg, const mgpu_explicit_params* p, int* rc) {
+    mgpu::ExplicitParams xp;
+    std::string err;
+    *rc = MGPU_ERR_ARG;
+    if (!explicit_params_from(p, xp, err, rc)) return nullptr;
+    xp.ls_window = mgpu::ExplicitParams().ls_window;
+    std::shared_ptr<const TwinGeometry> geometry = twin_geometry(cfg, xp);
+    if (!geometry->ls) { *rc = MGPU_ERR_UNSUPPORTED; return nullptr; }
+    *rc = MGPU_OK;
+    return geometry;
+}
+}  // namespace
+
+int mgpu_host_wiener_select(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_bank_entry* e, int n, size_t entry_size, const double* grid,
+                            int* design, double corr[4], int* n1, int* n2) {
+    if (!grid || !e || entry_size != sizeof(mgpu_wiener_bank_entry) || n < 1 || n > MGPU_WIENER_BANK_MAX) return MGPU_ERR_ARG;
+    try {
+        int rc = MGPU_OK;
+        const std::shared_ptr<const TwinGeometry> geometry = bank_geometry(cfg, p, &rc);
+        if (!geometry) return rc;
+        const TwinGeometry& t = *geometry;
+        mgpu::WienerDesign designs[MGPU_WIENER_BANK_MAX];
+        const mgpu::WienerBankRule rule = bank_rule(t.cell_type, t.Nsymb, t.Nc, e, n, designs);
+        const size_t nP = rule.pair.size();
+        std::vector<double> yp(2 * nP + 4, 0.0);
+        size_t pilot = 0;
+        for (int q = 0; q < t.Nsymb * t.Nc; ++q) {      // the pilots times their sign, in pilot order
+            if (!t.cell_type[size_t(q)]) continue;
+            const bool neg = t.pilot_val[size_t(q)] < 0;
+            yp[2 * pilot] = neg ? -grid[2 * q] : grid[2 * q];
+            yp[2 * pilot + 1] = neg ? -grid[2 * q + 1] : grid[2 * q + 1];
+            ++pilot;
+        }
+        double R1r = 0, R1i = 0, R2r = 0, R2i = 0;
+        for (int sy = 0; sy < t.Nsymb; ++sy) {          // a symbol's terms in ascending a, then the symbols in ascending order
+            double r1r = 0, r1i = 0, r2r = 0, r2i = 0;
+            for (size_t a = rule.sym_first[size_t(sy)]; a < rule.sym_first[size_t(sy) + 1]; ++a) {
+                const double ar = yp[2 * a], ai = yp[2 * a + 1];
+                if (rule.pair[a] & 1) { const double br = yp[2 * a + 2], bi = yp[2 * a + 3]; r1r += (ar * br) + (ai * bi); r1i += (ar * bi) - (ai * br); }
+                if (rule.pair[a] & 2) { const double br = yp[2 * a + 4], bi = yp[2 * a + 5]; r2r += (ar * br) + (ai * bi); r2i += (ar * bi) - (ai * br); }
+            }
+            R1r += r1r; R1i += r1i; R2r += r2r; R2i += r2i;
+        }
+        const double n1sq = double(rule.n1) * double(rule.n1), n2sq = double(rule.n2) * double(rule.n2);
+        const double q2 = (R2r * R2r + R2i * R2i) * n1sq, q1 = (R1r * R1r + R1i * R1i) * n2sq;
+        int ch = n - 1;                                 // the fallback; the first eligible entry in bank order otherwise
+        for (int d = n - 2; d >= 0; --d) {
+            const double rho2 = rule.sel[size_t(4) * d], ur = rule.sel[size_t(4) * d + 1], ui = rule.sel[size_t(4) * d + 2], tn = rule.sel[size_t(4) * d + 3];
+            bool ok = q2 >= rho2 * q1;                  // every comparison fails on a NaN
+            if (tn >= 0) {
+                const double zr = R1r * ur + R1i * ui, zi = R1i * ur - R1r * ui;
+                ok = ok && zr > 0 && std::fabs(zi) <= tn * zr;
+            }
+            if (ok) ch = d;
+        }
+        if (design) *design = ch;
+        if (corr) { corr[0] = R1r; corr[1] = R1i; corr[2] = R2r; corr[3] = R2i; }
+        if (n1) *n1 = rule.n1;
+        if (n2) *n2 = rule.n2;
+        return MGPU_OK;
+    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+}
+
+int mgpu_host_wiener_bank_thresholds(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_bank_entry* e, int n, size_t entry_size, double* rho_min,
+                                     int* pilot_spacing) {
+    if (!e || entry_size != sizeof(mgpu_wiener_bank_entry) || n < 1 || n > MGPU_WIENER_BANK_MAX) return MGPU_ERR_ARG;
+    try {
+        int rc = MGPU_OK;
+        const std::shared_ptr<const TwinGeometry> geometry = bank_geometry(cfg, p, &rc);
+        if (!geometry) return rc;
+        mgpu::WienerDesign designs[MGPU_WIENER_BANK_MAX];
+        const mgpu::WienerBankRule rule = bank_rule(geometry->cell_type, geometry->Nsymb, geometry->Nc, e, n, designs);
+        if (rho_min) std::copy(rule.rho_min.begin(), rule.rho_min.end(), rho_min);
+        if (pilot_spacing) *pilot_spacing = rule.s;
         return MGPU_OK;
     } catch (const std::exception&) { return MGPU_ERR_ARG; }
 }

@@ -60,23 +60,27 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
             nm.fc = nm.rows > 0 ? c->dmp.d_fc + row * size_t(t.Nc) : nullptr;
             nm.fs = nm.rows > 0 ? c->dmp.d_fs + row * size_t(t.Nsymb) : nullptr;
             const size_t lds_wiener = wiener ? mgpu_frontend_wiener_lds_bytes(dev.G, dev.nPilots, dev.nBits, c->fe_threads, csi ? 1 : 0) : 0;
+            MgpuWiener wv = wiener ? *wiener : MgpuWiener{};     // a bank's choices go to the frames' rows in the context's arrays, from rung 0 alone
+            wv.rows = wiener && wv.n_designs > 1 && rung == 0 && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
+            wv.choice = wv.rows > 0 ? c->lad.d_choice + row : nullptr;
+            wv.corr = wv.rows > 0 ? c->lad.d_corr + row * 4 : nullptr;
             if (nmap && wiener && cfo)
-                hipLaunchKernelGGL(fe_wiener_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co, *wiener);
+                hipLaunchKernelGGL(fe_wiener_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co, wv);
             else if (nmap && wiener)
-                hipLaunchKernelGGL(fe_wiener_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, *wiener);
+                hipLaunchKernelGGL(fe_wiener_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, wv);
             else if (nmap && cfo)
                 hipLaunchKernelGGL(fe_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co);
             else if (nmap)
                 hipLaunchKernelGGL(fe_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm);
             else if (wiener && cfo && csi)
-                hipLaunchKernelGGL(fe_wiener_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co, *wiener);
+                hipLaunchKernelGGL(fe_wiener_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co, wv);
             else if (wiener && cfo)
-                hipLaunchKernelGGL(fe_wiener_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co, *wiener);
+                hipLaunchKernelGGL(fe_wiener_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co, wv);
             else if (wiener && csi)
-                hipLaunchKernelGGL(fe_wiener_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, *wiener);
+                hipLaunchKernelGGL(fe_wiener_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, wv);
             else if (wiener)
                 hipLaunchKernelGGL(fe_wiener_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar,
-                                   static_cast<double*>(nullptr), tp, w, *wiener);
+                                   static_cast<double*>(nullptr), tp, w, wv);
             else if (cfo && csi)
                 hipLaunchKernelGGL(fe_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co);
             else if (cfo)

@@ -29,6 +29,7 @@ struct MgpuCfo {
 // What the separable Wiener estimator (frontend.hip WIENER; include/mercury_estimator.h MGPU_RUNG_WIENER) needs beyond MgpuDev, again an
 // argument of its own; made at mgpu_set_estimator_ladder_ex (ladder.hip) from wiener_tables.cpp's tables. The matrices stay in global
 // memory: a few per mode, shared by every workgroup.
+struct MgpuWienerBank;
 struct MgpuWiener {
     const double* A;            // the time classes' matrices one after the other, each row-major n x n
     const double* B;            // the frequency classes' matrices one after the other, each row-major n x n complex (re, im)
@@ -37,6 +38,20 @@ struct MgpuWiener {
     const uint16_t* pilot;      // [nPilots][8] time class, row in it, its size n, first entry of the carrier's list in col_list;
                                 //              frequency class, row in it, its size n, the symbol's first pilot (a symbol's pilots are consecutive)
     const uint16_t* col_list;   // every carrier's pilots in ascending symbols, carrier after carrier
+    // A bank of designs (include/mercury_wiener_bank.h; made at mgpu_set_wiener_bank): the workgroup chooses one per frame. The class
+    // structure depends on the geometry alone, so a_off, b_off, pilot and col_list above are the same for every design.
+    int n_designs;              // 0 or 1: A and B are the one design's and nothing below is read
+    int rows;                   // rows of choice / corr that may be written
+    const MgpuWienerBank* bank; // in device memory: what only the choice reads stays out of the kernel's arguments
+    int* choice;                // row of the launch's first frame in the context's arrays, or null (a retry, a rung behind rung 0)
+    double* corr;               // [rows][4] R1r R1i R2r R2i
+};
+struct MgpuWienerBank {
+    int a_stride, b_stride;     // from one design's block to the next: doubles in A, complex in B
+    const uint16_t* pair;       // [nPilots] bit 0: pilots p and p + 1 are a 1-pair, bit 1: p and p + 2 are a 2-pair
+    const uint16_t* sym_first;  // [Nsymb + 1] a symbol's first pilot in pilot order; sym_first[Nsymb] = nPilots
+    double n1sq, n2sq;          // double(n1) double(n1), double(n2) double(n2)
+    double sel[3][4];           // per entry but the last: rho_min^2, u.re, u.im, t (< 0: no centroid test)
 };
 
 // What the noise-map demapper's front-end (frontend.hip NMAP; include/mercury_demapper.h MGPU_DEMAP_NMAP) needs beyond MgpuDev and MgpuCsi,

@@ -138,6 +138,19 @@ struct WienerTables {
 bool wiener_design_ok(const WienerDesign& d);                  // tau_max > tau_min, doppler >= 0, snr_db in [-20, 40], all finite
 WienerTables build_wiener_tables(const std::vector<uint8_t>& cell_type, int Nsymb, int Nc, double pilot_boost, const WienerDesign& d);
 
+// What choosing a Wiener design per frame (include/mercury_wiener_bank.h) needs of the geometry and of a bank of n designs: the pilot
+// spacing s, the pair lists as one flag word per pilot (a symbol's pilots are consecutive in pilot order, so the partner of pilot p is
+// p + 1 or p + 2), and per entry but the last the constants of its two tests.
+struct WienerBankRule {
+    int s = 0, n1 = 0, n2 = 0;                      // pilot spacing in bins; 1-pairs and 2-pairs per frame
+    std::vector<uint16_t> pair;                     // [nPilots] bit 0: (p, p + 1) is a 1-pair, bit 1: (p, p + 2) is a 2-pair
+    std::vector<uint16_t> sym_first;                // [Nsymb + 1] a symbol's first pilot; sym_first[Nsymb] = nPilots
+    std::vector<double> rho_min;                    // [n - 1] the thresholds as applied
+    std::vector<double> sel;                        // [n - 1][4] rho_min^2, u.re, u.im, t (-1: the centroid test is waived)
+};
+// throws std::invalid_argument with the reason where the bank is refused (widths not ascending, a design out of range, a bad rho_min)
+WienerBankRule build_wiener_bank_rule(const std::vector<uint8_t>& cell_type, int Nsymb, int Nc, const WienerDesign* designs, const double* rho_min, int n);
+
 uint16_t crc16_modbus(const uint8_t* bytes, int n);
 
 // pre_equalization_channel of a freshly loaded configuration for a given carrier (telecom_system.cc:3108-3145): [Nc]

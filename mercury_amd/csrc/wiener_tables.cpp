@@ -4,6 +4,7 @@
 // so the pilots are filtered along time per carrier (real taps A) and then along frequency per symbol (complex taps B). The taps are the
 // MMSE interpolator's for a channel whose Doppler spectrum is flat within +-doppler_hz and whose delay profile is flat within
 // [tau_min, tau_max], evaluated at the pilots themselves and scaled to unit gain on that channel model.
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <map>
@@ -158,6 +159,57 @@ WienerTables build_wiener_tables(const std::vector<uint8_t>& cell_type, int Nsym
         for (size_t i = 0; i < list.size(); ++i) { w.freq_class[list[i]] = uint16_t(it->second); w.freq_row[list[i]] = uint16_t(i); }
     }
     return w;
+}
+
+// The set-time half of include/mercury_wiener_bank.h's rule.
+WienerBankRule build_wiener_bank_rule(const std::vector<uint8_t>& cell_type, int Nsymb, int Nc, const WienerDesign* designs, const double* rho_min, int n) {
+    if (n < 1 || n > 4 || !designs || !rho_min) throw std::invalid_argument("Wiener bank: 1..MGPU_WIENER_BANK_MAX entries");
+    WienerBankRule r;
+    const auto bin = [&](int c) { return c < Nc / 2 ? c - Nc / 2 : c - Nc / 2 + 1; };
+    std::vector<int> k;                             // per pilot: its bin
+    std::vector<int> sym;                           // per pilot: its symbol
+    r.sym_first.assign(size_t(Nsymb) + 1, 0);
+    for (int q = 0; q < Nsymb * Nc; ++q) {
+        if (!cell_type[size_t(q)]) continue;
+        k.push_back(bin(q % Nc)); sym.push_back(q / Nc);
+    }
+    const int nP = int(k.size());
+    if (nP > 0xffff) throw std::runtime_error("Wiener bank: more pilots than the 2-byte fields hold");
+    for (int p = 0; p < nP; ++p) r.sym_first[size_t(sym[size_t(p)]) + 1] = uint16_t(p + 1);
+    for (int sy = 1; sy <= Nsymb; ++sy) r.sym_first[size_t(sy)] = std::max(r.sym_first[size_t(sy)], r.sym_first[size_t(sy) - 1]);      // a symbol without pilots
+    for (int p = 0; p + 1 < nP; ++p)
+        if (sym[size_t(p)] == sym[size_t(p) + 1] && (r.s == 0 || k[size_t(p) + 1] - k[size_t(p)] < r.s)) r.s = k[size_t(p) + 1] - k[size_t(p)];
+    if (r.s <= 0) throw std::invalid_argument("Wiener bank: no symbol has two pilots");
+    r.pair.assign(size_t(nP), 0);
+    for (int p = 0; p < nP; ++p) {
+        if (p + 1 < nP && sym[size_t(p) + 1] == sym[size_t(p)] && k[size_t(p) + 1] - k[size_t(p)] == r.s) { r.pair[size_t(p)] |= 1; ++r.n1; }
+        if (p + 2 < nP && sym[size_t(p) + 2] == sym[size_t(p)] && k[size_t(p) + 2] - k[size_t(p)] == 2 * r.s) { r.pair[size_t(p)] |= 2; ++r.n2; }
+    }
+    if (r.n1 == 0 || r.n2 == 0) throw std::invalid_argument("Wiener bank: the geometry has no pilot pairs one and two spacings apart");
+    const double s = double(r.s);
+    const auto g = [](double x) { return x < 1.0 ? sinc(x) : 0.0; };
+    std::vector<double> W(static_cast<size_t>(n), 0.0), m(static_cast<size_t>(n), 0.0);
+    for (int d = 0; d < n; ++d) {
+        if (!wiener_design_ok(designs[d])) throw std::invalid_argument("Wiener bank: a design needs tau_max > tau_min, doppler_hz >= 0 and snr_db in -20..40, all finite");
+        W[size_t(d)] = (designs[d].tau_max_us - designs[d].tau_min_us) * 0.012;
+        if (d > 0 && !(W[size_t(d)] > W[size_t(d) - 1])) throw std::invalid_argument("Wiener bank: the designs' widths must be strictly ascending");
+        const double den = g(s * W[size_t(d)] / kNfft);
+        m[size_t(d)] = den > 0.0 ? g(2.0 * s * W[size_t(d)] / kNfft) / den : 0.0;
+    }
+    for (int d = 0; d + 1 < n; ++d) {
+        double rho = rho_min[d];
+        if (std::isnan(rho)) rho = (m[size_t(d)] + m[size_t(d) + 1]) / 2.0;
+        if (!std::isfinite(rho) || rho < 0.0) throw std::invalid_argument("Wiener bank: rho_min must be finite and >= 0, or NaN for the default");
+        const double tau0 = designs[d].tau_min_us * kSampleRate / 1e6, tau1 = designs[d].tau_max_us * kSampleRate / 1e6;
+        const double phi = -2.0 * M_PI * s * (tau0 + tau1) / (2.0 * kNfft);
+        const bool centroid = s * W[size_t(d)] < 64.0;
+        r.rho_min.push_back(rho);
+        r.sel.push_back(rho * rho);
+        r.sel.push_back(std::cos(phi));
+        r.sel.push_back(std::sin(phi));
+        r.sel.push_back(centroid ? std::tan(M_PI * s * W[size_t(d)] / kNfft) : -1.0);
+    }
+    return r;
 }
 
 }  // namespace mgpu

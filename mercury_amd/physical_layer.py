@@ -160,14 +160,21 @@ def _wiener_design(design):
 def parse_ladder(text):
     """'21x21,5x21' -> [(21, 21), (5, 21)] (width = carriers, height = symbols); '' or None -> []. A Wiener rung (include/mercury_estimator.h:
     MGPU_RUNG_WIENER) is 'wiener' or 'wiener:tau=-333/2333,fd=0.5,snr=5' (delay bounds in us, Doppler in Hz, design SNR in dB; what is left
-    out keeps its default) -> ("wiener", {the fields given, named as mgpu_wiener_design's})."""
+    out keeps its default) -> ("wiener", {the fields given, named as mgpu_wiener_design's}). A Wiener rung that chooses its design per
+    frame (include/mercury_wiener_bank.h) is 'bank:tau=-333/333|-333/1000|-333/2333,fd=0.5,snr=5' with an optional 'rho=0.9|0.6': the
+    intervals in ascending width, one fd / snr for every design -> ("bank", {tau: [(min, max), ...], doppler_hz, snr_db, rho: [...]})."""
     if not text:
         return []
     rungs = []
     for item in text.split(","):
         item = item.strip().lower()
-        if rungs and isinstance(rungs[-1][1], dict) and "=" in item and "x" not in item.split("=")[0] and not item.startswith("wiener"):
+        if rungs and isinstance(rungs[-1][1], dict) and "=" in item and "x" not in item.split("=")[0] and not item.startswith(("wiener", "bank")):
             key, value = item.split("=", 1)          # a further field of the Wiener rung before it: the fields are comma-separated too
+        elif item.startswith("bank"):
+            if not item.startswith("bank:") or "=" not in item:
+                raise MgpuError("a bank rung is 'bank:tau=MIN/MAX|MIN/MAX|...,fd=HZ,snr=DB,rho=R|R', not %r" % item)
+            rungs.append(("bank", {}))
+            key, value = item[len("bank:"):].split("=", 1)
         elif item.startswith("wiener"):
             rungs.append(("wiener", {}))
             if item == "wiener":
@@ -179,18 +186,101 @@ def parse_ladder(text):
             rungs.append(tuple(int(v) for v in item.split("x")))
             continue
         d = rungs[-1][1]
-        if key == "tau":
+        if rungs[-1][0] == "bank" and key in ("tau", "rho"):
+            if key == "tau":
+                d["tau"] = [tuple(float(v) for v in iv.split("/")) for iv in value.split("|")]
+                if any(len(iv) != 2 for iv in d["tau"]):
+                    raise MgpuError("a bank's intervals are MIN/MAX, separated by '|', not %r" % value)
+            else:
+                d["rho"] = [float(v) for v in value.split("|")]
+        elif key == "tau":
             lo, hi = value.split("/")
             d["tau_min_us"], d["tau_max_us"] = float(lo), float(hi)
         elif key in ("fd", "snr"):
             d["doppler_hz" if key == "fd" else "snr_db"] = float(value)
         else:
             raise MgpuError("a Wiener rung's fields are tau, fd and snr, not %r" % key)
+    for kind, d in [r for r in rungs if isinstance(r[1], dict) and r[0] == "bank"]:
+        if not d.get("tau"):
+            raise MgpuError("a bank rung needs tau=MIN/MAX|MIN/MAX|...")
+        if "rho" in d and len(d["rho"]) != len(d["tau"]) - 1:
+            raise MgpuError("a bank of %d designs takes %d rho values" % (len(d["tau"]), len(d["tau"]) - 1))
     return rungs
 
 
 def _is_wiener(rung):
     return rung == "wiener" or (isinstance(rung, (tuple, list)) and len(rung) == 2 and rung[0] == "wiener")
+
+
+# ---- a Wiener rung's bank of designs (include/mercury_wiener_bank.h) ---------------------------------------------
+WIENER_BANK_SYMBOLS = ["mgpu_set_wiener_bank", "mgpu_get_wiener_bank", "mgpu_get_wiener_choice", "mgpu_host_wiener_select",
+                       "mgpu_host_wiener_bank_thresholds"]
+WIENER_BANK_MAX = 4
+
+
+class WienerBankEntry(C.Structure):  # mgpu_wiener_bank_entry
+    _fields_ = [("design", WienerDesign), ("rho_min", C.c_double)]
+
+
+def _is_bank(rung):
+    return isinstance(rung, (tuple, list)) and len(rung) == 2 and rung[0] == "bank"
+
+
+def bank_entries(spec):
+    """a ("bank", {...}) rung's dict as parse_ladder gives it (tau: [(min, max), ...] in us, doppler_hz, snr_db for every design, rho:
+    the thresholds of all but the last) -> [(design dict, rho_min or None), ...] as RxPhy.set_wiener_bank takes them"""
+    common = {k: spec[k] for k in ("doppler_hz", "snr_db") if k in spec}
+    rho = list(spec.get("rho", [])) + [None] * len(spec["tau"])
+    return [(dict(common, tau_min_us=lo, tau_max_us=hi), rho[i]) for i, (lo, hi) in enumerate(spec["tau"])]
+
+
+def _bank_array(entries):
+    entries = list(entries or [])
+    arr = (WienerBankEntry * max(len(entries), 1))()
+    for i, e in enumerate(entries):
+        design, rho = e if isinstance(e, (tuple, list)) else (e, None)
+        arr[i] = WienerBankEntry(_wiener_design(design), float("nan") if rho is None else float(rho))
+    return arr, len(entries)
+
+
+def host_wiener_select(cfg, grid, entries, explicit=None):
+    """mgpu_host_wiener_select: the design a bank's rung chooses for one frame grid (complex128 [Nsymb * Nc], after the AGC); no GPU.
+    entries: [(design dict, rho_min or None: the default), ...], the last one the fallback.
+    -> dict(design, corr: float64 [4] R1r R1i R2r R2i, n1, n2)"""
+    lib = load_library()
+    lib.mgpu_host_wiener_select.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    g = np.ascontiguousarray(grid, np.complex128).ravel()
+    xp = _explicit_struct(explicit)
+    arr, n = _bank_array(entries)
+    design, n1, n2, corr = C.c_int(), C.c_int(), C.c_int(), np.zeros(4, np.float64)
+    rc = lib.mgpu_host_wiener_select(int(cfg), C.byref(xp) if xp is not None else None, arr, n, C.sizeof(WienerBankEntry), _ptr(g), C.byref(design),
+                                     _ptr(corr), C.byref(n1), C.byref(n2))
+    if rc != 0:
+        raise MgpuError("mgpu_host_wiener_select failed (%d)" % rc, rc)
+    return dict(design=design.value, corr=corr, n1=n1.value, n2=n2.value)
+
+
+def host_wiener_bank_thresholds(cfg, entries, explicit=None):
+    """mgpu_host_wiener_bank_thresholds: (rho_min as applied: float64 [n - 1], the pilot spacing s) of a bank on the mode's geometry; no GPU"""
+    lib = load_library()
+    lib.mgpu_host_wiener_bank_thresholds.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+    xp = _explicit_struct(explicit)
+    arr, n = _bank_array(entries)
+    rho, s = np.zeros(max(n - 1, 1), np.float64), C.c_int()
+    rc = lib.mgpu_host_wiener_bank_thresholds(int(cfg), C.byref(xp) if xp is not None else None, arr, n, C.sizeof(WienerBankEntry), _ptr(rho), C.byref(s))
+    if rc != 0:
+        raise MgpuError("mgpu_host_wiener_bank_thresholds failed (%d)" % rc, rc)
+    return rho[: max(n - 1, 0)], s.value
+
+
+def wiener_sounding(corr, n1, n2, s):
+    """(rho, delay_us) from the four sums of mgpu_get_wiener_choice / mgpu_host_wiener_select (corr [..., 4]): rho = (|R2| / n2) / (|R1| / n1),
+    the centroid delay = -arg R1 * 256 / (2 pi s) / 0.012 us"""
+    corr = np.asarray(corr, np.float64)
+    r1, r2 = corr[..., 0] + 1j * corr[..., 1], corr[..., 2] + 1j * corr[..., 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = (np.abs(r2) / n2) / (np.abs(r1) / n1)
+    return rho, -np.angle(r1) * 256.0 / (2.0 * np.pi * s) / 0.012
 
 
 def host_wiener_estimate(cfg, grid, design=None, explicit=None):
@@ -604,6 +694,7 @@ class RxPhy:
         if rc != 0:
             raise MgpuError("mgpu_create failed (%d): %s" % (rc, self.lib.mgpu_last_error(None).decode()))
         self.config = c
+        self._mode = (int(cfg), dict(explicit) if explicit else None)      # for the host twins that need the geometry
         self.max_iters = max_iters
         self.max_batch = max_batch
         i = Info()
@@ -631,8 +722,15 @@ class RxPhy:
     def set_estimator_ladder(self, rungs):
         """rungs: [(width, height), ...] in cells (carriers x symbols), at most LADDER_MAX; [] or None: no ladder. Frames whose CRC fails are
         re-estimated and decoded again with the next rung, on the device, in every receive entry point of this context. A rung may also be
-        "wiener" or ("wiener", {design fields}) as parse_ladder gives it: the separable Wiener estimator (MGPU_RUNG_WIENER)."""
+        "wiener" or ("wiener", {design fields}) as parse_ladder gives it: the separable Wiener estimator (MGPU_RUNG_WIENER), or
+        ("bank", {...}): a Wiener rung carrying the bank's last design, plus set_wiener_bank with all of them."""
         rungs = list(rungs or [])
+        banks = {i: bank_entries(r[1]) for i, r in enumerate(rungs) if _is_bank(r)}
+        if banks:       # a bank rung is a Wiener rung carrying the bank's last design, plus the bank
+            self.set_estimator_ladder([("wiener", dict(banks[i][-1][0])) if i in banks else r for i, r in enumerate(rungs)])
+            for i, entries in banks.items():
+                self.set_wiener_bank(i, entries)
+            return
         if any(_is_wiener(r) for r in rungs):
             arr = (EstimatorRung * len(rungs))()
             for i, r in enumerate(rungs):
@@ -663,6 +761,33 @@ class RxPhy:
         self._ck(self.lib.mgpu_get_estimator_ladder_ex(self.h, arr, C.byref(n), C.sizeof(EstimatorRung)))
         return [("wiener", {k: getattr(arr[r].design, k) for k in WIENER_DESIGN_DEFAULT}) if arr[r].kind == RUNG_WIENER
                 else (arr[r].window.width, arr[r].window.height) for r in range(n.value)]
+
+    # ---- a Wiener rung's bank of designs (include/mercury_wiener_bank.h) --------------------------
+    def set_wiener_bank(self, rung, entries):
+        """Rung `rung` of the ladder in force (a Wiener rung) chooses per frame among entries = [(design dict, rho_min or None: the
+        default), ...] (a bare design dict is (design, None)); the last entry is the fallback. [] or None removes the bank."""
+        arr, n = _bank_array(entries)
+        self.lib.mgpu_set_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t]
+        self._ck(self.lib.mgpu_set_wiener_bank(self.h, int(rung), arr if n else None, n, C.sizeof(WienerBankEntry)))
+
+    def wiener_bank(self, rung):
+        """the bank of a rung with the thresholds as applied: [(design dict, rho_min), ...] (None for a NaN: the fallback's is reported as
+        it was given); [] where it has none"""
+        arr, n = (WienerBankEntry * WIENER_BANK_MAX)(), C.c_int()
+        self.lib.mgpu_get_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        self._ck(self.lib.mgpu_get_wiener_bank(self.h, int(rung), arr, C.byref(n), C.sizeof(WienerBankEntry)))
+        return [({k: getattr(arr[d].design, k) for k in WIENER_DESIGN_DEFAULT}, None if np.isnan(arr[d].rho_min) else arr[d].rho_min) for d in range(n.value)]
+
+    def wiener_choice(self, first=0, count=None):
+        """rung 0's choice for rows first .. first + count - 1 (default: to max_batch) of the last receive call:
+        dict(design int32 [count], corr float64 [count, 4], n1, n2, rho, delay_us) - rho and delay_us computed here from corr"""
+        count = self.max_batch - int(first) if count is None else int(count)
+        design, corr, n1, n2 = np.zeros(count, np.int32), np.zeros((count, 4), np.float64), C.c_int(), C.c_int()
+        self.lib.mgpu_get_wiener_choice.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._ck(self.lib.mgpu_get_wiener_choice(self.h, int(first), count, _ptr(design), _ptr(corr), C.byref(n1), C.byref(n2)))
+        _, s = host_wiener_bank_thresholds(self._mode[0], self.wiener_bank(0), explicit=self._mode[1])
+        rho, delay = wiener_sounding(corr, n1.value, n2.value, s)
+        return dict(design=design, corr=corr, n1=n1.value, n2=n2.value, rho=rho, delay_us=delay)
 
     def last_rungs(self, F):
         """winning rung of each of the first F frames of the last receive call, -1 where no rung decoded: int32 [F]"""

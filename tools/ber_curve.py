@@ -10,7 +10,8 @@ prints EsN0;BER;FER lines like the reference does, for far more frames per point
 reference's AWGN FER < 0.1 value (include/common/common_defines.h:130-147) to 40 dB above it in 1 dB steps, in one call; one JSON line
 gives the first point of the first run of three with FER < 0.1 ("fer01_esn0_db", null if none) beside the AWGN value.
 --ladder 21x21,5x21 (any form): an estimator ladder (include/mercury_estimator.h; windows as carriers x symbols, or `wiener` /
-`wiener:tau=-333/2333,fd=0.5,snr=5` for the separable Wiener estimator) on the context; the JSON
+`wiener:tau=-333/2333,fd=0.5,snr=5` for the separable Wiener estimator, `bank:tau=-333/333|-333/1000|-333/2333,snr=5` for one that
+chooses its design per frame, include/mercury_wiener_bank.h) on the context; the JSON
 line then carries the frames each rung decoded.
 --diversity D (baseband form; with --channel and at most a one-rung --ladder): D branches per payload, each with its own channel realisation
 and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_per_point counts payloads, Es/N0 is per branch.

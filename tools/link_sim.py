@@ -173,7 +173,7 @@ def main():
     ap.add_argument("--max-iters", type=int, default=50)
     ap.add_argument("--max-batch", type=int, default=0, help="receive_byte windows per call (0: the number of links)")
     ap.add_argument("--power", type=float, default=1.0, help="output_power_watt (1: Es/N0 is the signal's own, BER_PLOT_passband's convention)")
-    ap.add_argument("--ladder", default="", help="estimator ladder, e.g. 21x21,5x21 (carriers x symbols) or 21x21,wiener (include/mercury_estimator.h)")
+    ap.add_argument("--ladder", default="", help="estimator ladder, e.g. 21x21,5x21 (carriers x symbols) or 21x21,wiener (include/mercury_estimator.h) or bank:tau=-333/333|-333/2333 (include/mercury_wiener_bank.h)")
     ap.add_argument("--demapper", default="maxlog", type=_demapper,
                     help="csi: LLRs weighted by |H|^2 per cell; nmap[:band=2,smooth=1]: those divided by a noise factor per carrier and per symbol (include/mercury_demapper.h)")
     ap.add_argument("--cfo", default="off", choices=["off", "pilots"], help="pilots: every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)")
