@@ -38,29 +38,81 @@ def full_estimate(orc, ref):
     return ref["H_noamp"] if orc.amp_restore else ref["H"]
 
 
-def np_demap_csi(orc, grid, H):
-    """the rule in numpy: (llr_demod float32 [nBits], sigma2). numpy's complex division is not the equaliser's, so the LLRs agree with the
-    library's twin within the project's bound for such differences, not bit for bit; sigma2 is exact (np.cumsum is a serial sum)."""
+def np_cdiv(n, d):
+    """fe_math.h's cdiv (libgcc's __divdc3 main path) component-wise in real numpy arithmetic, operation for operation: the operands
+    swapped where |d.re| < |d.im|, one ratio, the same five operations. Every numpy operation is one IEEE double operation, so this is
+    the equaliser's division bit for bit, NaN where it gives NaN."""
+    a, b, c, dd = n.real, n.imag, d.real, d.imag
+    with np.errstate(all="ignore"):
+        sw = np.abs(c) < np.abs(dd)
+        p, q = np.where(sw, c, dd), np.where(sw, dd, c)
+        ratio = p / q
+        denom = (p * ratio) + q
+        u, v = np.where(sw, a, b), np.where(sw, b, a)
+        x = ((u * ratio) + v) / denom
+        t = v * ratio
+        y = np.where(sw, t - a, b - t) / denom
+    return x, y
+
+
+def np_maxlog(orc, er, ei, scale):
+    """the demapping both twins share: squared distances to the constellation in double narrowed to float, per bit the running minima taken
+    with np.fmin (which keeps the minimum on a NaN distance, as std::fmin does) from +Inf in constellation order, LLR = scale * (d1 - d0)
+    in float. er, ei: the equalised symbols' components [nData]; scale: float32 [nData]. -> llr_demod float32 [nBits]"""
+    cons = orc.constellation()
+    bps = orc.bits_per_symbol
+    d0 = np.full((bps, er.size), np.inf, np.float32)
+    d1 = np.full((bps, er.size), np.inf, np.float32)
+    with np.errstate(all="ignore"):
+        for j in range(orc.M):
+            dr, di = er - cons[j].real, ei - cons[j].imag
+            D = (dr * dr + di * di).astype(np.float32)
+            for b in range(bps):
+                side = d1 if (j >> b) & 1 else d0
+                side[b] = np.fmin(side[b], D)
+        llr = np.zeros((er.size, bps), np.float32)
+        for b in range(bps):
+            llr[:, bps - 1 - b] = scale * (d1[b] - d0[b])
+    return llr.ravel()
+
+
+def np_sigma2(orc, grid, H):
+    """(the pilots' residuals |g - h x|^2 in pilot order, their serial sum over nPilots) - np.cumsum adds one term after the other"""
     pilots = np.flatnonzero(orc.frame_types() != 0)
     x = orc.pilot_seq().real
     g, h = grid[pilots], H[pilots]
-    dr, di = g.real - h.real * x, g.imag - h.imag * x
-    sigma2 = np.cumsum(dr * dr + di * di)[-1] / float(orc.nPilots)
+    with np.errstate(all="ignore"):
+        dr, di = g.real - h.real * x, g.imag - h.imag * x
+        r = dr * dr + di * di
+        return r, float(np.cumsum(r)[-1] / float(orc.nPilots))
+
+
+def np_demap_csi(orc, grid, H):
+    """the rule in numpy: (llr_demod float32 [nBits], sigma2). Exact: the division is np_cdiv, the minima np_maxlog's, the scale formed as
+    the twin forms it, (float32(1) / float32(sigma2)) * wf - so it equals mgpu_host_demap_csi bit for bit, NaN where it gives NaN, on
+    degenerate grids too (tests/test_frontend_degenerate_host.py)."""
+    grid, H = np.asarray(grid, np.complex128).ravel(), np.asarray(H, np.complex128).ravel()
+    _, sigma2 = np_sigma2(orc, grid, H)
     src = sym_src(orc)
     hs = H[src]
-    e = grid[src] / hs
-    wf = (hs.real * hs.real + hs.imag * hs.imag).astype(np.float32)
-    cons = orc.constellation()
-    er, ei = e.real[:, None] - cons.real[None, :], e.imag[:, None] - cons.imag[None, :]
-    D = (er * er + ei * ei).astype(np.float32)                       # [nData, M]
-    bps = orc.bits_per_symbol
-    scale = (np.float32(1.0) / np.float32(sigma2)) * wf
-    llr = np.zeros((orc.nData, bps), np.float32)
-    j = np.arange(orc.M)
-    for b in range(bps):
-        one = ((j >> b) & 1) == 1
-        llr[:, bps - 1 - b] = scale * (D[:, one].min(axis=1) - D[:, ~one].min(axis=1))
-    return llr.ravel(), float(sigma2)
+    er, ei = np_cdiv(grid[src], hs)
+    with np.errstate(all="ignore"):
+        wf = (hs.real * hs.real + hs.imag * hs.imag).astype(np.float32)
+        scale = (np.float32(1.0) / np.float64(sigma2).astype(np.float32)) * wf
+    return np_maxlog(orc, er, ei, scale), sigma2
+
+
+def same_bits(got, want):
+    """bit for bit where `want` is a number - signs of zeros and infinities included -, NaN exactly where it is NaN (x86 and CDNA differ in
+    the sign bit of a generated NaN, so NaNs are compared as positions)"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return False
+    if got.dtype.kind == "c":
+        got, want = got.view(got.real.dtype), want.view(want.real.dtype)
+    nan = np.isnan(want)
+    bits = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
+    return bool(np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan].view(bits), want[~nan].view(bits)))
 
 
 def llr_tol(ref):

@@ -6,7 +6,7 @@ import functools
 
 import numpy as np
 
-from demapper_csi_ref import CASES, DY5, full_estimate, llr_src, llr_tol, sym_src, tail  # noqa: F401  (shared with the tests)
+from demapper_csi_ref import CASES, DY5, full_estimate, llr_src, llr_tol, np_cdiv, np_maxlog, np_sigma2, same_bits, sym_src, tail  # noqa: F401  (shared with the tests)
 from oraclelib import Oracle, noise_amp_for
 
 LS_CASES = [(cfg, explicit) for cfg, explicit in CASES if cfg != 16]          # 0, 8, 11, 13 and (8, Dy 5 / Nsymb 20): the zero-forcing mode is refused
@@ -15,7 +15,8 @@ INF = float("inf")
 
 def _serial(terms):
     """the sum of terms one after the other from +0.0 (np.cumsum adds serially), 0.0 for none"""
-    return float(np.cumsum(np.asarray(terms, np.float64))[-1]) if len(terms) else 0.0
+    with np.errstate(all="ignore"):
+        return float(np.cumsum(np.asarray(terms, np.float64))[-1]) if len(terms) else 0.0
 
 
 def _banded(v, n, sigma2, band):
@@ -29,11 +30,7 @@ def np_noise_map(orc, grid, H, band=2.0, smooth=1):
     """the map in numpy: (sigma2, fc [Nc], fs [Nsymb], raw fc, raw fs) - the factors after the dead band and before it"""
     Nc, Ns = orc.Nc, orc.Nsymb
     pilots = np.flatnonzero(orc.frame_types() != 0)
-    x = orc.pilot_seq().real
-    g, h = grid[pilots], H[pilots]
-    dr, di = g.real - h.real * x, g.imag - h.imag * x
-    r = dr * dr + di * di
-    sigma2 = float(np.cumsum(r)[-1] / float(orc.nPilots))
+    r, sigma2 = np_sigma2(orc, grid, H)
     car, sym = pilots % Nc, pilots // Nc
     S = [_serial(r[car == c]) for c in range(Nc)]                    # pilot order is ascending symbols within a carrier
     n = [int((car == c).sum()) for c in range(Nc)]
@@ -54,26 +51,20 @@ def np_noise_map(orc, grid, H, band=2.0, smooth=1):
 
 
 def np_demap_nmap(orc, grid, H, band=2.0, smooth=1):
-    """the rule in numpy: (llr_demod float32 [nBits], sigma2, fc, fs). As with np_demap_csi the division is numpy's, so the LLRs agree with
-    the library's twin within llr_tol; sigma2 and the factors are the same serial sums and agree to rounding."""
+    """the rule in numpy: (llr_demod float32 [nBits], sigma2, fc, fs). Exact, as np_demap_csi: its division and minima, the scale formed as
+    the twin forms it, (a[c] * b[s]) * wf with a = 1 / float32(sigma2 * fc) and b = 1 / float32(fs) - so it equals mgpu_host_demap_nmap bit
+    for bit, NaN where it gives NaN; sigma2 and the factors are the same serial sums."""
+    grid, H = np.asarray(grid, np.complex128).ravel(), np.asarray(H, np.complex128).ravel()
     sigma2, fc, fs, _, _ = np_noise_map(orc, grid, H, band, smooth)
-    a = np.float32(1.0) / (np.float64(sigma2) * fc).astype(np.float32)
-    b = np.float32(1.0) / fs.astype(np.float32)
     src = sym_src(orc)
     hs = H[src]
-    e = grid[src] / hs
-    wf = (hs.real * hs.real + hs.imag * hs.imag).astype(np.float32)
-    cons = orc.constellation()
-    er, ei = e.real[:, None] - cons.real[None, :], e.imag[:, None] - cons.imag[None, :]
-    D = (er * er + ei * ei).astype(np.float32)
-    bps = orc.bits_per_symbol
-    scale = (a[src % orc.Nc] * b[src // orc.Nc]) * wf
-    llr = np.zeros((orc.nData, bps), np.float32)
-    j = np.arange(orc.M)
-    for bit in range(bps):
-        one = ((j >> bit) & 1) == 1
-        llr[:, bps - 1 - bit] = scale * (D[:, one].min(axis=1) - D[:, ~one].min(axis=1))
-    return llr.ravel(), sigma2, fc, fs
+    er, ei = np_cdiv(grid[src], hs)
+    with np.errstate(all="ignore"):
+        a = np.float32(1.0) / (np.float64(sigma2) * fc).astype(np.float32)
+        b = np.float32(1.0) / fs.astype(np.float32)
+        wf = (hs.real * hs.real + hs.imag * hs.imag).astype(np.float32)
+        scale = (a[src % orc.Nc] * b[src // orc.Nc]) * wf
+    return np_maxlog(orc, er, ei, scale), sigma2, fc, fs
 
 
 def _key(explicit):

@@ -49,12 +49,27 @@ def np_select(orc, grid, entries):
     from equality - how far the frame is from the other choice)"""
     Nc, Ns = orc.Nc, orc.Nsymb
     types = orc.frame_types().ravel() != 0
-    yp = (np.asarray(grid).ravel()[types]) * np.sign(orc.pilot_seq().real)
+    g, sign = np.asarray(grid, np.complex128).ravel()[types], np.sign(orc.pilot_seq().real)
+    yr, yi = g.real * sign, g.imag * sign                                  # per component: exact, and an Inf stays an Inf
+    pilot_sym = np.flatnonzero(types) // Nc
     s, one, two = np_pairs(orc)
     n1, n2 = len(one), len(two)
-    R1 = np.sum(np.conj(yp[one[:, 0]]) * yp[one[:, 1]])
-    R2 = np.sum(np.conj(yp[two[:, 0]]) * yp[two[:, 1]])
-    q2, q1 = abs(R2) ** 2 * float(n1) ** 2, abs(R1) ** 2 * float(n2) ** 2
+
+    def serial(v):
+        return float(np.cumsum(np.concatenate([[0.0], v]))[-1])            # one term after the other from +0.0
+
+    def corr(pairs):
+        """the header's sums: a pair's term from its four products, per symbol in ascending a, then the symbols' sums in ascending symbols"""
+        a, b = pairs[:, 0], pairs[:, 1]
+        tr, ti = (yr[a] * yr[b]) + (yi[a] * yi[b]), (yr[a] * yi[b]) - (yi[a] * yr[b])
+        sym = pilot_sym[a]
+        return (serial([serial(tr[sym == i]) for i in range(Ns)]), serial([serial(ti[sym == i]) for i in range(Ns)]))
+
+    (R1r, R1i), (R2r, R2i) = corr(one), corr(two)
+    R1, R2 = complex(R1r, R1i), complex(R2r, R2i)
+    # the header's sums of squares, not abs() ** 2: hypot(Inf, NaN) is Inf, and a sum with a NaN component must fail every comparison
+    q2 = (R2r * R2r + R2i * R2i) * (float(n1) * float(n1))
+    q1 = (R1r * R1r + R1i * R1i) * (float(n2) * float(n2))
     rho_min = np_thresholds(entries, s)
     choice, margin = len(entries) - 1, np.inf
     for d in range(len(entries) - 2, -1, -1):
@@ -66,7 +81,7 @@ def np_select(orc, grid, entries):
         if s * Wd < 64:
             tau0, tau1 = design["tau_min_us"] * 12000.0 / 1e6, design["tau_max_us"] * 12000.0 / 1e6
             phi = -2.0 * np.pi * s * (tau0 + tau1) / 512.0
-            z = R1 * np.conj(np.exp(1j * phi))
+            z = complex(R1r * np.cos(phi) + R1i * np.sin(phi), R1i * np.cos(phi) - R1r * np.sin(phi))
             t = np.tan(np.pi * s * Wd / 256.0)
             ok = ok and z.real > 0 and abs(z.imag) <= t * z.real
             if np.isfinite(abs(z)) and abs(z) > 0:
@@ -74,8 +89,8 @@ def np_select(orc, grid, entries):
         if ok:
             choice = d
     with np.errstate(divide="ignore", invalid="ignore"):
-        rho = (abs(R2) / n2) / (abs(R1) / n1)
-    return dict(design=choice, corr=np.array([R1.real, R1.imag, R2.real, R2.imag]), n1=n1, n2=n2, rho=float(rho), margin=float(margin))
+        rho = (np.float64(abs(R2)) / n2) / (np.float64(abs(R1)) / n1)
+    return dict(design=choice, corr=np.array([R1r, R1i, R2r, R2i]), n1=n1, n2=n2, rho=float(rho), margin=float(margin))
 
 
 @functools.lru_cache(maxsize=None)

@@ -77,17 +77,28 @@ def np_estimate(orc, grid, tables):
     types = orc.frame_types().reshape(Ns, Nc) != 0
     sign = np.zeros((Ns, Nc))
     sign[types] = np.sign(orc.pilot_seq().real)
-    yp = grid.reshape(Ns, Nc) * sign
+    g = np.asarray(grid, np.complex128).reshape(Ns, Nc)
     t = np.zeros((Ns, Nc), np.complex128)
     for c in range(Nc):
         rows = np.flatnonzero(types[:, c])
         if rows.size:
-            t[rows, c] = tables["time"][tuple(int(r) for r in rows)] @ yp[rows, c]
+            # the sign and the real taps applied per component, as the rule has them: a complex product with (x + 0j) would turn an
+            # infinite component into a NaN in the other one
+            A = tables["time"][tuple(int(r) for r in rows)]
+            col = np.zeros(rows.size, np.complex128)
+            col.real = A @ (g.real[rows, c] * sign[rows, c])
+            col.imag = A @ (g.imag[rows, c] * sign[rows, c])
+            t[rows, c] = col
     H = np.zeros((Ns, Nc), np.complex128)
     for i in range(Ns):
         cars = np.flatnonzero(types[i])
         if cars.size:
-            H[i, cars] = tables["freq"][tuple(int(c) for c in cars)] @ t[i, cars]
+            # four real products, for the same reason (a BLAS complex product scales by alpha = 1 + 0j at the end)
+            B, row = tables["freq"][tuple(int(c) for c in cars)], t[i, cars]
+            out = np.zeros(cars.size, np.complex128)
+            out.real = B.real @ row.real - B.imag @ row.imag
+            out.imag = B.real @ row.imag + B.imag @ row.real
+            H[i, cars] = out
     return H[types]
 
 
@@ -99,17 +110,18 @@ def interpolate_cols(orc, Hp):
     types = orc.frame_types().reshape(Ns, Nc) != 0
     H = np.zeros((Ns, Nc), np.complex128)
     H[types] = Hp
-    for c in range(Nc):
-        rows = np.flatnonzero(types[:, c])
-        for i in range(Ns):
-            if types[i, c]:
-                continue
-            k = int(np.searchsorted(rows, i))
-            k = min(max(k, 1), rows.size - 1)
-            ia, ib = int(rows[k - 1]), int(rows[k])
-            a, b = H[ia, c], H[ib, c]
-            m, q = float(i - ia), float(ib - ia)
-            H[i, c] = complex(a.real + ((b.real - a.real) * m) / q, a.imag + ((b.imag - a.imag) * m) / q)
+    with np.errstate(all="ignore"):                                        # (an estimate may hold Inf and NaN: the degenerate-frame tests)
+        for c in range(Nc):
+            rows = np.flatnonzero(types[:, c])
+            for i in range(Ns):
+                if types[i, c]:
+                    continue
+                k = int(np.searchsorted(rows, i))
+                k = min(max(k, 1), rows.size - 1)
+                ia, ib = int(rows[k - 1]), int(rows[k])
+                a, b = H[ia, c], H[ib, c]
+                m, q = float(i - ia), float(ib - ia)
+                H[i, c] = complex(a.real + ((b.real - a.real) * m) / q, a.imag + ((b.imag - a.imag) * m) / q)
     return H.ravel()
 
 
