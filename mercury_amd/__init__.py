@@ -10,7 +10,7 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              host_hilbert_taps, load_library, pool_shard, HF_STREAM_SYMBOLS, LINKSIM_SYMBOLS, LINKSIM_COUNTERS_DTYPE, HfStream, LinkSim,
                              LinkSimConfig, linksim_config, host_hf_stream_noise, host_linksim_frame_start, host_linksim_payload, ESTIMATOR_SYMBOLS, LADDER_MAX, host_ls_estimate, parse_ladder, host_wiener_estimate, host_wiener_tables, WIENER_DESIGN_DEFAULT,
                              DIVERSITY_SYMBOLS, DIVERSITY_MAX, host_llr_combine, DEMAPPER_SYMBOLS, DEMAPPERS, host_demap_csi, host_demap_nmap, parse_demapper, NMAP_DEFAULT, DemapperParams,
-                             CFO_SYMBOLS, CFO_MODES, host_cfo_pilots,
+                             CFO_SYMBOLS, CFO_MODES, host_cfo_pilots, BLANKER_SYMBOLS, BLANKER_MODES, BLANKER_DEFAULT, BLANKER_REPORT_DTYPE, BlankerParams, host_blank, parse_blanker,
                              WIENER_BANK_SYMBOLS, WIENER_BANK_MAX, WienerBankEntry, host_wiener_select, host_wiener_bank_thresholds, wiener_sounding, bank_entries)
 
 from .shm import ShmRing  # noqa: E402
@@ -20,5 +20,5 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "host_hf_channel_draws", "host_hf_channel_taps", "HfStream", "LinkSim", "LinkSimConfig", "linksim_config", "HF_STREAM_SYMBOLS", "LINKSIM_SYMBOLS",
            "LINKSIM_COUNTERS_DTYPE", "host_hf_stream_noise", "host_linksim_frame_start", "host_linksim_payload", "ESTIMATOR_SYMBOLS", "LADDER_MAX", "host_ls_estimate",
            "parse_ladder", "host_wiener_estimate", "host_wiener_tables", "WIENER_DESIGN_DEFAULT", "DIVERSITY_SYMBOLS", "DIVERSITY_MAX", "host_llr_combine", "DEMAPPER_SYMBOLS", "DEMAPPERS", "host_demap_csi", "host_demap_nmap", "parse_demapper", "NMAP_DEFAULT", "DemapperParams",
-           "CFO_SYMBOLS", "CFO_MODES", "host_cfo_pilots",
+           "CFO_SYMBOLS", "CFO_MODES", "host_cfo_pilots", "BLANKER_SYMBOLS", "BLANKER_MODES", "BLANKER_DEFAULT", "BLANKER_REPORT_DTYPE", "BlankerParams", "host_blank", "parse_blanker",
            "WIENER_BANK_SYMBOLS", "WIENER_BANK_MAX", "WienerBankEntry", "host_wiener_select", "host_wiener_bank_thresholds", "wiener_sounding", "bank_entries"]

@@ -20,6 +20,7 @@
 #include "../../include/mercury_diversity.h"
 #include "../../include/mercury_demapper.h"
 #include "../../include/mercury_cfo.h"
+#include "../../include/mercury_blanker.h"
 #include "device_tables.h"
 #include "ls_rect.h"
 #include "tables.hpp"
@@ -246,6 +247,15 @@ struct Cfo {
     DevArray<double> d_step;                        // [max_batch] radians per symbol, by the frame's row in the context's workspaces
 };
 
+// The context's impulse blanker (include/mercury_blanker.h; blanker.hip). MGPU_BLANK_MEDIAN: the fused span starts with the blanker kernel and
+// everything behind it reads the blanked frames in d_ws.
+struct Blanker {
+    int mode = MGPU_BLANK_OFF;
+    mgpu_blanker_params params = MGPU_BLANKER_PARAMS_DEFAULT;   // as set; the defaults until then
+    DevArray<double> d_ws;                          // [max_batch][frame_samples] c128 the blanked frames, by the frame's row; held while the mode is on
+    DevArray<int> d_report;                         // [max_batch] {marked, blanked} of the last span's frames, by the frame's row
+};
+
 // The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
 struct SpanIo {
     const double* bb = nullptr;         // input frames
@@ -312,6 +322,7 @@ struct mgpu_ctx {
     Diversity div;
     Demapper dmp;
     Cfo cfo;
+    Blanker blk;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     // the blocking host-buffer entry points' chunk pipeline (rx_batch.hip rx_batch_pipelined)
@@ -418,6 +429,11 @@ void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, in
 // frames still undecoded and merges the ones that decode. Nothing without a ladder. Waits for the stream once per rung (the retry's frame count).
 void launch_ladder(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
 void launch_zf_snr(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
+// The impulse blanker (blanker.hip): F frames, in_stride complex samples apart in d_in, into the dense d_out (and their reports, if wanted),
+// with the context's parameters. blanked_span: the head of a fused span with the stage on - the blanker on io.bb into the context's workspace
+// rows from io.frame0, input_free (if given) recorded right behind it - and the SpanIo the rest of the span runs on.
+void launch_blanker(mgpu_ctx* c, const double* d_in, int F, size_t in_stride, double* d_out, int* d_report, hipStream_t s);
+SpanIo blanked_span(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s, hipEvent_t input_free);
 // The grouped span's own steps (combine.hip): the context's compact rows, made on first use; the sums of G groups of member rows (uniform
 // groups of D when d_first is null, else the CSR on the device) into d_out; the groups' decode back to the F rows of io.
 void diversity_workspaces(mgpu_ctx* c);

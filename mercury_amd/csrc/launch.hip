@@ -137,7 +137,14 @@ static void launch_group_span(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTa
     if (io.zf_snr) launch_zf_snr(c, io, F, s);     // per row: the group's payload against the branch's own equalised symbols
 }
 
-void launch_span(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, hipStream_t s, hipEvent_t input_free) {
+void launch_span(mgpu_ctx* c, const SpanIo& caller_io, int F, const MgpuTapsDev& taps, hipStream_t s, hipEvent_t input_free) {
+    // The impulse blanker (include/mercury_blanker.h), when on: in front of the front-end's start event, so that the kernel timings keep
+    // describing the front-end. It is the only reader of the caller's buffer (input_free is recorded right behind it); everything from here
+    // on, the ladder's retries and the grouped span included, reads the blanked frames in the context's workspace.
+    const bool blank = c->blk.mode == MGPU_BLANK_MEDIAN;
+    const SpanIo blanked = blank ? blanked_span(c, caller_io, F, s, input_free) : SpanIo{};
+    const SpanIo& io = blank ? blanked : caller_io;
+    if (blank) input_free = nullptr;
     if (io.group > 0) { launch_group_span(c, io, F, taps, s, input_free); return; }
     const bool retries = c->lad.n > 1;           // an estimator ladder's retries read the input again
     launch_frontend(c, io, F, taps, s);

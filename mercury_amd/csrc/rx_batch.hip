@@ -324,8 +324,8 @@ int mgpu_host_path_last(mgpu_ctx* c, int* chunk_frames, int* n_chunks, float* fi
 
 int mgpu_rx_batch(mgpu_ctx* c, const double* bb, int F, uint8_t* payload, mgpu_frame_stats* stats, float* llr_opt) {
     // (an estimator ladder's retry depends on the frame's result: it does not go into the captured graph; nor does the channel-aware
-    // demapper's kernel or the residual carrier-offset stage's, so that the graph never has to be captured again)
-    if (c && bb && F == 1 && !llr_opt && !c->kt.timing && c->max_batch >= 1 && c->lad.n == 0 && c->dmp.mode == MGPU_DEMAP_MAXLOG && c->cfo.mode == MGPU_CFO_OFF && !std::getenv("MERCURY_NO_GRAPH"))
+    // demapper's kernel, the residual carrier-offset stage's or the impulse blanker's, so that the graph never has to be captured again)
+    if (c && bb && F == 1 && !llr_opt && !c->kt.timing && c->max_batch >= 1 && c->lad.n == 0 && c->dmp.mode == MGPU_DEMAP_MAXLOG && c->cfo.mode == MGPU_CFO_OFF && c->blk.mode == MGPU_BLANK_OFF && !std::getenv("MERCURY_NO_GRAPH"))
         return rx_one_frame(c, bb, payload, stats);
     if (c && bb && F > 1 && F <= c->max_batch && !llr_opt && !c->kt.timing && !std::getenv("MERCURY_NO_PIPELINE"))
         return guard(c, [&] { rx_batch_pipelined(c, bb, F, payload, stats); });

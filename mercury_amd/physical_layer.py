@@ -484,6 +484,68 @@ def host_cfo_pilots(cfg, grid, explicit=None):
     return out, float(step.value)
 
 
+# ---- the impulse blanker (include/mercury_blanker.h) -----------------------------------------------------------------
+BLANKER_SYMBOLS = ["mgpu_set_blanker", "mgpu_get_blanker", "mgpu_get_blanker_report", "mgpu_blank_dev", "mgpu_host_blank"]
+BLANKER_MODES = {"off": 0, "median": 1}
+BLANKER_DEFAULT = {"threshold": 24.0, "guard": 4, "max_share": 0.125}
+BLANKER_REPORT_DTYPE = np.dtype([("marked", "<i4"), ("blanked", "<i4")])
+
+
+class BlankerParams(C.Structure):
+    """mgpu_blanker_params (include/mercury_blanker.h)"""
+    _fields_ = [("threshold", C.c_double), ("guard", C.c_int), ("max_share", C.c_double)]
+
+
+def _blanker_params(threshold=None, guard=None, max_share=None):
+    d = BLANKER_DEFAULT
+    return BlankerParams(float(d["threshold"] if threshold is None else threshold), int(d["guard"] if guard is None else guard),
+                         float(d["max_share"] if max_share is None else max_share))
+
+
+def parse_blanker(text):
+    """"off", "median" or "median:thr=24,guard=4,share=0.125" (the tools' --blanker) -> (name, {threshold, guard, max_share} or None)"""
+    name, _, rest = str(text).partition(":")
+    if name not in BLANKER_MODES or (rest and name != "median"):
+        raise ValueError("blanker: off, or median with :thr=T,guard=G,share=S")
+    if name != "median":
+        return name, None
+    prm = dict(BLANKER_DEFAULT)
+    for item in filter(None, rest.split(",")):
+        key, _, value = item.partition("=")
+        if key == "thr":
+            prm["threshold"] = float(value)
+        elif key == "guard":
+            prm["guard"] = int(value)
+        elif key == "share":
+            prm["max_share"] = float(value)
+        else:
+            raise ValueError("blanker median: thr=T, guard=G and share=S are what it takes, not %r" % item)
+    return name, prm
+
+
+def host_blank(cfg, frame, explicit=None, **params):
+    """mgpu_host_blank, no GPU: one frame's baseband samples (complex128 [frame_samples]) -> (the blanked frame, {"marked", "blanked"}).
+    params: threshold, guard, max_share (the defaults where left out). explicit: as RxPhy's."""
+    lib = load_library()
+    lib.mgpu_host_blank.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    x = np.ascontiguousarray(frame, np.complex128).ravel()
+    xp = _explicit_struct(explicit)
+    # frame_samples of the (possibly explicit) geometry: an explicit Nsymb symbols of the mode's length, else the mode's own
+    info = Info()
+    lib.mgpu_host_mode_info.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    if lib.mgpu_host_mode_info(int(cfg), 0, C.byref(info)) != 0:
+        raise MgpuError("host_blank: cfg %r is no mode" % (cfg,), 1)
+    n = int((explicit or {}).get("Nsymb", 0)) * info.Nofdm or info.frame_samples
+    if x.size != n:
+        raise MgpuError("host_blank: the frame must have frame_samples (%d) samples" % n, 1)
+    prm = _blanker_params(**params)
+    out, rep = np.zeros_like(x), np.zeros(1, BLANKER_REPORT_DTYPE)
+    rc = lib.mgpu_host_blank(int(cfg), C.byref(xp) if xp is not None else None, C.byref(prm), _ptr(x), _ptr(out), _ptr(rep))
+    if rc != 0:
+        raise MgpuError("mgpu_host_blank failed (%d)" % rc, rc)
+    return out, {"marked": int(rep["marked"][0]), "blanked": int(rep["blanked"][0])}
+
+
 # ---- diversity combining (include/mercury_diversity.h, DESIGN.md §3.8) ------------------------------------------------------------
 DIVERSITY_SYMBOLS = ["mgpu_rx_batch_div_dev", "mgpu_rx_batch_div", "mgpu_llr_combine_dev", "mgpu_host_llr_combine", "mgpu_baseband_test_esn0_div"]
 DIVERSITY_MAX = 8
@@ -870,6 +932,72 @@ class RxPhy:
         self.lib.mgpu_get_cfo_steps.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._ck(self.lib.mgpu_get_cfo_steps(self.h, int(F), _ptr(out)))
         return out
+
+    # ---- the impulse blanker (include/mercury_blanker.h) -------------------------------------------
+    def set_blanker(self, name, threshold=None, guard=None, max_share=None):
+        """"off": the samples go to the front-end as they are (the default). "median": every frame passes through the median-gated blanker
+        first, in every receive entry point of this context (threshold, default 24 block medians; guard, default 4 samples; max_share,
+        default 0.125 of the frame). name may also be the tools' form, "median:thr=24,guard=4,share=0.125" (parse_blanker)."""
+        try:
+            name, spec = parse_blanker(name)
+        except ValueError:
+            raise MgpuError("blanker must be one of %s" % sorted(BLANKER_MODES))
+        spec = spec or BLANKER_DEFAULT
+        prm = _blanker_params(spec["threshold"] if threshold is None else threshold, spec["guard"] if guard is None else guard,
+                              spec["max_share"] if max_share is None else max_share)
+        self.lib.mgpu_set_blanker.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        self._ck(self.lib.mgpu_set_blanker(self.h, BLANKER_MODES[name], C.byref(prm), C.sizeof(prm)))
+
+    @property
+    def blanker(self):
+        """(name, {threshold, guard, max_share}): the mode and the parameters as last set (the defaults before)"""
+        v, prm = C.c_int(), BlankerParams()
+        self.lib.mgpu_get_blanker.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        self._ck(self.lib.mgpu_get_blanker(self.h, C.byref(v), C.byref(prm), C.sizeof(prm)))
+        return {n: k for k, n in BLANKER_MODES.items()}[v.value], {"threshold": prm.threshold, "guard": prm.guard, "max_share": prm.max_share}
+
+    def blanker_report(self, first=0, count=None):
+        """{marked, blanked} (BLANKER_REPORT_DTYPE [count]) of rows first .. first + count - 1 (default: to max_batch) of the last call that
+        ran with the blanker on"""
+        count = self.max_batch - int(first) if count is None else int(count)
+        out = np.zeros(count, BLANKER_REPORT_DTYPE)
+        self.lib.mgpu_get_blanker_report.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self._ck(self.lib.mgpu_get_blanker_report(self.h, int(first), count, _ptr(out)))
+        return out
+
+    def blank(self, baseband, frame_stride=None):
+        """mgpu_blank_dev, the stage on its own: baseband complex128 [F, frame_samples] (or [F, frame_stride] with a frame_stride larger than
+        the frame, of which each row's first frame_samples are the frame) -> (blanked complex128 [F, frame_samples], report [F]); with the
+        parameters last set, whether or not the mode is on."""
+        width = self.frame_samples if frame_stride is None else int(frame_stride)
+        bb = np.ascontiguousarray(baseband, np.complex128).reshape(-1, width)
+        F = bb.shape[0]
+        out, rep = np.zeros((F, self.frame_samples), np.complex128), np.zeros(F, BLANKER_REPORT_DTYPE)
+        lib = self.lib
+        lib.mgpu_device_malloc.restype = C.c_void_p
+        lib.mgpu_device_malloc.argtypes = [C.c_void_p, C.c_size_t]
+        lib.mgpu_device_free.argtypes = [C.c_void_p, C.c_void_p]
+        lib.mgpu_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mgpu_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mgpu_blank_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mgpu_context_stream.restype = C.c_void_p
+        lib.mgpu_context_stream.argtypes = [C.c_void_p]
+        if F == 0:
+            return out, rep
+        bufs = [lib.mgpu_device_malloc(self.h, a.nbytes) for a in (bb, out, rep)]
+        try:
+            if not all(bufs):
+                raise MgpuError("mgpu_device_malloc failed")
+            s = lib.mgpu_context_stream(self.h)
+            self._ck(lib.mgpu_copy_to_device(self.h, bufs[0], _ptr(bb), bb.nbytes, s))
+            self._ck(lib.mgpu_blank_dev(self.h, bufs[0], F, 0 if frame_stride is None else width, bufs[1], bufs[2], s))
+            self._ck(lib.mgpu_copy_to_host(self.h, _ptr(out), bufs[1], out.nbytes, s))
+            self._ck(lib.mgpu_copy_to_host(self.h, _ptr(rep), bufs[2], rep.nbytes, s))
+        finally:
+            for b in bufs:
+                if b:
+                    lib.mgpu_device_free(self.h, b)
+        return out, rep
 
     # ---- host-buffer entry points -------------------------------------------------------------
     def receive(self, baseband, taps=False, want_llr=False):

@@ -35,6 +35,16 @@ def ladder(text, S):
     return pts, np.array([pts[s * len(pts) // S] for s in range(S)])
 
 
+def _blanker(text):
+    """--blanker: the spec as RxPhy.set_blanker takes it, checked by the library's one parser"""
+    from mercury_amd import parse_blanker
+    try:
+        parse_blanker(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _demapper(text):
     """--demapper: the spec as RxPhy.set_demapper takes it, checked by the library's one parser"""
     from mercury_amd import parse_demapper
@@ -177,6 +187,8 @@ def main():
     ap.add_argument("--demapper", default="maxlog", type=_demapper,
                     help="csi: LLRs weighted by |H|^2 per cell; nmap[:band=2,smooth=1]: those divided by a noise factor per carrier and per symbol (include/mercury_demapper.h)")
     ap.add_argument("--cfo", default="off", choices=["off", "pilots"], help="pilots: every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)")
+    ap.add_argument("--blanker", default="off", type=_blanker,
+                    help="median[:thr=24,guard=4,share=0.125]: every frame through the median-gated impulse blanker ahead of the front-end (include/mercury_blanker.h)")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--compare", action="store_true", help="simulator and baseline alternating, --repeats times each")
@@ -193,6 +205,7 @@ def main():
     rx = RxPhy(a.cfg, max_iters=a.max_iters, max_batch=a.max_batch or a.links)
     rx.set_demapper(a.demapper)
     rx.set_cfo(a.cfo)
+    rx.set_blanker(a.blanker)
     if a.stream_bench:
         stream_bench(rx, a, info)
         rx.close()
@@ -216,7 +229,7 @@ def main():
                                       "delivered_share": d / max(1, int(c["frames_sent"][m].sum()))}))
             rates[which].append(sim_seconds / wall)
     out = {"cfg": a.cfg, "links": a.links, "channel": a.channel, "gap_hops": a.gap_hops, "simulated_seconds_per_link": hops * p["symbol_period"] / FS,
-           "max_iters": a.max_iters, "ladder": a.ladder, "demapper": a.demapper, "cfo": a.cfo}
+           "max_iters": a.max_iters, "ladder": a.ladder, "demapper": a.demapper, "cfo": a.cfo, "blanker": a.blanker}
     if a.ladder:
         by, frames = rx.ladder_counters()
         out["decoded_by_rung"], out["ladder_frames"] = [int(v) for v in by], frames
