@@ -353,6 +353,10 @@ int mgpu_debug_p2b_variant(int variant);
  * complex samples. variant 0: one wavefront per span; 1: one lane per span (what receive_byte launches from 4096 spans up). */
 int mgpu_debug_span_energy(mgpu_ctx* ctx, const double* bb, int W, int size, const int* wv, const int* off, int n, int len, int variant, double* sum,
                            int* cnt);
+/* Test hook (host only, no GPU): the fp64 sum-product decoder's bin tables for the built-in code with K message bits, placed afresh on every
+ * call. dims: padded slots S (64 per bin), mask row length DM, table rounds, N, E, P. Arrays may be NULL (ask for the sizes first):
+ * sadr [(rounds+1)*1024][2], bhead [(rounds+1)*16][4], bmask [rounds*16][DM]. Returns 0, or 1 for an unknown K. */
+int mgpu_debug_spa_bins(int K, int dims[6], uint32_t* sadr, uint64_t* bhead, uint64_t* bmask);
 /* test hook: evaluates the decoder's device tanh/atanh (csrc/spa_math.h) on n host doubles so the tests
  * can compare them bit for bit with the libm the reference calls (ldpc_decoder_SPA.cc:145,156).
  * atanh_out[i] is 0 where |in[i]| >= 1. */

@@ -114,6 +114,124 @@ std::vector<uint8_t> make_pilot_lattice(int Nsymb, int Nc, int Dy) {
     return t;
 }
 
+// ---- bins of the fp64 sum-product kernel -------------------------------------------------------------------------------------------
+// One wavefront owns a bin of 64 slots and every edge of the checks in it, so checks are packed whole. A bin-iteration costs the same
+// instruction stream whatever the bin holds, so the first cost is the NUMBER of bins; the second is the product walk, which runs for the
+// bin's largest check degree in groups of q steps (pairs for the 16-step kernels, quads for the 48-step one): sum over bins of
+// ceil(maxdeg / q). First-fit decreasing is good at the second and leaves one bin too many where a degree does not divide 64 (seven checks
+// of degree 9 fill 63 slots, and nothing of one slot exists to close the gap): rates 1/16, 6/16 and 8/16 of the built-in codes.
+// pack_dense fills bin after bin towards a given number of bins. A bin is opened by the largest check left (so bins come out in
+// non-increasing order of walk length, which the on-demand bin handout relies on) and then filled, among the fills the slack still allows,
+// by the one that takes the most slots from the opener's own walk class (degrees of the same ceil(d / q): they cost no step), then the most
+// from the class below, and so on; inside a class larger degrees first. Slack = bins * 64 - edges is spent where it buys density in a high
+// class (seven 9s and a gap, not six 9s, an 8 and a 2), and small checks are only drawn to close a gap exactly, beside larger ones, where
+// they raise no bin's maximum. A fill that put one large check among small ones would lengthen that bin's walk: the opener rule excludes it.
+// pack_spa_bins keeps first-fit decreasing unless the dense packing has fewer bins AND no more walk groups by either group size: the tables
+// of a code that is at its minimum already do not change. Deterministic: counts and the stable degree order only.
+typedef std::vector<std::vector<uint32_t>> SpaBins;
+
+static SpaBins pack_ffd(const uint8_t* cdeg, const std::vector<uint32_t>& order) {
+    std::vector<int> fill;                       // used slots per bin
+    SpaBins members;                             // checks per bin
+    for (uint32_t c : order) {
+        const int d = cdeg[c];
+        size_t b = 0;
+        for (; b < fill.size(); ++b) if (fill[b] + d <= 64) break;
+        if (b == fill.size()) { fill.push_back(0); members.emplace_back(); }
+        fill[b] += d;
+        members[b].push_back(c);
+    }
+    return members;
+}
+
+static long spa_walk_groups(const uint8_t* cdeg, const SpaBins& bins, int q) {
+    long w = 0;
+    for (const auto& bin : bins) {
+        int mx = 0;
+        for (uint32_t c : bin) mx = std::max(mx, int(cdeg[c]));
+        w += (mx + q - 1) / q;
+    }
+    return w;
+}
+
+static bool pack_dense(const uint8_t* cdeg, const std::vector<uint32_t>& order, size_t nb, int q, SpaBins& out) {
+    int cnt[65] = {0};
+    size_t next[65];                             // order[] is sorted by degree: the checks of one degree are a run, handed out front to back
+    long edges = 0, left = 0;
+    for (size_t i = order.size(); i-- > 0;) {
+        const int d = cdeg[order[i]];
+        if (d == 0) return false;                // an empty check has no place of its own: first-fit decreasing's business
+        ++cnt[d]; next[d] = i; edges += d; ++left;
+    }
+    long slack = long(nb) * 64 - edges;
+    if (slack < 0) return false;
+    out.clear();
+    bool below[65][65], in_class[66][65];        // below[d][s]: s slots can be filled with checks of degree <= d; in_class[i][s]: with the first i degrees of a class
+    auto take = [&](int d, int k) { for (; k > 0; --k) { out.back().push_back(order[next[d]++]); --cnt[d]; --left; } };
+    while (left > 0) {
+        if (out.size() == nb) return false;
+        int m = 64;
+        while (!cnt[m]) --m;
+        out.emplace_back();
+        take(m, 1);
+        const int room = 64 - m;
+        for (int s = 0; s <= room; ++s) below[0][s] = s == 0;
+        for (int d = 1; d <= m; ++d)
+            for (int s = 0; s <= room; ++s) {
+                below[d][s] = false;
+                for (int k = 0; k <= cnt[d] && k * d <= s && !below[d][s]; ++k) below[d][s] = below[d - 1][s - k * d];
+            }
+        int t = -1;                              // slots still to fill in this bin; chosen with the opener's class, then fixed
+        for (int c = (m + q - 1) / q; c >= 1 && t != 0; --c) {
+            const int lo = q * (c - 1), hi = std::min(q * c, m), nd = hi - lo, lim = t < 0 ? room : t;
+            for (int s = 0; s <= lim; ++s) in_class[0][s] = s == 0;
+            for (int i = 1; i <= nd; ++i)
+                for (int s = 0; s <= lim; ++s) {
+                    const int d = lo + i;
+                    in_class[i][s] = false;
+                    for (int k = 0; k <= cnt[d] && k * d <= s && !in_class[i][s]; ++k) in_class[i][s] = in_class[i - 1][s - k * d];
+                }
+            int sc = -1;                         // slots this class supplies
+            if (t < 0) {
+                for (int tt = room; tt >= 0 && room - tt <= slack; --tt)
+                    for (int s = tt; s > sc; --s)
+                        if (in_class[nd][s] && below[lo][tt - s]) { sc = s; t = tt; break; }
+                if (sc < 0) return false;        // unreachable (tt = 0 always fits) unless the slack is spent and no exact fill is left
+                slack -= room - t;
+            } else {
+                for (int s = t; s >= 0 && sc < 0; --s)
+                    if (in_class[nd][s] && below[lo][t - s]) sc = s;
+            }
+            t -= sc;
+            for (int i = nd; i >= 1; --i) {
+                const int d = lo + i;
+                int k = std::min(cnt[d], sc / d);
+                while (!in_class[i - 1][sc - k * d]) --k;
+                take(d, k);
+                sc -= k * d;
+            }
+        }
+    }
+    return true;
+}
+
+static SpaBins pack_spa_bins(const uint8_t* cdeg, const std::vector<uint32_t>& order) {
+    long edges = 0;
+    int maxdeg = 0;
+    for (uint32_t c : order) {
+        if (cdeg[c] > 64) throw std::runtime_error("check degree exceeds a wavefront");
+        edges += cdeg[c];
+        maxdeg = std::max(maxdeg, int(cdeg[c]));
+    }
+    SpaBins ffd = pack_ffd(cdeg, order);
+    const long w2 = spa_walk_groups(cdeg, ffd, 2), w4 = spa_walk_groups(cdeg, ffd, 4);
+    for (size_t nb = size_t(std::max(1l, (edges + 63) / 64)); nb < ffd.size(); ++nb) {
+        SpaBins dense;
+        if (pack_dense(cdeg, order, nb, maxdeg > 16 ? 4 : 2, dense) && spa_walk_groups(cdeg, dense, 2) <= w2 && spa_walk_groups(cdeg, dense, 4) <= w4) return dense;
+    }
+    return ffd;
+}
+
 static LdpcGraph load_graph_uncached(int K, const uint8_t* blob, size_t size) {
     auto rd32 = [&](size_t off) { uint32_t x; if (off + 4 > size) throw std::runtime_error("LDPC table blob truncated"); std::memcpy(&x, blob + off, 4); return x; };
     if (size < 12 || std::memcmp(blob, "MLDP", 4) != 0 || rd32(4) != 1) throw std::runtime_error("LDPC table blob: bad magic/version");
@@ -157,22 +275,12 @@ static LdpcGraph load_graph_uncached(int K, const uint8_t* blob, size_t size) {
         }
         g.vptr[N] = s;
         if (s != E) throw std::runtime_error("LDPC table blob: edge count mismatch");
-        // ---- wave-private bins (first-fit decreasing over check degrees) ----------------------
+        // ---- wave-private bins: whole checks in 64-slot bins, as few bins as whole checks allow (pack_spa_bins above) ----------------------
         std::vector<uint32_t> order(P);
         for (uint32_t c = 0; c < P; ++c) order[c] = c;
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cdeg[a] > cdeg[b]; });
-        std::vector<int> fill;                       // used slots per bin
-        std::vector<std::vector<uint32_t>> members;  // checks per bin
-        for (uint32_t c : order) {
-            const int d = cdeg[c];
-            if (d > 64) throw std::runtime_error("check degree exceeds a wavefront");
-            size_t b = 0;
-            for (; b < fill.size(); ++b) if (fill[b] + d <= 64) break;
-            if (b == fill.size()) { fill.push_back(0); members.emplace_back(); }
-            fill[b] += d;
-            members[b].push_back(c);
-        }
-        g.S = int(fill.size()) * 64;
+        const std::vector<std::vector<uint32_t>> members = pack_spa_bins(cdeg, order);  // checks per bin
+        g.S = int(members.size()) * 64;
         if (g.S >= 8192) throw std::runtime_error("padded edge count exceeds the 13-bit slot field");
         std::vector<uint32_t> slot_of_edge(E);
         for (size_t b = 0; b < members.size(); ++b) {
@@ -808,6 +916,23 @@ ModeTables build_mode_tables(int cfg, int mfsk_ctrl_mode, const uint8_t* blob, s
     t.graph = load_graph(t.K, blob, blob_size);
     if (t.graph.P != t.P) throw std::runtime_error("LDPC graph does not match the mode");
     return t;
+}
+
+// Test hook (host only): the fp64 sum-product kernel's bin tables for the built-in code with K message bits, placed afresh on every call (not
+// through load_graph's cache, so two calls show that the placement is deterministic). dims: S, DM, table rounds, N, E, P. The arrays may be
+// NULL (sizes first): sadr [(rounds+1)*1024*2], bhead [(rounds+1)*64], bmask [rounds*16*DM].
+extern "C" const unsigned char mgpu_ldpc_blob[];
+extern "C" const unsigned long mgpu_ldpc_blob_size;
+extern "C" int mgpu_debug_spa_bins(int K, int dims[6], uint32_t* sadr, uint64_t* bhead, uint64_t* bmask) {
+    if (!dims) return 1;
+    try {
+        const LdpcGraph g = load_graph_uncached(K, mgpu_ldpc_blob, mgpu_ldpc_blob_size);
+        dims[0] = g.S; dims[1] = g.DM; dims[2] = int(g.bmask.size() / (16 * size_t(g.DM))); dims[3] = g.N; dims[4] = g.E; dims[5] = g.P;
+        if (sadr) std::memcpy(sadr, g.sadr.data(), g.sadr.size() * sizeof(uint32_t));
+        if (bhead) std::memcpy(bhead, g.bhead.data(), g.bhead.size() * sizeof(uint64_t));
+        if (bmask) std::memcpy(bmask, g.bmask.data(), g.bmask.size() * sizeof(uint64_t));
+        return 0;
+    } catch (const std::exception&) { return 1; }
 }
 
 }  // namespace mgpu

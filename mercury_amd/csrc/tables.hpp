@@ -43,7 +43,7 @@ struct LdpcGraph {
     std::vector<uint16_t> cvar;    // [E]   variable of edge e
     std::vector<uint32_t> vptr;    // [N+1] first slot of each variable
     std::vector<uint16_t> vedge;   // [E]   edge index of (variable, slot) in the reference's slot order
-    // wave-private layout for the sum-product kernel: whole checks bin-packed (first-fit decreasing)
+    // wave-private layout for the sum-product kernel: whole checks bin-packed (tables.cpp pack_spa_bins: fewest bins, then shortest walks)
     // into 64-slot bins so that one wavefront owns every edge of the checks it updates
     int S = 0;                     // padded slot count = 64 * bins
     std::vector<uint32_t> vinfo;   // [N][8] (6 used) variable | deg<<11, then 10 u16 padded-slot indices; rows sorted by degree (descending); host only: vinfo2 is its device form

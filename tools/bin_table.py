@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Per-bin table of the fp64 sum-product kernel's layout (first-fit decreasing of whole checks into 64-slot bins, tables.cpp: load_graph)
-for one LDPC rate: the checks' degrees, lanes in use, product-walk steps (= the largest degree).   tools/bin_table.py [K=1400]"""
+"""Per-bin table of whole checks packed into 64-slot bins by FIRST-FIT DECREASING for one LDPC rate: the checks' degrees, lanes in use,
+product-walk steps (= the largest degree). This is the baseline the fp64 sum-product kernel's layout is held against (tables.cpp:
+pack_spa_bins keeps it unless a denser packing has fewer bins and no longer walks - rates 1/16, 6/16 and 8/16 of the built-in codes); the
+layout the library really builds is read back through mgpu_debug_spa_bins (tests/test_spa_packing_host.py).   tools/bin_table.py [K=1400]"""
 import struct
 import sys
 import os
