@@ -65,18 +65,8 @@ int mgpu_set_cfo(mgpu_ctx* c, int cfo) {
                 K.d_pair = std::move(d_pair); K.d_first = std::move(d_first); K.d_step = std::move(d_step);
                 K.arg = MgpuCfo{};
                 K.arg.pair = K.d_pair; K.arg.first = K.d_first; K.arg.Dy = t.xp.Dy;
-                // the context's own square window as the rectangular form takes it
-                K.own = MgpuLsRect{};
-                K.own.weight = c->dev.ls_weight;
-                K.own.hw_f = K.own.hw_t = t.lsw / 2;
-                K.own.lattice = c->dev.regular_lattice;
             }
-            // the new kernels' LDS limits: the plain carve for the one, the channel-aware demapper's for the other (where that fits at all:
-            // mgpu_set_demapper refuses a geometry for which it does not)
-            const size_t csi_lds = mgpu_frontend_csi_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads);
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_fe)));
-            if (csi_lds <= size_t(160) * 1024)
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_csi_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(csi_lds)));
+            frontend_raise_lds_limits(c);
             HIPCK(hipMemset(K.d_step.p, 0, size_t(c->max_batch > 0 ? c->max_batch : 1) * sizeof(double)));
         }
         K.mode = cfo;

@@ -204,7 +204,12 @@ void ctx_upload(mgpu_ctx* c, const Plan& p) {
     auto lds_limit = [](auto kernel, size_t bytes) {
         HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
     };
-    if (t.mfsk_M == 0) lds_limit(fe_kernel(c->fe_threads), c->lds_fe);
+    if (t.mfsk_M == 0) lds_limit(mgpu_frontend_form_kernel(c->fe_threads, 0), c->lds_fe);     // the plain form alone: an option's setter raises the others (frontend_raise_lds_limits)
+    // the context's own square LS window as the front-end's rectangular forms take it
+    c->own_window = MgpuLsRect{};
+    c->own_window.weight = d.ls_weight;
+    c->own_window.hw_f = c->own_window.hw_t = t.lsw / 2;
+    c->own_window.lattice = d.regular_lattice;
     lds_limit(mgpu_txgen_kernel, c->lds_tx);
     lds_limit(mgpu_tsync_metric_fine_kernel_r4, mgpu_tsync_fine_geometry(4).lds_bytes);
     lds_limit(mgpu_tsync_metric_fine_kernel_r8, mgpu_tsync_fine_geometry(8).lds_bytes);

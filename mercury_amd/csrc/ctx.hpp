@@ -30,39 +30,17 @@ extern "C" const unsigned long mgpu_ldpc_blob_size;
 
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads);
-extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi);
 extern "C" size_t mgpu_frontend_nmap_lds_bytes(int G, int nPilots, int nBits, int threads);
+// The OFDM front-end's kernels stay in frontend.hip; these two name them. A form is a set of MGPU_FE_* bits (ls_rect.h), and every kernel has
+// the signature (MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuFeOpt) - but the form RECT | CSI, which takes
+// (..., MgpuTapsDev, MgpuLsRect, MgpuCsi): frontend.hip FE_FORMS says why. A form that is none of the 13: null, 0.
+extern "C" const void* mgpu_frontend_form_kernel(int threads, unsigned form);
+extern "C" size_t mgpu_frontend_form_lds_bytes(int G, int nPilots, int nBits, int threads, unsigned form);
 extern "C" size_t mgpu_spa_lds_bytes(int E, int N);
 extern "C" size_t mgpu_gbf_lds_bytes(int N);
 extern "C" size_t mgpu_spa_fast_lds_bytes(int Sg, int N);
 extern "C" size_t mgpu_txgen_lds_bytes(int G);
 
-extern "C" __global__ void mgpu_frontend_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
-extern "C" __global__ void mgpu_frontend_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
-extern "C" __global__ void mgpu_frontend_rect_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
-extern "C" __global__ void mgpu_frontend_rect_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
-extern "C" __global__ void mgpu_frontend_csi_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
-extern "C" __global__ void mgpu_frontend_csi_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
-extern "C" __global__ void mgpu_frontend_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
-extern "C" __global__ void mgpu_frontend_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
-extern "C" __global__ void mgpu_frontend_csi_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
-extern "C" __global__ void mgpu_frontend_csi_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
-extern "C" __global__ void mgpu_frontend_wiener_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_csi_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_csi_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_csi_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_csi_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_nmap_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap);
-extern "C" __global__ void mgpu_frontend_nmap_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap);
-extern "C" __global__ void mgpu_frontend_nmap_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo);
-extern "C" __global__ void mgpu_frontend_nmap_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo);
-extern "C" __global__ void mgpu_frontend_wiener_nmap_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_nmap_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_nmap_cfo_kernel(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo, MgpuWiener);
-extern "C" __global__ void mgpu_frontend_wiener_nmap_cfo_kernel_t1024(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo, MgpuWiener);
 extern "C" __global__ void mgpu_ladder_select_kernel(const MgpuStatsDev*, int, int, int*, int*, int*, unsigned long long*);
 extern "C" __global__ void mgpu_ladder_merge_kernel(const int*, int, int, int, int, const float*, const float*, const float*, const double*, const uint8_t*,
                                                     const MgpuStatsDev*, float*, float*, float*, double*, uint8_t*, MgpuStatsDev*, int*, unsigned long long*);
@@ -225,13 +203,10 @@ struct Diversity {
 // The context's demapper (include/mercury_demapper.h; demapper.hip). MGPU_DEMAP_CSI: every front-end launch of the fused span is the CSI form.
 struct Demapper {
     int mode = MGPU_DEMAP_MAXLOG;
-    size_t lds = 0;                                 // the CSI form's LDS carve
-    MgpuLsRect own{};                               // the context's own square window as that (rectangular) form takes it
     MgpuCsi arg{};
     DevArray<uint16_t> d_sym_data;                  // arg.sym_data; made with the first MGPU_DEMAP_CSI or MGPU_DEMAP_NMAP
     // MGPU_DEMAP_NMAP: every front-end launch of the fused span is a noise-map form (a CSI form with per-carrier and per-symbol noise factors)
     mgpu_demapper_params params{2.0, 1};            // as set; the defaults until then
-    size_t nmap_lds = 0;                            // the noise-map forms' LDS carve
     MgpuNmap nmap{};                                // lists, band, smooth; fc / fs / rows are set per launch
     DevArray<uint16_t> d_nmap_idx;                  // car_list, car_first, sym_first; made with the first MGPU_DEMAP_NMAP
     DevArray<double> d_fc, d_fs;                    // [max_batch][Nc], [max_batch][Nsymb] the factors of the last call's frames, by the frame's row
@@ -241,7 +216,6 @@ struct Demapper {
 // is a CFO form (with or without the channel-aware demapper).
 struct Cfo {
     int mode = MGPU_CFO_OFF;
-    MgpuLsRect own{};                               // the context's own square window as the (rectangular) CFO forms take it
     MgpuCfo arg{};                                  // pair, first, Dy; step / step_rows are set per launch
     DevArray<uint16_t> d_pair, d_first;             // made with the first MGPU_CFO_PILOTS
     DevArray<double> d_step;                        // [max_batch] radians per symbol, by the frame's row in the context's workspaces
@@ -344,6 +318,7 @@ struct mgpu_ctx {
         bool ev_fe[kEvRing]{};          // whether the front-end ran in that slot
     } kt;
     size_t lds_fe = 0, lds_dec = 0, lds_tx = 0;
+    MgpuLsRect own_window{};        // the context's own square LS window as the front-end's rectangular forms take it (frames = NULL)
     int fe_threads = 512;           // front-end workgroup size: 1024 when the 512-thread carve is more than half a compute unit's LDS (no mode or golden geometry today: 1024 runs under MERCURY_FE_THREADS only)
     DecoderKernel spa_kernel = nullptr;
     int dec_threads = 1024;         // workgroup size of the decoder kernel
@@ -366,37 +341,6 @@ template <typename Fn> void for_frame_chunks(int F, Fn&& fn) {      // fn(first 
 }
 template <typename T> T* at(T* p, size_t off) { return p ? p + off : nullptr; }
 
-using FrontendKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev);
-inline FrontendKernel fe_kernel(int threads) { return threads == 1024 ? mgpu_frontend_kernel_t1024 : mgpu_frontend_kernel; }
-using FrontendRectKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect);
-inline FrontendRectKernel fe_rect_kernel(int threads) { return threads == 1024 ? mgpu_frontend_rect_kernel_t1024 : mgpu_frontend_rect_kernel; }
-using FrontendCsiKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi);
-inline FrontendCsiKernel fe_csi_kernel(int threads) { return threads == 1024 ? mgpu_frontend_csi_kernel_t1024 : mgpu_frontend_csi_kernel; }
-using FrontendCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo);
-inline FrontendCfoKernel fe_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_cfo_kernel_t1024 : mgpu_frontend_cfo_kernel; }
-using FrontendCsiCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo);
-inline FrontendCsiCfoKernel fe_csi_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_csi_cfo_kernel_t1024 : mgpu_frontend_csi_cfo_kernel; }
-
-// the Wiener forms (frontend.hip WIENER): plain, with the carrier-offset stage, with the channel-aware demapper, with both
-using FrontendWienerKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuWiener);
-inline FrontendWienerKernel fe_wiener_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_kernel_t1024 : mgpu_frontend_wiener_kernel; }
-using FrontendWienerCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCfo, MgpuWiener);
-inline FrontendWienerCfoKernel fe_wiener_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_cfo_kernel_t1024 : mgpu_frontend_wiener_cfo_kernel; }
-using FrontendWienerCsiKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuWiener);
-inline FrontendWienerCsiKernel fe_wiener_csi_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_csi_kernel_t1024 : mgpu_frontend_wiener_csi_kernel; }
-using FrontendWienerCsiCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuCfo, MgpuWiener);
-inline FrontendWienerCsiCfoKernel fe_wiener_csi_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_csi_cfo_kernel_t1024 : mgpu_frontend_wiener_csi_cfo_kernel; }
-
-// the noise-map demapper's forms (frontend.hip NMAP): plain, with the carrier-offset stage, and both again with the Wiener estimate
-using FrontendNmapKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap);
-inline FrontendNmapKernel fe_nmap_kernel(int threads) { return threads == 1024 ? mgpu_frontend_nmap_kernel_t1024 : mgpu_frontend_nmap_kernel; }
-using FrontendNmapCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo);
-inline FrontendNmapCfoKernel fe_nmap_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_nmap_cfo_kernel_t1024 : mgpu_frontend_nmap_cfo_kernel; }
-using FrontendWienerNmapKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuWiener);
-inline FrontendWienerNmapKernel fe_wiener_nmap_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_nmap_kernel_t1024 : mgpu_frontend_wiener_nmap_kernel; }
-using FrontendWienerNmapCfoKernel = void (*)(MgpuDev, const double*, int, float*, float*, float*, double*, MgpuTapsDev, MgpuLsRect, MgpuCsi, MgpuNmap, MgpuCfo, MgpuWiener);
-inline FrontendWienerNmapCfoKernel fe_wiener_nmap_cfo_kernel(int threads) { return threads == 1024 ? mgpu_frontend_wiener_nmap_cfo_kernel_t1024 : mgpu_frontend_wiener_nmap_cfo_kernel; }
-
 // whether the caller wants a tap with a row per frame (a launch's kernel writes them from row 0: one launch per call then)
 inline bool wants_frame_taps(const MgpuTapsDev& t) { return t.grid || t.H || t.eq || t.syms || t.llr_demod || t.variance || t.agc_gain; }
 
@@ -418,11 +362,15 @@ void launch_frontend(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& ta
 void launch_decoder(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
                     const float* d_var, const float* d_snrvar, hipStream_t s);
 // The same launches without the timing events, as the ladder's retries run them: the kernel timings describe rung 0.
-// rect: null = rung 0 (the ladder's first window where it is not the context's own, else the default kernel); a retry's window otherwise,
-// (with MGPU_DEMAP_CSI all of them are the CSI kernel, the context's own window included, with MGPU_DEMAP_NMAP a noise-map kernel; with MGPU_CFO_PILOTS all of them are a CFO kernel)
+// rect: null = rung 0 (the ladder's first window where it is not the context's own, else the context's own); a retry's window otherwise,
 // whose `frames` list names the frame each row of the compact outputs in io belongs to. rung: the ladder's rung the launch is (0 without a
-// ladder): its kind, which the ladder keeps, picks the LS or the Wiener forms.
+// ladder). The launch's form (ls_rect.h) follows from the context: WIENER from the rung's kind, which the ladder keeps, CSI and NMAP from the
+// demapper, CFO from the carrier-offset setting, RECT with any of them or a window other than the context's own.
 void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& taps, const MgpuLsRect* rect, hipStream_t s, int rung = 0);
+// Lets every form's kernel of the context's workgroup size use its whole LDS carve (a BPSK geometry's exceeds the default limit). The setter
+// of each option calls it, so that no setter has to know the forms its option makes with the others. 13 hipFuncSetAttribute calls
+// on every such call of a setter, where each setter used to make one to four on its first: idempotent, and setters are not on the receive path.
+void frontend_raise_lds_limits(mgpu_ctx* c);
 void decoder_untimed(mgpu_ctx* c, const float* d_llr, int F, uint8_t* d_bits, int* d_iters, uint8_t* d_payload, MgpuStatsDev* d_stats,
                      const float* d_var, const float* d_snrvar, hipStream_t s);
 // The estimator ladder behind rung 0 (ladder.hip), called by launch_span alone: marks each frame's rung and, rung by rung, re-runs the

@@ -90,16 +90,10 @@ int mgpu_set_demapper_ex(mgpu_ctx* c, int demapper, const mgpu_demapper_params* 
                 sym_data[size_t(k)] = uint16_t(i);
             }
             DevArray<uint16_t> d = upload(sym_data);
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_csi_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
             D.d_sym_data = std::move(d);
             D.arg.sym_data = D.d_sym_data;
-            D.lds = lds;
-            // the context's own square window as the rectangular form takes it
-            D.own = MgpuLsRect{};
-            D.own.weight = c->dev.ls_weight;
-            D.own.hw_f = D.own.hw_t = t.lsw / 2;
-            D.own.lattice = c->dev.regular_lattice;
         }
+        if (demapper != MGPU_DEMAP_MAXLOG) frontend_raise_lds_limits(c);
         if (demapper == MGPU_DEMAP_NMAP) {
             const size_t rows = size_t(c->max_batch > 0 ? c->max_batch : 1);
             if (!D.d_nmap_idx) {
@@ -112,17 +106,11 @@ int mgpu_set_demapper_ex(mgpu_ctx* c, int demapper, const mgpu_demapper_params* 
                 idx.insert(idx.end(), L.sym_first.begin(), L.sym_first.end());
                 DevArray<uint16_t> d_idx = upload(idx);
                 DevArray<double> d_fc(rows * size_t(t.Nc) * sizeof(double)), d_fs(rows * size_t(t.Nsymb) * sizeof(double));
-                const int bytes = int(nmap_lds);
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_nmap_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_nmap_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_nmap_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_nmap_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
                 D.d_nmap_idx = std::move(d_idx); D.d_fc = std::move(d_fc); D.d_fs = std::move(d_fs);
                 D.nmap = MgpuNmap{};
                 D.nmap.car_list = D.d_nmap_idx;
                 D.nmap.car_first = D.d_nmap_idx + at_car;
                 D.nmap.sym_first = D.d_nmap_idx + at_sym;
-                D.nmap_lds = nmap_lds;
             }
             HIPCK(hipMemset(D.d_fc.p, 0, rows * size_t(t.Nc) * sizeof(double)));
             HIPCK(hipMemset(D.d_fs.p, 0, rows * size_t(t.Nsymb) * sizeof(double)));

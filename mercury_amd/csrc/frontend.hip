@@ -113,33 +113,36 @@ __host__ __device__ inline FeCarve fe_carve_with(int G, int nPilots, int nBits, 
     c.total = fixed + c.work;
     return c;
 }
-__host__ __device__ inline FeCarve fe_carve(int G, int nPilots, int nBits, int FE_WAVES) { return fe_carve_with(G, nPilots, nBits, FE_WAVES, 0); }
-extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve(G, nPilots, nBits, threads / 64).total; }
 // The channel-aware demapper's form (CSI below; include/mercury_demapper.h) keeps two more arrays in the work area: the terms of its own
 // noise variance, one double per pilot, and |h|^2 of every data cell as a float, in de-framed order. Both are written after the FFTs, whose
 // work areas they share, so the carve grows only where Hp + rsz + these exceed the FFT areas: 5.6 KB in the BPSK modes (73.6 -> 79.4 KB, still
 // two workgroups per compute unit - with a float per CELL it would be 82.6 KB and one), nothing in the others.
 __host__ __device__ inline size_t fe_csi_var_bytes(int nPilots) { return (size_t(8) * nPilots + 15) & ~size_t(15); }
-__host__ __device__ inline FeCarve fe_carve_csi(int G, int nPilots, int nBits, int FE_WAVES) {
-    return fe_carve_with(G, nPilots, nBits, FE_WAVES, fe_csi_var_bytes(nPilots) + ((size_t(4) * (G - nPilots) + 15) & ~size_t(15)));
-}
-extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve_csi(G, nPilots, nBits, threads / 64).total; }
-// The Wiener forms (WIENER below; include/mercury_estimator.h MGPU_RUNG_WIENER) keep nothing of their own: the time pass writes Hp, the
-// frequency pass the signed pilots' area (16 nPilots bytes of rsz), so their carve is the rectangular form's, or the CSI form's with that demapper.
-extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi) {
-    return (csi ? fe_carve_csi(G, nPilots, nBits, threads / 64) : fe_carve(G, nPilots, nBits, threads / 64)).total;
-}
+__host__ __device__ inline size_t fe_csi_h2_bytes(int G, int nPilots) { return (size_t(4) * (G - nPilots) + 15) & ~size_t(15); }
 // The noise-map demapper's form (NMAP below; include/mercury_demapper.h MGPU_DEMAP_NMAP) is the CSI form with one more piece behind |h|^2: the
 // carrier sums S_c (64 doubles), the symbol sums U_s (Nsymb doubles) and the two scales a_c (64 floats) and b_s (Nsymb floats). Everything
 // before it in the work area is in use when it is written (Hp by the data cells, the three term arrays by their sums, |h|^2 being filled) and
 // the LLRs take the terms' place while a_c and b_s are read, so it is a piece of its own: 1,056 bytes in mode 8, where the FFT work areas
 // cover it, 1,344 more than the CSI carve in the BPSK modes (79,392 -> 80,736 bytes: still two workgroups per compute unit).
 __host__ __device__ inline size_t fe_nmap_bytes(int G) { return (size_t(64) * 12 + size_t(G / 50) * 12 + 15) & ~size_t(15); }
-__host__ __device__ inline FeCarve fe_carve_nmap(int G, int nPilots, int nBits, int FE_WAVES) {
-    return fe_carve_with(G, nPilots, nBits, FE_WAVES, fe_csi_var_bytes(nPilots) + ((size_t(4) * (G - nPilots) + 15) & ~size_t(15)) + fe_nmap_bytes(G));
+// A form's carve (ls_rect.h: the form bits), for the host and for the kernel alike: the noise map's with NMAP, else the CSI form's with CSI,
+// else the plain one. RECT and CFO keep nothing in LDS behind the FFTs, and neither do the Wiener forms (WIENER below;
+// include/mercury_estimator.h MGPU_RUNG_WIENER): the time pass writes Hp, the frequency pass the signed pilots' area (16 nPilots bytes of rsz).
+__host__ __device__ inline FeCarve fe_carve_form(int G, int nPilots, int nBits, int FE_WAVES, unsigned form) {
+    const size_t csi = fe_csi_var_bytes(nPilots) + fe_csi_h2_bytes(G, nPilots);
+    return fe_carve_with(G, nPilots, nBits, FE_WAVES, form & MGPU_FE_NMAP ? csi + fe_nmap_bytes(G) : form & MGPU_FE_CSI ? csi : 0);
 }
-extern "C" size_t mgpu_frontend_nmap_lds_bytes(int G, int nPilots, int nBits, int threads) { return fe_carve_nmap(G, nPilots, nBits, threads / 64).total; }
-// workgroups per compute unit the LDS lets a carve of `bytes` have, counted as fe_carve counts them (blocks of 1280 bytes, 256 of overhead)
+extern "C" size_t mgpu_frontend_form_lds_bytes(int G, int nPilots, int nBits, int threads, unsigned form) {
+    return mgpu_fe_form_valid(form) ? fe_carve_form(G, nPilots, nBits, threads / 64, form).total : 0;
+}
+// the forms' carves by their earlier names, which the host tests call
+extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads) { return mgpu_frontend_form_lds_bytes(G, nPilots, nBits, threads, 0); }
+extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads) { return mgpu_frontend_form_lds_bytes(G, nPilots, nBits, threads, MGPU_FE_RECT | MGPU_FE_CSI); }
+extern "C" size_t mgpu_frontend_wiener_lds_bytes(int G, int nPilots, int nBits, int threads, int csi) {
+    return mgpu_frontend_form_lds_bytes(G, nPilots, nBits, threads, MGPU_FE_RECT | MGPU_FE_WIENER | (csi ? MGPU_FE_CSI : 0));
+}
+extern "C" size_t mgpu_frontend_nmap_lds_bytes(int G, int nPilots, int nBits, int threads) { return mgpu_frontend_form_lds_bytes(G, nPilots, nBits, threads, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_NMAP); }
+// workgroups per compute unit the LDS lets a carve of `bytes` have, counted as fe_carve_with counts them (blocks of 1280 bytes, 256 of overhead)
 extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(160) * 1024 / ((bytes + 256 + 1279) / 1280 * 1280)); }
 
 // RECT: the LS window has a width and a height of its own (`win`, ls_rect.h) instead of T.lsw squared, and the workgroup may take its
@@ -156,16 +159,21 @@ extern "C" int mgpu_frontend_lds_workgroups(size_t bytes) { return int(size_t(16
 // NMAP (with CSI): the noise-map demapper (include/mercury_demapper.h MGPU_DEMAP_NMAP). The CSI form's pilot residuals are
 // also averaged per carrier and per symbol; the LLRs of a cell are scaled by a_c b_s |h|^2 with a_c = 1 / (sigma2 fc(c)), b_s = 1 / fs(s)
 // in place of |h|^2 / sigma2, fc and fs being those means over sigma2, 1 inside the dead band. Its scratch is a piece of the carve of its own.
-template <int FE_THREADS, bool RECT, bool CSI, bool CFO, bool WIENER, bool NMAP>
+template <int FE_THREADS, unsigned FORM>
 __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
                                          float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out,
-                                         const MgpuTapsDev& taps, const MgpuLsRect& win, const MgpuCsi& csi, const MgpuCfo& cfo, const MgpuWiener& wn,
-                                         const MgpuNmap& nm) {
-    static_assert(!NMAP || (CSI && RECT), "the noise-map demapper is a form of the channel-aware one");
+                                         const MgpuTapsDev& taps, const MgpuFeOpt& opt) {
+    static_assert(mgpu_fe_form_valid(FORM), "any option implies RECT, and the noise-map demapper is a form of the channel-aware one");
+    constexpr bool RECT = FORM & MGPU_FE_RECT, CSI = FORM & MGPU_FE_CSI, CFO = FORM & MGPU_FE_CFO, WIENER = FORM & MGPU_FE_WIENER, NMAP = FORM & MGPU_FE_NMAP;
+    [[maybe_unused]] const MgpuLsRect& win = opt.win;
+    [[maybe_unused]] const MgpuCsi& csi = opt.csi;
+    [[maybe_unused]] const MgpuCfo& cfo = opt.cfo;
+    [[maybe_unused]] const MgpuWiener& wn = opt.wn;
+    [[maybe_unused]] const MgpuNmap& nm = opt.nm;
     constexpr int FE_WAVES = FE_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int G = T.G, Nc = 50, Ns = T.Nsymb;
-    const FeCarve carve = NMAP ? fe_carve_nmap(G, T.nPilots, T.nBits, FE_WAVES) : CSI ? fe_carve_csi(G, T.nPilots, T.nBits, FE_WAVES) : fe_carve(G, T.nPilots, T.nBits, FE_WAVES);
+    const FeCarve carve = fe_carve_form(G, T.nPilots, T.nBits, FE_WAVES, FORM);
     c2* grid = reinterpret_cast<c2*>(smem);
     c2* Hp = grid + G;                                              // channel estimate at the pilots, pilot order; Hp and red are the FFT work area first
     c2* fftb = Hp;
@@ -698,179 +706,56 @@ __device__ __forceinline__ void fe_frame(const MgpuDev& T, const double* __restr
 #undef FE_STAMP
 }
 
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<512, false, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
-}
+// The 13 forms, one row each: the kernel's name, the options it is built with, and how the options' arguments reach it. Every row makes
+// the 512- and the 1024-thread kernel; a form reads the members of `opt` that its bits name.
+//   plain ....... the context's own square window and nothing else: the default span
+//   rect ........ a window of its own and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when it is
+//                 not the context's own window, and every later rung on the frames that rung left undecoded
+//   csi, nmap ... every launch of the span while the context's demapper is MGPU_DEMAP_CSI / MGPU_DEMAP_NMAP (include/mercury_demapper.h)
+//   cfo ......... every launch of the span while the context's correction is MGPU_CFO_PILOTS (include/mercury_cfo.h)
+//   wiener ...... a Wiener rung of an estimator ladder, as rung 0 or as a retry (include/mercury_estimator.h MGPU_RUNG_WIENER)
+// OPT: the one signature, the options' arguments in a trailing MgpuFeOpt. WIN_CSI: the csi pair alone takes its two structs as arguments of
+// their own, (..., MgpuTapsDev, MgpuLsRect, MgpuCsi): with the wider argument block, whatever its layout, the compiler gives the pair two
+// more spill slots at 512 threads and a vector register more at 1024 (profiles/frontend_forms.md); frontend_untimed has one `if` for it.
+#define FE_FORMS(X)                                                                                                 \
+    X(mgpu_frontend_kernel, 0, OPT)                                                                                 \
+    X(mgpu_frontend_rect_kernel, MGPU_FE_RECT, OPT)                                                                 \
+    X(mgpu_frontend_csi_kernel, MGPU_FE_RECT | MGPU_FE_CSI, WIN_CSI)                                                \
+    X(mgpu_frontend_cfo_kernel, MGPU_FE_RECT | MGPU_FE_CFO, OPT)                                                    \
+    X(mgpu_frontend_csi_cfo_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_CFO, OPT)                                  \
+    X(mgpu_frontend_wiener_kernel, MGPU_FE_RECT | MGPU_FE_WIENER, OPT)                                              \
+    X(mgpu_frontend_wiener_cfo_kernel, MGPU_FE_RECT | MGPU_FE_CFO | MGPU_FE_WIENER, OPT)                            \
+    X(mgpu_frontend_wiener_csi_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_WIENER, OPT)                            \
+    X(mgpu_frontend_wiener_csi_cfo_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_CFO | MGPU_FE_WIENER, OPT)          \
+    X(mgpu_frontend_nmap_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_NMAP, OPT)                                    \
+    X(mgpu_frontend_nmap_cfo_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_NMAP | MGPU_FE_CFO, OPT)                  \
+    X(mgpu_frontend_wiener_nmap_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_NMAP | MGPU_FE_WIENER, OPT)            \
+    X(mgpu_frontend_wiener_nmap_cfo_kernel, MGPU_FE_RECT | MGPU_FE_CSI | MGPU_FE_NMAP | MGPU_FE_CFO | MGPU_FE_WIENER, OPT)
 
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps) {
-    fe_frame<1024, false, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, MgpuLsRect{}, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
-}
+#define FE_ARGS_OPT MgpuFeOpt opt
+#define FE_PASS_OPT opt
+#define FE_ARGS_WIN_CSI MgpuLsRect win, MgpuCsi csi
+#define FE_PASS_WIN_CSI MgpuFeOpt{win, MgpuNmap{}, MgpuWiener{}, MgpuCfo{}, csi}
+#define FE_KERNEL(name, form, args)                                                                                                        \
+    extern "C" __global__ __launch_bounds__(512, 6) void name(                                                                             \
+        MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out, float* __restrict__ variance_out,              \
+        float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, FE_ARGS_##args) {                         \
+        fe_frame<512, (form)>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, FE_PASS_##args);                  \
+    }                                                                                                                                      \
+    extern "C" __global__ __launch_bounds__(1024, 4) void name##_t1024(                                                                    \
+        MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out, float* __restrict__ variance_out,              \
+        float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, FE_ARGS_##args) {                         \
+        fe_frame<1024, (form)>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, FE_PASS_##args);                 \
+    }
+FE_FORMS(FE_KERNEL)
+#undef FE_KERNEL
 
-// The same body with a rectangular LS window and an optional frame list (include/mercury_estimator.h): rung 0 of an estimator ladder when
-// it is not the context's own window, and every later rung on the frames that rung left undecoded.
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_rect_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<512, true, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_rect_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win) {
-    fe_frame<1024, true, false, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
-}
-
-// The rectangular form with the channel-aware demapper (include/mercury_demapper.h): the plain span (the context's own window passed as a
-// rectangle), rung 0 and every retry of an estimator ladder while the context's demapper is MGPU_DEMAP_CSI.
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<512, true, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi) {
-    fe_frame<1024, true, true, false, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, MgpuNmap{});
-}
-
-// The rectangular form with the residual carrier-offset stage (include/mercury_cfo.h), without and with the channel-aware demapper: the
-// plain span (the context's own window passed as a rectangle), rung 0 and every retry of an estimator ladder while the context's
-// correction is MGPU_CFO_PILOTS.
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_cfo_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
-    fe_frame<512, true, false, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{}, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_cfo_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo) {
-    fe_frame<1024, true, false, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, MgpuWiener{}, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_csi_cfo_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
-    MgpuCfo cfo) {
-    fe_frame<512, true, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_csi_cfo_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
-    MgpuCfo cfo) {
-    fe_frame<1024, true, true, true, false, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, MgpuNmap{});
-}
-
-// The rectangular forms with the separable Wiener estimate in place of the window mean (include/mercury_estimator.h MGPU_RUNG_WIENER): a
-// Wiener rung of an estimator ladder, as rung 0 or as a retry, for each combination of the context's demapper and carrier-offset setting.
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win,
-    MgpuWiener wn) {
-    fe_frame<512, true, false, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win,
-    MgpuWiener wn) {
-    fe_frame<1024, true, false, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, MgpuCfo{}, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_cfo_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo,
-    MgpuWiener wn) {
-    fe_frame<512, true, false, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_cfo_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCfo cfo,
-    MgpuWiener wn) {
-    fe_frame<1024, true, false, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, MgpuCsi{}, cfo, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_csi_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
-    MgpuWiener wn) {
-    fe_frame<512, true, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_csi_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi,
-    MgpuWiener wn) {
-    fe_frame<1024, true, true, false, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_csi_cfo_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuCfo cfo,
-    MgpuWiener wn) {
-    fe_frame<512, true, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, MgpuNmap{});
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_csi_cfo_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuCfo cfo,
-    MgpuWiener wn) {
-    fe_frame<1024, true, true, true, true, false>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, MgpuNmap{});
-}
-
-// The rectangular forms with the noise-map demapper (include/mercury_demapper.h MGPU_DEMAP_NMAP): the plain span, rung 0 and every retry of
-// an estimator ladder while the context's demapper is that one, for each combination of the carrier-offset setting and the rung's kind.
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_nmap_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm) {
-    fe_frame<512, true, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, nm);
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_nmap_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm) {
-    fe_frame<1024, true, true, false, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, MgpuWiener{}, nm);
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_nmap_cfo_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo) {
-    fe_frame<512, true, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, nm);
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_nmap_cfo_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo) {
-    fe_frame<1024, true, true, true, false, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, MgpuWiener{}, nm);
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_nmap_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuWiener wn) {
-    fe_frame<512, true, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, nm);
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_nmap_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuWiener wn) {
-    fe_frame<1024, true, true, false, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, MgpuCfo{}, wn, nm);
-}
-
-extern "C" __global__ __launch_bounds__(512, 6) void mgpu_frontend_wiener_nmap_cfo_kernel(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo, MgpuWiener wn) {
-    fe_frame<512, true, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, nm);
-}
-
-extern "C" __global__ __launch_bounds__(1024, 4) void mgpu_frontend_wiener_nmap_cfo_kernel_t1024(
-    MgpuDev T, const double* __restrict__ baseband, int F, float* __restrict__ llr_out,
-    float* __restrict__ variance_out, float* __restrict__ snr_variance_out, double* __restrict__ eqdata_out, MgpuTapsDev taps, MgpuLsRect win, MgpuCsi csi, MgpuNmap nm, MgpuCfo cfo, MgpuWiener wn) {
-    fe_frame<1024, true, true, true, true, true>(T, baseband, F, llr_out, variance_out, snr_variance_out, eqdata_out, taps, win, csi, cfo, wn, nm);
+// a form's kernel for a workgroup of `threads` (512 or 1024); null when the form is none of the 13
+extern "C" const void* mgpu_frontend_form_kernel(int threads, unsigned form) {
+#define FE_ROW(name, form, args) {(form), reinterpret_cast<const void*>(name), reinterpret_cast<const void*>(name##_t1024)},
+    static const struct { unsigned form; const void *t512, *t1024; } table[] = {FE_FORMS(FE_ROW)};
+#undef FE_ROW
+    for (const auto& row : table)
+        if (row.form == form) return threads == 1024 ? row.t1024 : threads == 512 ? row.t512 : nullptr;
+    return nullptr;
 }

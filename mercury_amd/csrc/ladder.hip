@@ -133,14 +133,12 @@ int mgpu_set_estimator_ladder_ex(mgpu_ctx* c, const mgpu_estimator_rung* rungs, 
     return guard(c, [&] {
         need(n_rungs >= 0 && n_rungs <= MGPU_LADDER_MAX && (rungs || n_rungs == 0), "estimator ladder: 0..MGPU_LADDER_MAX rungs");
         mgpu_ls_window win[MGPU_LADDER_MAX]{};
-        bool any_wiener = false;
         for (int r = 0; r < n_rungs; ++r) {
             need(rungs[r].kind == MGPU_RUNG_LS || rungs[r].kind == MGPU_RUNG_WIENER, "estimator ladder: a rung is MGPU_RUNG_LS or MGPU_RUNG_WIENER");
             if (rungs[r].kind == MGPU_RUNG_WIENER) {
                 const mgpu_wiener_design& d = rungs[r].design;
                 need(mgpu::wiener_design_ok(mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db}),
                      "estimator ladder: a Wiener design needs tau_max > tau_min, doppler_hz >= 0 and snr_db in -20..40, all finite");
-                any_wiener = true;
                 continue;
             }
             win[r].width = window_side(rungs[r].window.width);
@@ -195,19 +193,7 @@ int mgpu_set_estimator_ladder_ex(mgpu_ctx* c, const mgpu_estimator_rung* rungs, 
             if (!L.done) HIPCK(hipEventCreateWithFlags(&L.done.h, hipEventDisableTiming));
             L.d_rung.grow(B * sizeof(int));
             L.d_counters.grow((MGPU_LADDER_MAX + 1) * sizeof(unsigned long long));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_rect_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(c->lds_fe)));
-        }
-        if (any_wiener) {
-            // the Wiener kernels' LDS limits: the plain carve, and the channel-aware demapper's for its forms (where that fits at all:
-            // mgpu_set_demapper refuses a geometry for which it does not)
-            const size_t lds = mgpu_frontend_wiener_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads, 0);
-            const size_t csi_lds = mgpu_frontend_wiener_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads, 1);
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-            HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-            if (csi_lds <= size_t(160) * 1024) {
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_csi_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(csi_lds)));
-                HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_wiener_csi_cfo_kernel(c->fe_threads)), hipFuncAttributeMaxDynamicSharedMemorySize, int(csi_lds)));
-            }
+            frontend_raise_lds_limits(c);
         }
         if (n_rungs > 1) {
             L.d_idx.grow(B * sizeof(int)); L.d_count.grow(sizeof(int));

@@ -36,67 +36,52 @@ void frontend_untimed(mgpu_ctx* c, const SpanIo& io, int F, const MgpuTapsDev& t
         return;
     }
     if (!rect && c->lad.n > 0 && !c->lad.rung0_is_default) rect = &c->lad.win[0];      // rung 0 of an estimator ladder with a window of its own
-    const MgpuWiener* wiener = rung < c->lad.n && c->lad.kind[rung] == MGPU_RUNG_WIENER ? &c->lad.wiener[rung] : nullptr;   // a Wiener rung: `rect` carries the frame list alone
-    const bool nmap = c->dmp.mode == MGPU_DEMAP_NMAP;                                  // the noise-map demapper: a CSI form with a map of its own
-    const bool csi = c->dmp.mode == MGPU_DEMAP_CSI || nmap;                            // the channel-aware demapper: one kernel for every window
-    if (csi && !rect) rect = &c->dmp.own;
-    const bool cfo = c->cfo.mode == MGPU_CFO_PILOTS;                                   // residual carrier-offset correction: again one kernel for every window
-    if (cfo && !rect) rect = &c->cfo.own;
+    // The launch's form (ls_rect.h): one kernel and one LDS carve per call. A Wiener rung's `rect` carries the frame list alone.
+    const bool wiener = rung < c->lad.n && c->lad.kind[rung] == MGPU_RUNG_WIENER;
+    const bool nmap = c->dmp.mode == MGPU_DEMAP_NMAP, csi = nmap || c->dmp.mode == MGPU_DEMAP_CSI;     // the noise map is a CSI form with a map of its own
+    const bool cfo = c->cfo.mode == MGPU_CFO_PILOTS;
+    unsigned form = (wiener ? MGPU_FE_WIENER : 0) | (csi ? MGPU_FE_CSI : 0) | (nmap ? MGPU_FE_NMAP : 0) | (cfo ? MGPU_FE_CFO : 0);
+    if (rect || form) form |= MGPU_FE_RECT;                                            // every option runs on a rectangle: the context's own window as one
+    const void* kernel = mgpu_frontend_form_kernel(c->fe_threads, form);
+    const size_t lds = mgpu_frontend_form_lds_bytes(dev.G, dev.nPilots, dev.nBits, c->fe_threads, form);
+    if (!kernel) throw std::runtime_error("the front-end has no kernel for this combination of options");
     for_frame_chunks(F, [&](int off, int n) {
         begin_chunk(off);
         const double* bb = io.bb + size_t(off) * stride * 2;
         float *llr = io.llr + size_t(off) * t.N, *var = io.var + off, *snrvar = at(io.snrvar, off);
-        if (rect) {
-            MgpuLsRect w = *rect;
-            const bool retry = w.frames != nullptr;
-            if (w.frames) { w.frames += off; bb = io.bb; }       // a retry: workgroup b reads frame frames[b] and writes row b
-            double* eqd = retry ? static_cast<double*>(nullptr) : at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2);
-            MgpuCfo co = c->cfo.arg;                             // the steps go to the frames' rows in the context's array, as far as it reaches
-            const size_t row = size_t(io.frame0) + size_t(off);
-            co.step_rows = cfo && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
-            co.step = co.step_rows > 0 ? c->cfo.d_step + row : nullptr;
-            MgpuNmap nm = c->dmp.nmap;                           // the factors go to the frames' rows in the context's arrays, as far as they reach
-            nm.rows = nmap && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
-            nm.fc = nm.rows > 0 ? c->dmp.d_fc + row * size_t(t.Nc) : nullptr;
-            nm.fs = nm.rows > 0 ? c->dmp.d_fs + row * size_t(t.Nsymb) : nullptr;
-            const size_t lds_wiener = wiener ? mgpu_frontend_wiener_lds_bytes(dev.G, dev.nPilots, dev.nBits, c->fe_threads, csi ? 1 : 0) : 0;
-            MgpuWiener wv = wiener ? *wiener : MgpuWiener{};     // a bank's choices go to the frames' rows in the context's arrays, from rung 0 alone
-            wv.rows = wiener && wv.n_designs > 1 && rung == 0 && !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
-            wv.choice = wv.rows > 0 ? c->lad.d_choice + row : nullptr;
-            wv.corr = wv.rows > 0 ? c->lad.d_corr + row * 4 : nullptr;
-            if (nmap && wiener && cfo)
-                hipLaunchKernelGGL(fe_wiener_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co, wv);
-            else if (nmap && wiener)
-                hipLaunchKernelGGL(fe_wiener_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, wv);
-            else if (nmap && cfo)
-                hipLaunchKernelGGL(fe_nmap_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm, co);
-            else if (nmap)
-                hipLaunchKernelGGL(fe_nmap_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.nmap_lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, nm);
-            else if (wiener && cfo && csi)
-                hipLaunchKernelGGL(fe_wiener_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co, wv);
-            else if (wiener && cfo)
-                hipLaunchKernelGGL(fe_wiener_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co, wv);
-            else if (wiener && csi)
-                hipLaunchKernelGGL(fe_wiener_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, wv);
-            else if (wiener)
-                hipLaunchKernelGGL(fe_wiener_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), lds_wiener, s, dev, bb, n, llr, var, snrvar,
-                                   static_cast<double*>(nullptr), tp, w, wv);
-            else if (cfo && csi)
-                hipLaunchKernelGGL(fe_csi_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, c->dmp.arg, co);
-            else if (cfo)
-                hipLaunchKernelGGL(fe_cfo_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar, eqd, tp, w, co);
-            else if (csi)
-                hipLaunchKernelGGL(fe_csi_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->dmp.lds, s, dev, bb, n, llr, var, snrvar,
-                                   retry ? static_cast<double*>(nullptr) : at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2), tp, w, c->dmp.arg);
-            else
-            hipLaunchKernelGGL(fe_rect_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar,
-                               static_cast<double*>(nullptr), tp, w);
-        } else {
-            hipLaunchKernelGGL(fe_kernel(c->fe_threads), dim3(n), dim3(c->fe_threads), c->lds_fe, s, dev, bb, n, llr, var, snrvar,
-                               at<double>(c->d_eqdata, (size_t(io.frame0) + off) * t.nData * 2), tp);
-        }
-        HIPCK(hipGetLastError());
+        MgpuFeOpt opt{};
+        opt.win = rect ? *rect : c->own_window;
+        const bool retry = opt.win.frames != nullptr;
+        if (retry) { opt.win.frames += off; bb = io.bb; }        // a retry: workgroup b reads frame frames[b] and writes row b
+        // what a first pass reports per frame goes to the frames' rows in the context's max_batch-sized arrays, as far as they reach
+        const size_t row = size_t(io.frame0) + size_t(off);
+        const int rows = !retry && row < size_t(c->max_batch) ? int(std::min(size_t(c->max_batch) - row, size_t(n))) : 0;
+        double* eqd = retry ? nullptr : at<double>(c->d_eqdata, row * t.nData * 2);
+        opt.csi = c->dmp.arg;
+        opt.cfo = c->cfo.arg;
+        opt.cfo.step_rows = cfo ? rows : 0;
+        opt.cfo.step = opt.cfo.step_rows > 0 ? c->cfo.d_step + row : nullptr;
+        opt.nm = c->dmp.nmap;
+        opt.nm.rows = nmap ? rows : 0;
+        opt.nm.fc = opt.nm.rows > 0 ? c->dmp.d_fc + row * size_t(t.Nc) : nullptr;
+        opt.nm.fs = opt.nm.rows > 0 ? c->dmp.d_fs + row * size_t(t.Nsymb) : nullptr;
+        if (wiener) opt.wn = c->lad.wiener[rung];
+        opt.wn.rows = wiener && opt.wn.n_designs > 1 && rung == 0 ? rows : 0;         // a bank's choices: from rung 0 alone
+        opt.wn.choice = opt.wn.rows > 0 ? c->lad.d_choice + row : nullptr;
+        opt.wn.corr = opt.wn.rows > 0 ? c->lad.d_corr + row * 4 : nullptr;
+        void* args[] = {&dev, &bb, &n, &llr, &var, &snrvar, &eqd, &tp, &opt, nullptr};
+        if (form == (MGPU_FE_RECT | MGPU_FE_CSI)) { args[8] = &opt.win; args[9] = &opt.csi; }      // the csi pair takes its two structs themselves (frontend.hip FE_FORMS)
+        HIPCK(hipLaunchKernel(kernel, dim3(n), dim3(c->fe_threads), args, lds, s));
     });
+}
+
+void frontend_raise_lds_limits(mgpu_ctx* c) {
+    for (unsigned form = 0; form < MGPU_FE_FORMS; ++form) {
+        const void* kernel = mgpu_frontend_form_kernel(c->fe_threads, form);
+        const size_t lds = mgpu_frontend_form_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads, form);
+        // (a carve beyond a compute unit's LDS: the option that needs it is refused where it is set)
+        if (kernel && lds <= size_t(160) * 1024) HIPCK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    }
 }
 
 // The timed launchers: the only code that records into the context's event ring, one start and one stop around the untimed launches.

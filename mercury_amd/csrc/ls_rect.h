@@ -1,6 +1,8 @@
+// What the front-end's opt-in forms (frontend.hip) take beyond MgpuDev (device_tables.h), which stays what the plain form and the decoder
+// are built from: a struct per option, the form bits, and the one kernel argument MgpuFeOpt that carries the structs.
+//
 // One LS estimator window of its own width and height (include/mercury_estimator.h) as the front-end's rectangular
-// instantiation takes it (frontend.hip), and the frame list of a ladder retry (ladder.hip). A kernel argument of its own:
-// MgpuDev (device_tables.h) stays what the default kernels and the decoder are built from.
+// instantiation takes it, and the frame list of a ladder retry (ladder.hip).
 #pragma once
 #include <stdint.h>
 
@@ -65,4 +67,22 @@ struct MgpuNmap {
     double* fs;                 // [rows][Nsymb]
     int rows;                   // rows of fc / fs that may be written
     int smooth;                 // carriers on either side that share a carrier's mean, 0..4
+};
+
+// A front-end form (frontend.hip): which of the options above the one body fe_frame is built with, as a bit set. Any option implies RECT and
+// NMAP implies CSI, which leaves 13 forms: the plain one, RECT with any of CSI, CFO and WIENER, RECT | CSI | NMAP with any of CFO and WIENER.
+enum : unsigned { MGPU_FE_RECT = 1, MGPU_FE_CSI = 2, MGPU_FE_CFO = 4, MGPU_FE_WIENER = 8, MGPU_FE_NMAP = 16, MGPU_FE_FORMS = 32 };
+constexpr bool mgpu_fe_form_valid(unsigned form) {
+    return form < MGPU_FE_FORMS && (form == 0 || (form & MGPU_FE_RECT)) && (!(form & MGPU_FE_NMAP) || (form & MGPU_FE_CSI));
+}
+
+// The options' arguments, the last argument of every front-end kernel. A form reads the members its bits name and no other.
+// (In this order every kernel keeps the registers, scratch and occupancy it had with arguments of its own, and all but one no more
+// instructions inside loops: profiles/frontend_forms.md.)
+struct MgpuFeOpt {
+    MgpuLsRect win;
+    MgpuNmap nm;
+    MgpuWiener wn;
+    MgpuCfo cfo;
+    MgpuCsi csi;
 };

@@ -123,7 +123,7 @@ int mgpu_debug_occupancy(mgpu_ctx* c, int which) {
     int n = -1;
     guard(c, [&] {
         const auto& t = c->tab;
-        if (which == 0 && t.mfsk_M == 0) HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fe_kernel(c->fe_threads), c->fe_threads, c->lds_fe));
+        if (which == 0 && t.mfsk_M == 0) HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, mgpu_frontend_form_kernel(c->fe_threads, 0), c->fe_threads, c->lds_fe));
         else if (which == 0) HIPCK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, t.mfsk_M == 32 ? mgpu_mfsk_frontend_kernel_m32 : mgpu_mfsk_frontend_kernel_m16x2, 256, 0));
         else if (which == 1) n = int(c->lds_fe);          // dynamic LDS bytes of the front-end workgroup
         else if (which == 2) n = int(c->lds_dec);         // ... of the decoder workgroup
