@@ -11,7 +11,8 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              LinkSimConfig, linksim_config, host_hf_stream_noise, host_linksim_frame_start, host_linksim_payload, ESTIMATOR_SYMBOLS, LADDER_MAX, host_ls_estimate, parse_ladder, host_wiener_estimate, host_wiener_tables, WIENER_DESIGN_DEFAULT,
                              DIVERSITY_SYMBOLS, DIVERSITY_MAX, host_llr_combine, DEMAPPER_SYMBOLS, DEMAPPERS, host_demap_csi, host_demap_nmap, parse_demapper, NMAP_DEFAULT, DemapperParams,
                              CFO_SYMBOLS, CFO_MODES, host_cfo_pilots, BLANKER_SYMBOLS, BLANKER_MODES, BLANKER_DEFAULT, BLANKER_REPORT_DTYPE, BlankerParams, host_blank, parse_blanker,
-                             WIENER_BANK_SYMBOLS, WIENER_BANK_MAX, WienerBankEntry, host_wiener_select, host_wiener_bank_thresholds, wiener_sounding, bank_entries)
+                             WIENER_BANK_SYMBOLS, WIENER_BANK_MAX, WienerBankEntry, host_wiener_select, host_wiener_bank_thresholds, wiener_sounding, bank_entries,
+                             CHANNELIZER_SYMBOLS, Channelizer, ChanChannel, ChanConfig, chan_channels, chan_config, host_chan_design, host_chan_tables, host_chan_process)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -21,4 +22,5 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "LINKSIM_COUNTERS_DTYPE", "host_hf_stream_noise", "host_linksim_frame_start", "host_linksim_payload", "ESTIMATOR_SYMBOLS", "LADDER_MAX", "host_ls_estimate",
            "parse_ladder", "host_wiener_estimate", "host_wiener_tables", "WIENER_DESIGN_DEFAULT", "DIVERSITY_SYMBOLS", "DIVERSITY_MAX", "host_llr_combine", "DEMAPPER_SYMBOLS", "DEMAPPERS", "host_demap_csi", "host_demap_nmap", "parse_demapper", "NMAP_DEFAULT", "DemapperParams",
            "CFO_SYMBOLS", "CFO_MODES", "host_cfo_pilots", "BLANKER_SYMBOLS", "BLANKER_MODES", "BLANKER_DEFAULT", "BLANKER_REPORT_DTYPE", "BlankerParams", "host_blank", "parse_blanker",
-           "WIENER_BANK_SYMBOLS", "WIENER_BANK_MAX", "WienerBankEntry", "host_wiener_select", "host_wiener_bank_thresholds", "wiener_sounding", "bank_entries"]
+           "WIENER_BANK_SYMBOLS", "WIENER_BANK_MAX", "WienerBankEntry", "host_wiener_select", "host_wiener_bank_thresholds", "wiener_sounding", "bank_entries",
+           "CHANNELIZER_SYMBOLS", "Channelizer", "ChanChannel", "ChanConfig", "chan_channels", "chan_config", "host_chan_design", "host_chan_tables", "host_chan_process"]

@@ -1765,6 +1765,21 @@ class RxCapture:
         nb = self.rx.payload_bytes
         return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
 
+    def run_wideband(self, chan, iq, max_events=None):
+        """run() on wideband IQ through the Channelizer `chan` (mgpu_capture_run_wideband): H * P * D complex samples -> the decoded
+        frames as run() lists them"""
+        ptr, fmt, n_in, _keep = _iq(iq)
+        if n_in == 0 or n_in % (self.P * chan.D):
+            raise MgpuError("IQ samples must be H * P * D with P = %d, D = %d" % (self.P, chan.D))
+        H = n_in // (self.P * chan.D)
+        m = self.S * H if max_events is None else max_events
+        ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
+        pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
+        n = C.c_int()
+        self.rx._ck(_chan_argtypes(self.lib).mgpu_capture_run_wideband(self.h, chan.h, ptr, fmt, H, _ptr(ev), _ptr(pl), m, C.byref(n)))
+        nb = self.rx.payload_bytes
+        return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
+
     def state(self, s):
         st = np.zeros((), CAPTURE_STATE_DTYPE)
         self.rx._ck(self.lib.mgpu_capture_get_state(self.h, C.c_int(s), _ptr(st)))
@@ -1965,3 +1980,157 @@ class LinkSim:
 
     def payload(self, link, frame):
         return host_linksim_payload(self.config.seed, link, frame, self.rx.payload_bytes)
+
+
+# ---- wideband channeliser (include/mercury_channelizer.h, DESIGN.md §3d) ---------------------------------------------------------------
+CHANNELIZER_SYMBOLS = ["mgpu_chan_create", "mgpu_chan_destroy", "mgpu_chan_latency", "mgpu_chan_seek", "mgpu_chan_retune", "mgpu_chan_process",
+                       "mgpu_chan_process_dev", "mgpu_capture_run_wideband", "mgpu_host_chan_design", "mgpu_host_chan_default_taps",
+                       "mgpu_host_chan_tables", "mgpu_host_chan_process"]
+IQ_CS16, IQ_CF32, IQ_CF64 = 0, 1, 2
+CHAN_DEFAULT_TP, CHAN_PHASOR_LEN = 320, 48000
+
+
+class ChanChannel(C.Structure):         # mgpu_chan_channel
+    _fields_ = [("offset_hz", C.c_int), ("sideband", C.c_int), ("gain", C.c_double)]
+
+
+class ChanConfig(C.Structure):          # mgpu_chan_config
+    _fields_ = [("struct_size", C.c_int), ("D", C.c_int), ("S", C.c_int), ("audio_centre_hz", C.c_int), ("ntaps", C.c_int),
+                ("taps", C.c_void_p), ("max_out", C.c_int)]
+
+
+def _chan_argtypes(lib):
+    K, Ch, V = C.POINTER(ChanConfig), C.POINTER(ChanChannel), C.c_void_p
+    lib.mgpu_chan_create.argtypes = [V, K, Ch, C.POINTER(V)]
+    lib.mgpu_chan_destroy.argtypes = [V]
+    lib.mgpu_chan_latency.argtypes = [V]
+    lib.mgpu_chan_seek.argtypes = [V, C.c_uint64]
+    lib.mgpu_chan_retune.argtypes = [V, C.c_int, Ch]
+    lib.mgpu_chan_process.argtypes = [V, V, C.c_int, C.c_int, V]
+    lib.mgpu_chan_process_dev.argtypes = [V, V, C.c_int, C.c_int, V, V]
+    lib.mgpu_capture_run_wideband.argtypes = [V, V, V, C.c_int, C.c_int, V, V, C.c_int, C.POINTER(C.c_int)]
+    lib.mgpu_host_chan_design.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, V, C.POINTER(C.c_int)]
+    lib.mgpu_host_chan_default_taps.argtypes = [C.c_int, V, C.POINTER(C.c_int)]
+    lib.mgpu_host_chan_tables.argtypes = [K, Ch, V, V]
+    lib.mgpu_host_chan_process.argtypes = [K, Ch, V, C.c_int, C.c_int, C.c_uint64, V]
+    return lib
+
+
+def chan_channels(channels):
+    """[(offset_hz, sideband, gain), ...] (sideband 0 / "usb" or 1 / "lsb"; gain optional, 1.0) -> an array of mgpu_chan_channel"""
+    rows = []
+    for ch in channels:
+        ch = tuple(ch) if isinstance(ch, (tuple, list)) else (ch,)
+        off = ch[0]
+        sb = ch[1] if len(ch) > 1 else 0
+        sb = {"usb": 0, "lsb": 1}.get(sb.lower(), -1) if isinstance(sb, str) else int(sb)
+        rows.append(ChanChannel(int(off), sb, float(ch[2]) if len(ch) > 2 else 1.0))
+    return (ChanChannel * len(rows))(*rows)
+
+
+def chan_config(D, S, taps=None, audio_centre_hz=1472, max_out=0):
+    """-> (mgpu_chan_config, keep-alive of its taps)"""
+    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
+    k = ChanConfig(C.sizeof(ChanConfig), int(D), int(S), int(audio_centre_hz), 0 if h is None else h.size,
+                   None if h is None else h.ctypes.data, int(max_out))
+    return k, h
+
+
+def _iq(iq):
+    """-> (pointer, MGPU_IQ_* format, complex samples, keep-alive): complex64, complex128, or int16 with a last axis of 2;
+    a numpy array or a torch tensor (read in place)"""
+    if hasattr(iq, "data_ptr"):
+        import torch
+        fmt = {torch.complex64: IQ_CF32, torch.complex128: IQ_CF64, torch.int16: IQ_CS16}.get(iq.dtype)
+        if fmt is None or not iq.is_contiguous() or (fmt == IQ_CS16 and (iq.dim() < 1 or iq.shape[-1] != 2)):
+            raise MgpuError("device IQ: a contiguous complex64 / complex128 tensor, or int16 with a last axis of 2")
+        n = iq.numel() // (2 if fmt == IQ_CS16 else 1)
+        return C.c_void_p(iq.data_ptr()), fmt, n, iq
+    x = np.ascontiguousarray(iq)
+    fmt = {np.dtype(np.complex64): IQ_CF32, np.dtype(np.complex128): IQ_CF64, np.dtype(np.int16): IQ_CS16}.get(x.dtype)
+    if fmt is None or (fmt == IQ_CS16 and (x.ndim < 1 or x.shape[-1] != 2)):
+        raise MgpuError("IQ samples are complex64, complex128, or int16 with a last axis of 2, not %s %s" % (x.dtype, x.shape))
+    return _ptr(x), fmt, x.size // (2 if fmt == IQ_CS16 else 1), x
+
+
+def host_chan_design(D, tp=None, cutoff_hz=1500.0, atten_db=60.0):
+    """the prototype low-pass (mgpu_host_chan_design; tp None: the default design's 320): float64 [tp * D + 1]"""
+    tp = CHAN_DEFAULT_TP if tp is None else int(tp)
+    taps = np.zeros(max(tp, 0) * max(int(D), 0) + 1)
+    n = C.c_int()
+    if _chan_argtypes(load_library()).mgpu_host_chan_design(int(D), tp, cutoff_hz, atten_db, _ptr(taps), C.byref(n)) != 0:
+        raise MgpuError("mgpu_host_chan_design: bad argument", 1)
+    return taps[: n.value]
+
+
+def host_chan_tables(D, channel, taps=None, audio_centre_hz=1472, want_phasor=False):
+    """one channel's tap row g, complex128 [T] (and the phasor table W, complex128 [48000]) as the device reads them"""
+    k, keep = chan_config(D, 1, taps, audio_centre_hz)
+    T = keep.size if keep is not None else CHAN_DEFAULT_TP * max(int(D), 0) + 1
+    g = np.zeros(T, np.complex128)
+    W = np.zeros(CHAN_PHASOR_LEN, np.complex128) if want_phasor else None
+    if _chan_argtypes(load_library()).mgpu_host_chan_tables(C.byref(k), chan_channels([channel]), _ptr(g), _ptr(W)) != 0:
+        raise MgpuError("mgpu_host_chan_tables: bad argument", 1)
+    return (g, W) if want_phasor else g
+
+
+def host_chan_process(D, channels, iq, position=0, taps=None, audio_centre_hz=1472, struct_size=None):
+    """the twin (mgpu_host_chan_process): a fresh channeliser seeked to `position` and fed `iq` whole -> float64 [S, n_in // D]"""
+    chs = chan_channels(channels)
+    k, _keep = chan_config(D, len(chs), taps, audio_centre_hz)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    ptr, fmt, n_in, _x = _iq(iq)
+    out = np.zeros((len(chs), max(n_in // max(int(D), 1), 1)))
+    if _chan_argtypes(load_library()).mgpu_host_chan_process(C.byref(k), chs, ptr, fmt, n_in, int(position), _ptr(out)) != 0:
+        raise MgpuError("mgpu_host_chan_process: bad argument", 1)
+    return out
+
+
+class Channelizer:
+    """One wideband IQ stream at 48000 * D into S 48 kHz sideband audio streams on an RxPhy context (include/mercury_channelizer.h).
+    channels: [(offset_hz, sideband, gain), ...] as chan_channels takes them. process() takes complex64 / complex128 / int16 [..., 2]
+    samples (numpy, or a torch tensor on the context's device), a multiple of D of them, and returns float64 [S, n_in // D]."""
+
+    def __init__(self, rx, D, channels, taps=None, audio_centre_hz=1472, max_out=0):
+        self.rx, self.lib, self.D = rx, _chan_argtypes(rx.lib), int(D)
+        self._chs = chan_channels(channels)
+        self.S = len(self._chs)
+        self.config, self._taps = chan_config(D, self.S, taps, audio_centre_hz, max_out)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_chan_create(rx.h, C.byref(self.config), self._chs, C.byref(self.h)))
+        self.latency = int(self.lib.mgpu_chan_latency(self.h))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.mgpu_chan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_chan_seek(self.h, int(position)))
+
+    def retune(self, s, channel):
+        self.rx._ck(self.lib.mgpu_chan_retune(self.h, int(s), chan_channels([channel])))
+
+    def process(self, iq, out=None, stream=None):
+        """out None: a new numpy array (blocking call). out a float64 torch tensor [S, n_in // D] on the device, with `iq` one too:
+        mgpu_chan_process_dev, asynchronous on `stream` (None: the context's stream)."""
+        ptr, fmt, n_in, _keep = _iq(iq)
+        if out is not None and hasattr(out, "data_ptr"):
+            import torch
+            if not hasattr(iq, "data_ptr") or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() * self.D != self.S * n_in:
+                raise MgpuError("device output: device input and a contiguous float64 tensor [S, n_in // D]")
+            self.rx._ck(self.lib.mgpu_chan_process_dev(self.h, ptr, fmt, n_in, C.c_void_p(out.data_ptr()), stream))
+            return out
+        if out is None:
+            out = np.zeros((self.S, max(n_in // self.D, 1)))
+        if out.dtype != np.float64 or not out.flags.c_contiguous or out.size < self.S * (n_in // self.D):      # a bad n_in: the library refuses it
+            raise MgpuError("out: a contiguous float64 array [S, n_in // D]")
+        self.rx._ck(self.lib.mgpu_chan_process(self.h, ptr, fmt, n_in, _ptr(out)))
+        return out
