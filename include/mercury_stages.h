@@ -19,7 +19,10 @@
  *   mgpu_bit_to_byte                 void bit_to_byte(int* in, int* out, int nItems)                            misc.h
  *   mgpu_crc16_modbus_rtu            uint16_t CRC16_MODBUS_RTU_calc(int* data, int nItems)                      crc16_modbus_rtu.h
  *                                    (bits and byte values travel as one uint8_t each instead of one int)
- * G = Nsymb*Nc cells per frame grid; complex arrays are interleaved (re, im) doubles. OFDM modes only.
+ * G = Nsymb*Nc cells per frame grid; complex arrays are interleaved (re, im) doubles. OFDM modes only: the seven stages that read the
+ * frame geometry (automatic_gain_control ... deframer, psk_demod) return MGPU_ERR_ARG on an MFSK context; symbol_demod, the
+ * deinterleavers and the integer tail read none and serve any context. Every count must be positive (the CRC alone takes n = 0: 0xFFFF),
+ * 1 <= block_size <= nItems, n <= N for the dispersal; F is not bounded by the context's max_batch. Float denormals are kept.
  */
 #ifndef MERCURY_STAGES_H
 #define MERCURY_STAGES_H
