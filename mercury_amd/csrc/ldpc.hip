@@ -248,11 +248,34 @@ __device__ __forceinline__ void spa_walk4(double& temp, uint32_t achk, spa_cptr6
     if constexpr (C + 1 < CMAX) spa_walk4<C + 1, CMAX>(temp, achk, bm, n0, n1, n2, n3);
 }
 
+// The fp64 kernels' argument segment as the hardware lays it out (every argument at its natural alignment, in order). What only the epilogue
+// needs - the tail's tables and sizes, the output and variance pointers - is read from the segment BEHIND the
+// iteration loop (spa_decode: spa_late_args) and not through the kernel's parameters: a parameter the kernel uses is loaded at entry and
+// holds its scalar registers across the whole iteration loop, some 25 of them for values no iteration looks at, and the bin loop paid for
+// them with spilled scalars and constants re-formed in every bin (profiles/NOTES.md R8.1). tests/test_spa_kernarg.py checks these offsets
+// against the compiler's own argument metadata.
+struct SpaKernArgs {
+    LdpcDev T; const float* llr_in; int F; uint8_t* bits_out; int* iters_out; uint8_t* payload_out; MgpuStatsDev* stats_out;
+    const float* variance_in; const float* snr_variance_in;
+};
+static_assert(sizeof(LdpcDev) % 8 == 0 && offsetof(SpaKernArgs, T) == 0 && offsetof(SpaKernArgs, llr_in) == sizeof(LdpcDev), "fp64 decoder kernels: argument layout");
+static_assert(offsetof(SpaKernArgs, F) == sizeof(LdpcDev) + 8 && offsetof(SpaKernArgs, bits_out) == sizeof(LdpcDev) + 16, "fp64 decoder kernels: argument layout");
+static_assert(offsetof(SpaKernArgs, iters_out) == sizeof(LdpcDev) + 24 && offsetof(SpaKernArgs, payload_out) == sizeof(LdpcDev) + 32, "fp64 decoder kernels: argument layout");
+static_assert(offsetof(SpaKernArgs, stats_out) == sizeof(LdpcDev) + 40 && offsetof(SpaKernArgs, variance_in) == sizeof(LdpcDev) + 48, "fp64 decoder kernels: argument layout");
+static_assert(offsetof(SpaKernArgs, snr_variance_in) == sizeof(LdpcDev) + 56 && sizeof(SpaKernArgs) == sizeof(LdpcDev) + 64, "fp64 decoder kernels: argument layout");
+typedef const SpaKernArgs __attribute__((address_space(4))) * spa_kargs;
+// (opaque: a load through the pointer this returns cannot be moved in front of the place it was asked for)
+__device__ __forceinline__ spa_kargs spa_late_args() {
+    spa_kargs ka = (spa_kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return ka;
+}
+
+// T, llr_in, F: the kernel's own parameters, of which this function touches only what the bin loop and the start-up need (T.S, T.DM, T.sadr,
+// T.bhead, T.bmask, T.vinfo2); everything else comes through spa_late_args - the epilogue's arguments behind the loop, the iteration cap and the
+// look thresholds once per iteration, where they are used.
 template <int NE, int DMX>
-__device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __restrict__ llr_in, int F,
-                                            uint8_t* __restrict__ bits_out, int* __restrict__ iters_out,
-                                            uint8_t* __restrict__ payload_out, MgpuStatsDev* __restrict__ stats_out,
-                                            const float* __restrict__ variance_in, const float* __restrict__ snr_variance_in) {
+__device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __restrict__ llr_in, int F) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int S = T.S;
     constexpr int N = kN;
@@ -260,13 +283,15 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
     double* Lt = reinterpret_cast<double*>(smem + kSpaOnesBytes);       // LLRtmp per variable (behind the 48 doubles 1.0 at address 0: spa_walk)
     double* M = Lt + N;                                 // R or T per padded edge slot
     float* Li = reinterpret_cast<float*>(M + S);        // channel LLR
-    uint8_t* hard = reinterpret_cast<uint8_t*>(Li + N);
-    uint8_t* bytes = hard + ((N + 15) & ~15);
-    int* flag = reinterpret_cast<int*>(bytes + 256);
+    uint8_t* bytes0 = reinterpret_cast<uint8_t*>(Li + N) + ((N + 15) & ~15);      // (behind the hard decisions; both are the epilogue's, which forms them again)
+    int* flag = reinterpret_cast<int*>(bytes0 + 256);
 
     const int tid = threadIdx.x, f = blockIdx.x;
     if (f >= F) return;
     if (uint32_t(uintptr_t(smem)) != 0) __builtin_trap();
+    // (lane tests inside the iteration loop compare an opaque copy of the thread number: a test of tid itself is hoisted in front of the loop as a
+    // 64-bit lane mask, two scalar registers each across the check pass - the allocator kept them in vector lanes)
+    auto tid_now = [&]() -> uint32_t { uint32_t t = tid; asm volatile("" : "+v"(t)); return t; };
     if (tid < int(kSpaOnesBytes / 8)) reinterpret_cast<double*>(smem)[tid] = SPA_ALLLANES != 0 && NE != 8 ? 0x1p-10 : 1.0;      // (rate 14/16: the walk's own 1.0s - its padding lanes then read 1.0, see kAllLanes)       // the walk's neutral factors (published by the barrier in front of the first pass); kAllLanes: what a padding lane reads as its "posterior"
     // Rate 14/16 (the only code with checks of degree 46; the only one the zero-forcing modes 15 / 16 use): its wavefronts meet the regimes in
     // which a whole wavefront gets one of tanh's / atanh's immediate answers (spa_math.h: spa_tanh_half_wave, spa_atanh_x2_wave) - round 5:
@@ -312,7 +337,7 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         Lt[v] = spa_tanh_half(double(l));
         hard_lane &= int(__builtin_fabsf(l) >= kSpaHardLlr);     // false for a NaN (device_tables.h ties the threshold to the degree limit and the clamp)
     }
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    auto wave_now = [&]() -> int { return __builtin_amdgcn_readfirstlane(int(tid_now() >> 6)); };      // (likewise: the wavefront's number, formed where a pass starts)
     struct VarRec { uint32_t vi, w0, w1, w2, w3, w4; };
     const __amdgpu_buffer_rsrc_t vrec = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(T.vinfo2), 0, N * 32, 0x00020000);
     auto load_var = [&](int i) -> VarRec {          // rows past N read as zeros (the buffer's bounds check): degree 0
@@ -358,10 +383,10 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         }
         Lt[v] = s;
     };
-    if (tid == 0) { flag[0] = 0; flag[1] = 0; flag[2] = LDPC_THREADS / 64; flag[3] = LDPC_THREADS / 64; }
+    if (tid_now() == 0) { flag[0] = 0; flag[1] = 0; flag[2] = LDPC_THREADS / 64; flag[3] = LDPC_THREADS / 64; }
     // (no __syncthreads_and: it brings static LDS, and this kernel's byte-offset addressing needs the dynamic block at address 0) one word per
     // wavefront in the epilogue's scratch bytes, nothing to initialise
-    int* hard_w = reinterpret_cast<int*>(bytes);
+    int* hard_w = reinterpret_cast<int*>(bytes0);
     const int hard_wave = __builtin_amdgcn_ballot_w64(hard_lane == 0) == 0;       // (the whole wavefront votes: not under the lane-0 branch)
     if ((tid & 63) == 0) hard_w[tid >> 6] = hard_wave;
     __syncthreads();
@@ -384,7 +409,7 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
     // weight, 16 of the code's 56-116 bins). The sample steers only where the next looks are taken (below: "adaptive"), never what they see.
     // A look taken inside a check pass leaves 0 or 1.
     auto flag_report = [&](int p, bool unsat, int cnt) {
-        if (unsat && (tid & 63) == 0) __hip_atomic_fetch_add(&flag[p & 1], 1 + (cnt << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (unsat && (tid_now() & 63) == 0) __hip_atomic_fetch_add(&flag[p & 1], 1 + (cnt << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     // Per-slot addresses come straight from a table (no field extraction): the LDS offset of the slot's posterior and the
     // LDS address of its check's first message, one buffer load per round (lane offset in a register, round offset in a
@@ -392,27 +417,43 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
     // the walk masks (bmask); "valid" is the bin's lane mask applied as exec.
     const __amdgpu_buffer_rsrc_t sadr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(T.sadr), 0, 0x7fffffff, 0x00020000);
     constexpr int kRound = LDPC_THREADS * 8;                       // bytes of address table per round
-    const spa_cptr64 bhead0 = (spa_cptr64)(T.bhead) + size_t(wave) * 4;
 
     // Syndrome only (before the first iteration and, in a frame's first eight iterations, after every variable update): pure latency — one L2
     // round trip for the rounds' addresses and lane masks, one LDS round trip for the posteriors, a dependent run of scalar instructions —
     // and at a mode's operating point there is one of these per iteration. It comes in two halves: syn_fetch requests all rounds' addresses
     // and masks (issued in FRONT of the work that precedes the pass, the variable update, so the L2 round trip is over when the barrier
     // opens: round 4), syn_judge reads the posteriors and forms the parities.
-    struct SynPre { uint32_t alt[NE]; unsigned long long vmask[NE], ends[NE]; };
+    struct SynPre { uint32_t alt[NE]; };
     auto syn_fetch = [&](SynPre& q) {
         uint32_t off = tid * 8;
         asm volatile("" : "+v"(off));                  // a fetch per pass: hoisted out of the iteration loop these would be 6 + 24 registers to spill
 #pragma unroll
         for (int r = 0; r < NE; ++r) q.alt[r] = __builtin_amdgcn_raw_buffer_load_b32(sadr, off, r * kRound, 0);
-#pragma unroll
-        for (int r = 0; r < NE; ++r) { q.vmask[r] = bhead0[r * 64]; q.ends[r] = bhead0[r * 64 + 1]; }
     };
     auto syn_pin = [&](SynPre& q) {                    // keeps the requests above where they were written (ahead of a barrier)
 #pragma unroll
         for (int r = 0; r < NE; ++r) asm volatile("" : "+v"(q.alt[r]));
     };
-    auto syn_judge = [&](const SynPre& q, int p) {
+    // The rounds' lane masks (4 NE scalar registers) are requested HERE, with the posteriors' LDS reads, and wait with them on one counter: requested in
+    // syn_fetch they were 4 NE scalars to keep across the variable update - or, hoisted (loads from constant memory are, whatever stands between),
+    // across the whole iteration loop - and the allocator kept them in the lanes of a vector register, written and read back in every pass
+    auto syn_judge = [&](const SynPre& pre_, int p, auto all_at_once) {
+        struct { const uint32_t* alt; unsigned long long vmask[NE], ends[NE]; } q;
+        q.alt = pre_.alt;
+        const spa_cptr64 bh = spa_at(T.bhead, uint32_t(wave_now()) * 32u);
+        constexpr int kFirstGo = !decltype(all_at_once)::value || kWaveShortcuts ? NE : NE / 2;
+#pragma unroll
+        for (int r = 0; r < kFirstGo; ++r) { q.vmask[r] = bh[r * 64]; q.ends[r] = bh[r * 64 + 1]; }
+        // The look in front of the first iteration requests the rounds' masks in TWO goes (the first half here, the second half where the first has been
+        // tested): left alone the optimiser sinks each round's load into that round's (conditional) test, a scalar round trip per round in every
+        // wavefront that finds no odd check - and a hard frame is nothing but this look and the epilogue (rate 14/16, a launch of hard frames: +0.7 %
+        // with the sunk loads). Rate 14/16 - the rate of the modes that deliver hard frames - takes all eight rounds' masks in ONE go, as the parent did,
+        // and pays with four lane moves of a spilled scalar per iteration; at the other rates 4 NE at once, here or inside the iteration loop, are
+        // scalars in vector lanes all over the loop again. Inside the loop the sunk form stays.
+        if constexpr (decltype(all_at_once)::value) {
+#pragma unroll
+            for (int r = 0; r < kFirstGo; ++r) asm volatile("" : "+s"(q.vmask[r]), "+s"(q.ends[r]));
+        }
         double lt[NE];
 #pragma unroll
         for (int r = 0; r < NE; ++r) lt[r] = *ldsd(q.alt[r]);              // padding reads variable 0; masked out below
@@ -422,11 +463,22 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         const int cnt = kAdaptive ? bin_odd_count(pre, q.vmask[0], q.ends[0]) : 0;
         bool unsat = pre != 0;
 #pragma unroll
-        for (int r = 1; r < NE; ++r)
+        for (int r = 1; r < NE; ++r) {
+            if constexpr (decltype(all_at_once)::value) {
+                if (r == kFirstGo) {                                       // the second half's masks, into the registers the first half is done with
+                    spa_cptr64 bh2 = bh;
+                    asm volatile("" : "+s"(bh2));                           // (requested HERE: not hoisted to the first half's)
+#pragma unroll
+                    for (int k = NE / 2; k < NE; ++k) { q.vmask[k] = bh2[k * 64]; q.ends[k] = bh2[k * 64 + 1]; }
+#pragma unroll
+                    for (int k = NE / 2; k < NE; ++k) asm volatile("" : "+s"(q.vmask[k]), "+s"(q.ends[k]));
+                }
+            }
             if (!unsat) unsat = bin_unsat(__ballot(lt[r] < 0) & q.vmask[r], q.ends[r]);
+        }
         flag_report(p, unsat, cnt);
     };
-    auto syndrome_pass = [&](int p) { SynPre q; syn_fetch(q); syn_judge(q, p); };
+    auto syndrome_pass = [&](int p) { SynPre q; syn_fetch(q); syn_judge(q, p, std::false_type()); };
     // The check pass. Bins are handed out on demand: wavefront w starts with bin w, every further bin goes to whoever asks first (a counter
     // in LDS, asked for while the current bin is being worked on). The hardware issues the oldest wavefront of a SIMD first, so with a
     // fixed split (bin w + 16 r in round r: rounds 1-2) the first wavefronts of a workgroup finish long before the last ones and wait at the
@@ -438,8 +490,14 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         bool unsat = false;
         const int nbins = T.S >> 6;
         const uint32_t lane8 = (tid & 63) * 8;
-        int b = wave;
-        spa_u32x2 ad = __builtin_amdgcn_raw_buffer_load_b64(sadr, lane8, b * 512, 0);
+        int b = wave_now();                            // (what a pass derives from the wavefront's number is formed per pass, not kept in scalars across the iterations)
+        // the address table's descriptor as ONE opaque four-register value per pass: left to the allocator, its two constant words are re-formed by
+        // scalar moves in every bin (the pair's registers serve as temporaries in between)
+        // (rate 14/16 has no four registers for it: there the allocator answers with scalars in vector lanes)
+        __amdgpu_buffer_rsrc_t sadr_p = sadr;
+        if constexpr (!kWaveShortcuts) asm volatile("" : "+s"(sadr_p));
+        uint32_t b512 = uint32_t(b) * 512u;            // the bin's byte offset in the message array and the address table; the next bin's is formed once, where that bin is requested
+        spa_u32x2 ad = __builtin_amdgcn_raw_buffer_load_b64(sadr_p, lane8, b512, 0);
         int* ctr = &flag[2 + (p & 1)];
         const spa_cptr64 bh0 = (spa_cptr64)(T.bhead);
         unsigned long long vm, en;
@@ -448,7 +506,7 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
 #pragma unroll 1
         while (b < nbins) {
             const uint32_t alt = ad.x, achk = ad.y;
-            const uint32_t own = kMoff + lane8 + uint32_t(b) * 512u;
+            const uint32_t own = kMoff + lane8 + b512;
             spa_cptr64 bm;
             if constexpr (SPA_OFF32 != 0) { bm = spa_at(T.bmask, uint32_t(b) * (uint32_t(T.DM) * 8u)); asm volatile("" : "+s"(bm)); }     // (opaque: the bin's base address is formed ONCE - folded into the walk's loads it is re-added in front of every step pair)
             else bm = (spa_cptr64)(T.bmask) + size_t(b) * T.DM;
@@ -481,7 +539,8 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
             // the next bin's addresses and lane masks land in the registers this one is done with, behind the atanh (the tables have a spare round)
             nxt = __builtin_amdgcn_readfirstlane(nxt);
             const int nb = nxt < nbins ? nxt : nbins;
-            ad = __builtin_amdgcn_raw_buffer_load_b64(sadr, lane8, nb * 512, 0);
+            b512 = uint32_t(nb) * 512u;                              // (nb == the next bin wherever the loop goes on)
+            ad = __builtin_amdgcn_raw_buffer_load_b64(sadr_p, lane8, b512, 0);
             if constexpr (SPA_OFF32 != 0) { const spa_cptr64 h = spa_at(T.bhead, uint32_t(nb) * 32u); vm = h[0]; en = h[1]; }
             else { vm = bh0[size_t(nb) * 4]; en = bh0[size_t(nb) * 4 + 1]; }
             double rr;
@@ -505,13 +564,16 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
 #endif
     int iteration = 0;
     SPA_STAMP(2);                                   // 2: inputs in LDS, tables requested
-    syndrome_pass(0);
+    { SynPre q; syn_fetch(q); syn_judge(q, 0, std::true_type()); }
     SPA_STAMP(3);                                   // 3: syndrome pass done (before its barrier)
     __syncthreads();
     SPA_STAMP(4);                                   // 4: behind the barrier
+    constexpr int kRanOut = -1;                     // "all iterations used": becomes max_iters + 1 behind the loop (formed in front of it, it is one more scalar across the check pass)
     int look = flag[0];                             // what the last look at the posteriors reported (flag_report)
     if (look && hard_frame) {
-        iteration = T.max_iters + 1;
+        iteration = kRanOut;
+        // (the counters' address is the kernel's parameter: its last use stands here, in front of the iteration loop, so it holds no register across
+        // the loop - and read late, by a scalar load of its own, it cost a launch of hard frames at rate 14/16 a round trip, +0.6 %: NOTES R8.1)
         if (tid == 0 && T.hard_frames) atomicAdd(T.hard_frames + (f & 63), 1ull);      // so that a benchmark can tell reported from executed iterations (64 counters: a launch of hard frames does not queue on one address)
     }
     else if (look) {
@@ -530,7 +592,8 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         // instruction on: +6 literal moves per bin).
         // thresholds: bytes of T.spec_sample_pack (255 = never)
         auto run_after = [&](int lk, int shift) -> int {
-            const int n = lk >> 8, one = int(T.spec_sample_pack >> shift) & 255, two = int(T.spec_sample_pack >> (shift + 8)) & 255;
+            const unsigned pack = spa_late_args()->T.spec_sample_pack;       // read where it is used (once per judged look), not carried across the check pass
+            const int n = lk >> 8, one = int(pack >> shift) & 255, two = int(pack >> (shift + 8)) & 255;
             return !kAdaptive ? 0 : (n >= two && two != 255) ? 2 : (n >= one && one != 255) ? 1 : 0;
         };
         // The loop's whole control state is ONE scalar register across the check pass: the iteration (low 16 bits), "this iteration's check pass
@@ -539,15 +602,17 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         // limit there - answered by rematerialising three of fdlibm's double constants in every bin (+6 scalar moves, NOTES R6.8).
         constexpr int kCtlSpec = 1 << 16, kCtlRun = 1 << 20;
         int ctl = 1 + kCtlRun * run_after(look, 0);
+        int max_iters = 0;                              // (the first iteration asks for it behind its check pass)
         for (;; ++ctl) {
             asm volatile("" : "+s"(ctl));
             const int it = ctl & 0xffff;
             const bool spec = (ctl & kCtlSpec) != 0;
             const bool skip = it >= kSpecStart || ctl >= kCtlRun;            // this iteration's posteriors get no judged look
             if (it == 1) cn_pass(false, 0, std::true_type());
-            else if (it <= T.max_iters) cn_pass((ctl & kCtlSpec) != 0, it - 1, std::false_type());
+            else if (it <= max_iters) cn_pass((ctl & kCtlSpec) != 0, it - 1, std::false_type());
             else syndrome_pass(it - 1);
             asm volatile("" : "+s"(ctl));
+            max_iters = spa_late_args()->T.max_iters;  // read again behind every pass (the round trip ends long before the barrier opens) and used up to the next pass's start: not a scalar across the bin loop
 #if !SPA_VR_RESIDENT
             const VarRec va = load_var(tid), vb = load_var(tid + LDPC_THREADS);
 #else
@@ -560,9 +625,9 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
             if (spec) {
                 look = flag[(it - 1) & 1];
                 if (!look) { iteration = it - 1; break; }
-                if (it > T.max_iters) { iteration = T.max_iters + 1; break; }
+                if (it > max_iters) { iteration = kRanOut; break; }
             }
-            if (tid == 0) { flag[it & 1] = 0; flag[2 + (it & 1)] = LDPC_THREADS / 64; }
+            if (tid_now() == 0) { flag[it & 1] = 0; flag[2 + (it & 1)] = LDPC_THREADS / 64; }
             SynPre pre;
             if (!skip) syn_fetch(pre);
 #if SPA_VR_RESIDENT
@@ -572,7 +637,7 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
             spa_u32x4 qb = vb;
             asm volatile("" : "+v"(qa.vi), "+v"(qa.w0), "+v"(qa.w1), "+v"(qa.w2), "+v"(qa.w3), "+v"(qa.w4), "+v"(qb));
             var_update(qa);
-            if (tid + LDPC_THREADS < N) var_update4(qb.x, qb.y, qb.z);
+            if (tid_now() + LDPC_THREADS < uint32_t(N)) var_update4(qb.x, qb.y, qb.z);
 #else
             var_update(va);
             if (tid + LDPC_THREADS < N) var_update(vb);
@@ -583,21 +648,28 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
             SPA_STAMP(8);                           // 8: behind its barrier
             ctl = skip ? (ctl | kCtlSpec) - (ctl >= kCtlRun ? kCtlRun : 0) : ctl & ~kCtlSpec;
             if (!skip) {
-                syn_judge(pre, it);
+                syn_judge(pre, it, std::false_type());
                 SPA_STAMP(3);
                 __syncthreads();
                 SPA_STAMP(4);
                 look = flag[it & 1];
                 if (!look) { iteration = it; break; }
-                if (it == T.max_iters) { iteration = T.max_iters + 1; break; }
+                if (it == max_iters) { iteration = kRanOut; break; }
                 ctl += kCtlRun * run_after(look, 16);
             }
         }
     }
     SPA_STAMP(9);                                   // 9: loop left
+    const spa_kargs ka = spa_late_args();           // the tail's arguments: scalar loads issued here, see SpaKernArgs
+    if (iteration == kRanOut) iteration = ka->T.max_iters + 1;
+    uint8_t* const hard = smem + kMoff + size_t(ka->T.S) * 8 + N * 4;          // (as laid out at the top; S read again rather than kept)
+    uint8_t* const bytes = hard + ((N + 15) & ~15);
     for (int v = tid; v < N; v += LDPC_THREADS) hard[v] = Lt[v] < 0;
     __syncthreads();
-    decode_tail(T, f, hard, bytes, iteration, bits_out, iters_out, payload_out, stats_out, variance_in, snr_variance_in);
+    LdpcDev Tt{};                                   // (only the fields decode_tail reads; the rest zero)
+    Tt.K = ka->T.K; Tt.nReal = ka->T.nReal; Tt.payload_stride = ka->T.payload_stride;
+    Tt.scrambler = ka->T.scrambler; Tt.crc_tab = ka->T.crc_tab; Tt.crc_init = ka->T.crc_init;
+    decode_tail(Tt, f, hard, bytes, iteration, ka->bits_out, ka->iters_out, ka->payload_out, ka->stats_out, ka->variance_in, ka->snr_variance_in);
     SPA_STAMP(10);                                  // 10: tail done
 }
 
@@ -606,7 +678,7 @@ __device__ __forceinline__ void spa_decode(const LdpcDev& T, const float* __rest
         LdpcDev T, const float* __restrict__ llr_in, int F, uint8_t* __restrict__ bits_out,                     \
         int* __restrict__ iters_out, uint8_t* __restrict__ payload_out, MgpuStatsDev* __restrict__ stats_out,   \
         const float* __restrict__ variance_in, const float* __restrict__ snr_variance_in) {                     \
-        spa_decode<NE, DMX>(T, llr_in, F, bits_out, iters_out, payload_out, stats_out, variance_in, snr_variance_in); \
+        spa_decode<NE, DMX>(T, llr_in, F);                                                                      \
     }
 SPA_KERNEL(4, 16)
 SPA_KERNEL(5, 16)
