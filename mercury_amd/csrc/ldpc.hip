@@ -702,8 +702,12 @@ extern "C" int mgpu_spa_max_degree(int ne) { return ne == 8 ? 48 : 16; }
 // lane ^ 1, lane ^ 2 (quad permutes), half-row mirror, row mirror (DPP), and for 32 / 64 lanes the four row products through scalar
 // registers - instead of a walk through LDS: T never leaves the registers, M holds only R, and nothing between the tanh and the atanh
 // waits for memory. The own factor is divided out of the check's total (|T| is kept inside [2^-30, 1 - 2^-24], so never zero); padding
-// lanes contribute 1. The order of the multiplications differs from the reference's; this decoder's parity is statistical (same decode
-// rate and payloads as the fp64 decoder, tests/test_gpu_parity.py::test_spa_fast_*), unlike the fp64 kernel's.
+// lanes contribute 1. The order of the multiplications differs from the reference's, so against the fp64 decoder this decoder's parity is
+// statistical (same decode rate and payloads, tests/test_gpu_parity.py::test_spa_fast_*). Against models of their OWN rule both fp32
+// decoders are pinned (tests/fp32_decoders_ref.py, tests/test_gpu_fp32_decoders.py): min-sum's bits and iteration counts equal its float32
+// model's, the sum-product's equal its float64 model's wherever a posterior is not within rounding of zero. Both rest on the variable sum
+// running llr + R[slot 0] + R[slot 1] + ... in the table blob's slot order (vinfo_g follows vflat) with no contraction: that order is
+// pinned by those tests - a change of it is a change of min-sum's results.
 // The syndrome is the parity of the sign bits of each group: a fold of the ballot by the group size (2 log2(g) scalar instructions).
 template <int CTRL>
 __device__ __forceinline__ float spag_dpp(float x) {

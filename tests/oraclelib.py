@@ -304,6 +304,19 @@ class RefLib(_Base):
         return bits, int(it)
 
 
+def payload_tail(orc, bits):
+    """Payload bytes, CRC and the all-zeros flag the decoders' epilogue derives from hard decisions bits[K]: the reference's de-scrambling,
+    bit packing and CRC (interleaver.cc:111-117, misc.cc:107-130, telecom_system.cc:1319-1345) restated with the oracle's scrambler and
+    CRC. orc: an oraclelib.Oracle of the mode. Returns (bytes uint8, crc, all_zeros)."""
+    scr, nb = orc.scrambler(), orc.nReal
+    pad = np.zeros((nb + 7) // 8 * 8, np.int64)
+    pad[:nb] = np.asarray(bits[:nb], np.int64) ^ scr[:nb]
+    by = (pad.reshape(-1, 8) << np.arange(8)).sum(1)
+    all_zeros = int(not by[: nb // 8].any())
+    crc = 0 if all_zeros else orc.crc16(by[: nb // 8])
+    return by.astype(np.uint8), crc, all_zeros
+
+
 def noise_amp_for(esn0_db):
     """Per-component AWGN amplitude at the reference's 1/sqrt(Nfft) scale (telecom_system.cc:100,147)."""
     return float(10.0 ** (-esn0_db / 20.0) / np.sqrt(2.0))

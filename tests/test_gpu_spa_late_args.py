@@ -34,18 +34,13 @@ def _words(cfg):
 @functools.lru_cache(maxsize=None)
 def _reference(cfg, cap):
     """Per word: bits [K], iterations, payload bytes, crc, all_zeros - the oracle's decoder, then the reference's de-scrambling, bit packing
-    and CRC (interleaver.cc:111-117, misc.cc:107-130, telecom_system.cc:1319-1345) restated with the oracle's scrambler and CRC."""
+    and CRC restated with the oracle's scrambler and CRC (oraclelib.payload_tail)."""
     orc = Oracle(cfg, cap)
-    scr, nb = orc.scrambler(), orc.nReal
     ref = []
     for w in _words(cfg):
         bits, it = orc.ldpc_decode(w)
-        pad = np.zeros((nb + 7) // 8 * 8, np.int64)
-        pad[:nb] = bits[:nb] ^ scr[:nb]
-        by = (pad.reshape(-1, 8) << np.arange(8)).sum(1)
-        all_zeros = int(not by[: nb // 8].any())
-        crc = 0 if all_zeros else orc.crc16(by[: nb // 8])
-        ref.append(dict(bits=bits.astype(np.uint8), iterations=it, bytes=by.astype(np.uint8), crc=crc, all_zeros=all_zeros))
+        by, crc, all_zeros = oraclelib.payload_tail(orc, bits)
+        ref.append(dict(bits=bits.astype(np.uint8), iterations=it, bytes=by, crc=crc, all_zeros=all_zeros))
     return ref
 
 

@@ -5,16 +5,14 @@ decreasing's, long bins come first, and the placement is deterministic."""
 import collections
 import ctypes as C
 import functools
-import os
-import struct
 
 import numpy as np
 import pytest
 
+from fp32_decoders_ref import blob_codes
 from mercury_amd import load_library
 
 N = 1600
-BLOB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mercury_amd", "data", "mercury_ldpc_tables.bin")
 # K -> bins: ceil(E / 64) wherever whole checks allow it; at rate 14/16 the 108 checks of more than 32 edges take a bin each and the 15 of
 # exactly 32 edges eight more
 BINS = {100: 56, 200: 61, 300: 70, 400: 73, 500: 85, 600: 88, 800: 95, 1400: 116}
@@ -23,20 +21,13 @@ BINS = {100: 56, 200: 61, 300: 70, 400: 73, 500: 85, 600: 88, 800: 95, 1400: 116
 @functools.lru_cache(maxsize=None)
 def _blob():
     """K -> (check degrees, the checks' variable rows)"""
-    b = open(BLOB, "rb").read()
-    assert b[:4] == b"MLDP"
     out = {}
-    off = 12
-    for _ in range(struct.unpack_from("<I", b, 8)[0]):
-        k, P, n, E, _cw, _vw = struct.unpack_from("<6I", b, off)
-        off += 24
-        cdeg = list(b[off:off + P])
-        cflat = np.frombuffer(b, dtype="<u2", count=E, offset=off + P)
-        off += P + 2 * E + n + 2 * E
-        assert n == N
+    for k, c in blob_codes().items():
+        assert c["N"] == N
+        cdeg = [int(d) for d in c["cdeg"]]
         rows, e = [], 0
         for d in cdeg:
-            rows.append(tuple(int(v) for v in cflat[e:e + d]))
+            rows.append(tuple(int(v) for v in c["cflat"][e:e + d]))
             e += d
         out[k] = (cdeg, rows)
     return out
