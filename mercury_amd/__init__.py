@@ -2,8 +2,9 @@
 
 Only what the path needs lives here: ``csrc/`` (hand-written HIP kernels for gfx950 + the C-ABI
 declared in ``include/mercury_gpu.h``), ``data/`` (the LDPC graphs as compact derived data) and
-``physical_layer.py`` (a ctypes loader mirroring the reference's physical_layer surface), ``shm.py`` (the
-shared-memory ring decoded payloads are published through, ``include/mercury_shm.h``).
+``abi.py`` (the library's loader and the one table of its functions' prototypes), ``physical_layer.py`` (a ctypes binding mirroring
+the reference's physical_layer surface), ``shm.py`` (the shared-memory ring decoded payloads are published through,
+``include/mercury_shm.h``).
 """
 from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_SPA_FAST, EXPORTED_SYMBOLS, HF_CHANNEL_SYMBOLS, HF_PRESETS, LIB_PATH, HfChannel,
                              MgpuError, RxCapture, RxPhy, RxPool, STATS_DTYPE, device_props, hf_channel_preset, host_hf_channel_draws, host_hf_channel_taps,

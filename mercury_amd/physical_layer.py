@@ -1,6 +1,6 @@
-"""ctypes binding of the C-ABI in include/mercury_gpu.h.
+"""ctypes binding of the C-ABI in include/*.h; the functions' prototypes and the loader are in abi.py.
 
-This is only a thin loader: every computation happens in the HIP library
+This is only a thin binding: every computation happens in the HIP library
 (``mercury_amd/libmercury_gpu.so``). There is NO CPU fallback — if the library is missing or no
 GPU is visible, constructing :class:`RxPhy` raises.
 
@@ -11,13 +11,10 @@ the span of ``receive_byte`` after synchronisation (telecom_system.cc:1132-1345)
 frames, ``ldpc_decode`` is ``cl_ldpc::decode`` (ldpc.h:90) on a batch of LLR vectors.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-# MERCURY_GPU_LIB: another build of the same HIP library (kernel experiments: tools/build_variants.sh); never a CPU path
-LIB_PATH = os.environ.get("MERCURY_GPU_LIB") or os.path.join(HERE, "libmercury_gpu.so")
+from .abi import LIB_PATH, load_library, names  # noqa: F401  (LIB_PATH and load_library are part of this module's surface)
 
 DEC_GBF, DEC_SPA, DEC_MINSUM, DEC_SPA_FAST = 0, 1, 2, 3
 EST_ZF, EST_LS = 0, 1
@@ -71,66 +68,11 @@ RECEIVE_STATS_DTYPE = np.dtype([("iterations_done", "<i4"), ("crc", "<i4"), ("al
 STATS_DTYPE = np.dtype([("iterations_done", "<i4"), ("crc", "<i4"), ("all_zeros", "<i4"),
                         ("message_decoded", "<i4"), ("variance", "<f4"), ("snr_db", "<f4")])
 
-_lib = None
-
-
-def load_library():
-    """dlopen the HIP library; raise (never fall back) when it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(the Mercury RX path has no CPU fallback)" % LIB_PATH)
-        # torch (used by bench/tests for device buffers, streams and torch.distributed) bundles its own
-        # HIP runtime under the same SONAME; it has to be the first one in the process or the process ends
-        # up with two HSA runtimes and the second one sees no GPU.
-        try:
-            import torch  # noqa: F401
-        except Exception:  # torch is plumbing, not a dependency of the library itself
-            pass
-        lib = C.CDLL(LIB_PATH)
-        lib.mgpu_last_error.restype = C.c_char_p
-        lib.mgpu_last_error.argtypes = [C.c_void_p]
-        lib.mgpu_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
-        lib.mgpu_txgen_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_double, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mgpu_rx_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mgpu_frontend_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mgpu_ldpc_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mgpu_destroy.argtypes = [C.c_void_p]
-        _hf_argtypes(lib)
-        _div_argtypes(lib)
-        _lib = lib
-    return _lib
-
-
-EXPORTED_SYMBOLS = [
-    "mgpu_alloc_host", "mgpu_free_host", "mgpu_create", "mgpu_destroy", "mgpu_last_error", "mgpu_get_info", "mgpu_rx_batch", "mgpu_rx_batch_taps",
-    "mgpu_host_libm_selfcheck", "mgpu_host_select_peak", "mgpu_host_fir_taps", "mgpu_host_preamble_carriers", "mgpu_host_mode_info", "mgpu_host_layout_stats",
-    "mgpu_device_props_get", "mgpu_alloc_host_near", "mgpu_host_numa_node_of_pci", "mgpu_host_numa_cpus", "mgpu_pool_device_numa_node",
-    "mgpu_ldpc_batch", "mgpu_ldpc_encode_batch", "mgpu_rx_batch_dev", "mgpu_frontend_dev", "mgpu_ldpc_batch_dev", "mgpu_txgen_dev",
-    "mgpu_host_path_last", "mgpu_device_malloc", "mgpu_device_free", "mgpu_context_stream", "mgpu_synchronize", "mgpu_copy_to_host", "mgpu_copy_to_device",
-    "mgpu_pool_rx_batch_dev", "mgpu_pool_ldpc_batch_dev", "mgpu_pool_txgen_dev",
-    "mgpu_last_kernel_ms", "mgpu_kernel_ms_avg", "mgpu_decoder_hard_frames", "mgpu_enable_timing", "mgpu_debug_spa_math", "mgpu_debug_spa_bins", "mgpu_debug_glibc_trig", "mgpu_debug_tsync_metric", "mgpu_debug_occupancy", "mgpu_debug_select_peak", "mgpu_debug_span_energy", "mgpu_debug_p2b_variant", "mgpu_debug_mfsk_sync", "mgpu_baseband_test_esn0", "mgpu_passband_test_esn0", "mgpu_passband_to_baseband", "mgpu_time_sync_preamble", "mgpu_freq_sync", "mgpu_last_sync_kernel_ms",
-    "mgpu_time_sync_mfsk", "mgpu_detect_ack_pattern", "mgpu_detect_ack_pattern_from_passband",
-    "mgpu_receive_buffer_nsymb", "mgpu_receive_byte_batch", "mgpu_receive_byte_batch_samples", "mgpu_measure_signal_only",
-    "mgpu_host_pre_equalization_channel", "mgpu_context_pre_equalization_channel", "mgpu_set_pre_equalization_channel", "mgpu_transmit_bit_batch", "mgpu_transmit_frame_samples", "mgpu_transmit_byte_batch", "mgpu_transmit_byte_batch_dev", "mgpu_transmit_buffer", "mgpu_symbol_mod", "mgpu_generate_ack_pattern_passband",
-    "mgpu_symbol_demod", "mgpu_automatic_gain_control", "mgpu_channel_estimator", "mgpu_restore_channel_amplitude", "mgpu_channel_equalizer",
-    "mgpu_measure_variance", "mgpu_deframer", "mgpu_deinterleaver_c128", "mgpu_deinterleaver_f32", "mgpu_psk_demod",
-    "mgpu_bit_energy_dispersal", "mgpu_bit_to_byte", "mgpu_crc16_modbus_rtu",
-    "mgpu_shm_create", "mgpu_shm_connect", "mgpu_shm_close", "mgpu_shm_destroy", "mgpu_shm_used", "mgpu_shm_free", "mgpu_shm_capacity",
-    "mgpu_shm_clear", "mgpu_shm_write", "mgpu_shm_read", "mgpu_shm_read_all", "mgpu_shm_publish_decoded",
-    "mgpu_create_explicit", "mgpu_pool_create", "mgpu_pool_destroy", "mgpu_pool_size", "mgpu_pool_context", "mgpu_pool_last_error", "mgpu_pool_last_counters",
-    "mgpu_pool_shard", "mgpu_pool_rx_batch", "mgpu_pool_ldpc_batch", "mgpu_pool_receive_byte_batch",
-]
+EXPORTED_SYMBOLS = names("mercury_gpu.h", "mercury_shm.h", "mercury_rxloop.h", "mercury_stages.h", "mercury_tx.h", "mercury_pool.h")
 
 
 # ---- rectangular LS windows and the estimator ladder (include/mercury_estimator.h, DESIGN.md §3.7) -------------------------------
-ESTIMATOR_SYMBOLS = ["mgpu_set_estimator_ladder", "mgpu_get_estimator_ladder", "mgpu_estimator_rungs_last", "mgpu_estimator_ladder_counters",
-                     "mgpu_host_ls_estimate", "mgpu_set_estimator_ladder_ex", "mgpu_get_estimator_ladder_ex", "mgpu_host_wiener_estimate",
-                     "mgpu_host_wiener_tables"]
+ESTIMATOR_SYMBOLS = names("mercury_estimator.h")
 LADDER_MAX = 4
 RUNG_LS, RUNG_WIENER = 0, 1
 WIENER_DESIGN_DEFAULT = dict(tau_min_us=-333.33, tau_max_us=2333.33, doppler_hz=0.5, snr_db=0.0)
@@ -213,8 +155,7 @@ def _is_wiener(rung):
 
 
 # ---- a Wiener rung's bank of designs (include/mercury_wiener_bank.h) ---------------------------------------------
-WIENER_BANK_SYMBOLS = ["mgpu_set_wiener_bank", "mgpu_get_wiener_bank", "mgpu_get_wiener_choice", "mgpu_host_wiener_select",
-                       "mgpu_host_wiener_bank_thresholds"]
+WIENER_BANK_SYMBOLS = names("mercury_wiener_bank.h")
 WIENER_BANK_MAX = 4
 
 
@@ -248,7 +189,6 @@ def host_wiener_select(cfg, grid, entries, explicit=None):
     entries: [(design dict, rho_min or None: the default), ...], the last one the fallback.
     -> dict(design, corr: float64 [4] R1r R1i R2r R2i, n1, n2)"""
     lib = load_library()
-    lib.mgpu_host_wiener_select.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     g = np.ascontiguousarray(grid, np.complex128).ravel()
     xp = _explicit_struct(explicit)
     arr, n = _bank_array(entries)
@@ -263,7 +203,6 @@ def host_wiener_select(cfg, grid, entries, explicit=None):
 def host_wiener_bank_thresholds(cfg, entries, explicit=None):
     """mgpu_host_wiener_bank_thresholds: (rho_min as applied: float64 [n - 1], the pilot spacing s) of a bank on the mode's geometry; no GPU"""
     lib = load_library()
-    lib.mgpu_host_wiener_bank_thresholds.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
     xp = _explicit_struct(explicit)
     arr, n = _bank_array(entries)
     rho, s = np.zeros(max(n - 1, 1), np.float64), C.c_int()
@@ -288,7 +227,6 @@ def host_wiener_estimate(cfg, grid, design=None, explicit=None):
     grid (complex128 [Nsymb * Nc], after the AGC); no GPU. design: dict with any of tau_min_us, tau_max_us, doppler_hz, snr_db (None: the
     defaults). explicit: as RxPhy's."""
     lib = load_library()
-    lib.mgpu_host_wiener_estimate.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     g = np.ascontiguousarray(grid, np.complex128).ravel()
     xp = _explicit_struct(explicit)
     ref = C.byref(xp) if xp is not None else None
@@ -309,7 +247,6 @@ def host_wiener_tables(cfg, design=None, explicit=None):
     """mgpu_host_wiener_tables: (time classes, frequency classes) of a design, each a list of (members: int32 [n] - the pilot rows a carrier
     has / the pilot carriers a symbol has -, matrix [n, n]: float64 / complex128, as the kernel reads it); no GPU."""
     lib = load_library()
-    lib.mgpu_host_wiener_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     xp = _explicit_struct(explicit)
     ref = C.byref(xp) if xp is not None else None
     d = _wiener_design(design)
@@ -337,7 +274,6 @@ def host_ls_estimate(cfg, grid, width, height, explicit=None):
     """mgpu_host_ls_estimate: the LS estimate at the pilot cells (row-major pilot order, complex128 [nPilots]) of one frame grid
     (complex128 [Nsymb * Nc], after the AGC) for a width x height window; no GPU. explicit: as RxPhy's."""
     lib = load_library()
-    lib.mgpu_host_ls_estimate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     g = np.ascontiguousarray(grid, np.complex128).ravel()
     xp = None
     if explicit:
@@ -359,8 +295,7 @@ def host_ls_estimate(cfg, grid, width, height, explicit=None):
 
 
 # ---- the channel-aware demapper (include/mercury_demapper.h) --------------------------------------------------------
-DEMAPPER_SYMBOLS = ["mgpu_set_demapper", "mgpu_get_demapper", "mgpu_host_demap_csi", "mgpu_set_demapper_ex", "mgpu_get_demapper_ex",
-                    "mgpu_get_noise_map", "mgpu_host_demap_nmap"]
+DEMAPPER_SYMBOLS = names("mercury_demapper.h")
 DEMAPPERS = {"maxlog": 0, "csi": 1, "nmap": 2}
 NMAP_DEFAULT = {"dead_band": 2.0, "smooth": 1}
 
@@ -403,7 +338,6 @@ def host_demap_csi(cfg, grid, H, explicit=None):
     """mgpu_host_demap_csi, no GPU: one frame's cell grid (after the AGC) and channel estimate at every cell (complex128 [Nsymb * Nc] each)
     -> (the demodulated LLRs in the demapper's order: float32 [nBits], sigma2). explicit: as RxPhy's."""
     lib = load_library()
-    lib.mgpu_host_demap_csi.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     g = np.ascontiguousarray(grid, np.complex128).ravel()
     h = np.ascontiguousarray(H, np.complex128).ravel()
     if g.size != h.size:
@@ -427,7 +361,6 @@ def host_demap_nmap(cfg, grid, H, dead_band=2.0, smooth=1, explicit=None):
     """mgpu_host_demap_nmap, no GPU: as host_demap_csi with the noise map -> (llr_demod float32 [nBits], sigma2,
     fc float64 [Nc], fs float64 [Nsymb]); the factors are those after the dead band."""
     lib = load_library()
-    lib.mgpu_host_demap_nmap.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     g = np.ascontiguousarray(grid, np.complex128).ravel()
     h = np.ascontiguousarray(H, np.complex128).ravel()
     if g.size != h.size:
@@ -451,7 +384,7 @@ def host_demap_nmap(cfg, grid, H, dead_band=2.0, smooth=1, explicit=None):
 
 
 # ---- pilot-aided residual carrier-offset correction (include/mercury_cfo.h) ----------------------------------------
-CFO_SYMBOLS = ["mgpu_set_cfo", "mgpu_get_cfo", "mgpu_get_cfo_steps", "mgpu_host_cfo_pilots"]
+CFO_SYMBOLS = names("mercury_cfo.h")
 CFO_MODES = {"off": 0, "pilots": 1}
 _CFO_CELLS = {}
 
@@ -460,7 +393,6 @@ def host_cfo_pilots(cfg, grid, explicit=None):
     """mgpu_host_cfo_pilots, no GPU: one frame's cell grid (complex128 [Nsymb * Nc], after the AGC) -> (the grid with symbol s turned back
     by s steps: complex128 [Nsymb * Nc], the step in radians per symbol). explicit: as RxPhy's."""
     lib = load_library()
-    lib.mgpu_host_cfo_pilots.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     g = np.ascontiguousarray(grid, np.complex128).ravel()
     xp = _explicit_struct(explicit)
     ref = C.byref(xp) if xp is not None else None
@@ -485,7 +417,7 @@ def host_cfo_pilots(cfg, grid, explicit=None):
 
 
 # ---- the impulse blanker (include/mercury_blanker.h) -----------------------------------------------------------------
-BLANKER_SYMBOLS = ["mgpu_set_blanker", "mgpu_get_blanker", "mgpu_get_blanker_report", "mgpu_blank_dev", "mgpu_host_blank"]
+BLANKER_SYMBOLS = names("mercury_blanker.h")
 BLANKER_MODES = {"off": 0, "median": 1}
 BLANKER_DEFAULT = {"threshold": 24.0, "guard": 4, "max_share": 0.125}
 BLANKER_REPORT_DTYPE = np.dtype([("marked", "<i4"), ("blanked", "<i4")])
@@ -527,12 +459,10 @@ def host_blank(cfg, frame, explicit=None, **params):
     """mgpu_host_blank, no GPU: one frame's baseband samples (complex128 [frame_samples]) -> (the blanked frame, {"marked", "blanked"}).
     params: threshold, guard, max_share (the defaults where left out). explicit: as RxPhy's."""
     lib = load_library()
-    lib.mgpu_host_blank.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     x = np.ascontiguousarray(frame, np.complex128).ravel()
     xp = _explicit_struct(explicit)
     # frame_samples of the (possibly explicit) geometry: an explicit Nsymb symbols of the mode's length, else the mode's own
     info = Info()
-    lib.mgpu_host_mode_info.argtypes = [C.c_int, C.c_int, C.c_void_p]
     if lib.mgpu_host_mode_info(int(cfg), 0, C.byref(info)) != 0:
         raise MgpuError("host_blank: cfg %r is no mode" % (cfg,), 1)
     n = int((explicit or {}).get("Nsymb", 0)) * info.Nofdm or info.frame_samples
@@ -547,19 +477,8 @@ def host_blank(cfg, frame, explicit=None, **params):
 
 
 # ---- diversity combining (include/mercury_diversity.h) ------------------------------------------------------------
-DIVERSITY_SYMBOLS = ["mgpu_rx_batch_div_dev", "mgpu_rx_batch_div", "mgpu_llr_combine_dev", "mgpu_host_llr_combine", "mgpu_baseband_test_esn0_div"]
+DIVERSITY_SYMBOLS = names("mercury_diversity.h")
 DIVERSITY_MAX = 8
-
-
-def _div_argtypes(lib):
-    if not hasattr(lib, "mgpu_rx_batch_div_dev"):       # an older build loaded through MERCURY_GPU_LIB (A/B runs): these calls raise AttributeError
-        return
-    lib.mgpu_rx_batch_div_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mgpu_rx_batch_div.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mgpu_llr_combine_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.mgpu_host_llr_combine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.mgpu_baseband_test_esn0_div.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_uint64, C.c_uint64, C.POINTER(HfChannel), C.c_int,
-                                                C.c_void_p]
 
 
 def _csr(groups):
@@ -597,12 +516,9 @@ def host_llr_combine(llr, D=None, groups=None):
 # ---- Watterson HF fading channel (include/mercury_channel.h) ----------------------------------------------------
 HF_MAX_PATHS, HF_SINUSOIDS = 4, 32
 HF_PRESETS = {"awgn": 0, "good": 1, "moderate": 2, "poor": 3, "flutter": 4}
-HF_CHANNEL_SYMBOLS = ["mgpu_hf_channel_preset", "mgpu_host_hilbert_taps", "mgpu_host_hf_channel_draws", "mgpu_host_hf_channel_taps",
-                      "mgpu_hf_channel_apply", "mgpu_hf_channel_apply_dev", "mgpu_passband_test_esn0_hf", "mgpu_baseband_test_esn0_hf"]
+HF_CHANNEL_SYMBOLS = names("mercury_channel.h")
 # the streaming form in the same header (HfStream below)
-HF_STREAM_SYMBOLS = ["mgpu_hf_stream_create", "mgpu_hf_stream_destroy", "mgpu_hf_stream_seek", "mgpu_hf_stream_latency", "mgpu_hf_stream_apply",
-                     "mgpu_hf_stream_apply_dev", "mgpu_host_hf_stream_noise"]
-HF_CHANNEL_SYMBOLS += HF_STREAM_SYMBOLS
+HF_STREAM_SYMBOLS = [n for n in HF_CHANNEL_SYMBOLS if "_hf_stream_" in n]
 
 
 class HfChannel(C.Structure):
@@ -621,21 +537,6 @@ class HfChannel(C.Structure):
 
     def paths(self):
         return [(self.delay_ms[k], self.gain_db[k], self.spread_hz[k], self.shift_hz[k]) for k in range(self.n_paths)]
-
-
-def _hf_argtypes(lib):
-    P = C.POINTER(HfChannel)
-    lib.mgpu_hf_channel_preset.argtypes = [C.c_int, P]
-    lib.mgpu_host_hilbert_taps.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    lib.mgpu_host_hf_channel_draws.argtypes = [P, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
-    lib.mgpu_host_hf_channel_taps.argtypes = [P, C.c_double, C.c_uint64, C.c_uint64, C.c_longlong, C.c_int, C.c_void_p]
-    lib.mgpu_hf_channel_apply.argtypes = [C.c_void_p, P, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_longlong,
-                                          C.c_void_p]
-    lib.mgpu_hf_channel_apply_dev.argtypes = [C.c_void_p, P, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
-                                              C.c_longlong, C.c_void_p, C.c_void_p]
-    lib.mgpu_passband_test_esn0_hf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_uint64, C.c_uint64, C.c_double, C.c_double, P,
-                                               C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mgpu_baseband_test_esn0_hf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_uint64, C.c_uint64, P, C.c_void_p]
 
 
 def hf_channel_preset(name):
@@ -700,7 +601,7 @@ def device_props(device=0):
     """mgpu_device_props_get: compute units, clocks, LDS per compute unit, PCI address and NUMA node of a device, as a dict."""
     lib = load_library()
     p = DeviceProps()
-    rc = lib.mgpu_device_props_get(C.c_int(device), C.byref(p))
+    rc = lib.mgpu_device_props_get(device, C.byref(p))
     if rc != 0:
         raise MgpuError("mgpu_device_props_get(%d) failed (%d): no such device" % (device, rc))
     return {n: (getattr(p, n).decode() if isinstance(getattr(p, n), bytes) else getattr(p, n)) for n, _ in DeviceProps._fields_}
@@ -710,11 +611,6 @@ def pinned_empty(shape, dtype, device=None):
     """numpy array over page-locked host memory from mgpu_alloc_host — or, with ``device``, from mgpu_alloc_host_near (pages on that
     GPU's NUMA node). Keep the array alive while it is in use; the memory is released when the returned array's base object is collected."""
     lib = load_library()
-    lib.mgpu_alloc_host.restype = C.c_void_p
-    lib.mgpu_alloc_host.argtypes = [C.c_size_t]
-    lib.mgpu_alloc_host_near.restype = C.c_void_p
-    lib.mgpu_alloc_host_near.argtypes = [C.c_int, C.c_size_t]
-    lib.mgpu_free_host.argtypes = [C.c_void_p]
     dt = np.dtype(dtype)
     n = int(np.prod(shape))
     ptr = lib.mgpu_alloc_host(n * dt.itemsize) if device is None else lib.mgpu_alloc_host_near(int(device), n * dt.itemsize)
@@ -800,18 +696,15 @@ class RxPhy:
                     arr[i] = EstimatorRung(RUNG_WIENER, LsWindow(0, 0), _wiener_design(None if r == "wiener" else r[1]))
                 else:
                     arr[i] = EstimatorRung(RUNG_LS, LsWindow(int(r[0]), int(r[1])), WienerDesign())
-            self.lib.mgpu_set_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
             self._ck(self.lib.mgpu_set_estimator_ladder_ex(self.h, arr, len(rungs), C.sizeof(EstimatorRung)))
             return
         arr = (LsWindow * max(len(rungs), 1))(*[LsWindow(int(w), int(h)) for w, h in rungs])
-        self.lib.mgpu_set_estimator_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self._ck(self.lib.mgpu_set_estimator_ladder(self.h, arr if rungs else None, len(rungs)))
 
     @property
     def estimator_ladder(self):
         """the rungs as they are applied (odd sides): [(width, height), ...]"""
         arr, n = (LsWindow * LADDER_MAX)(), C.c_int()
-        self.lib.mgpu_get_estimator_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_estimator_ladder(self.h, arr, C.byref(n)))
         return [(arr[r].width, arr[r].height) for r in range(n.value)]
 
@@ -819,7 +712,6 @@ class RxPhy:
     def estimator_ladder_ex(self):
         """the rungs with their kind: (width, height) for an LS rung, ("wiener", {design}) for a Wiener rung"""
         arr, n = (EstimatorRung * LADDER_MAX)(), C.c_int()
-        self.lib.mgpu_get_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         self._ck(self.lib.mgpu_get_estimator_ladder_ex(self.h, arr, C.byref(n), C.sizeof(EstimatorRung)))
         return [("wiener", {k: getattr(arr[r].design, k) for k in WIENER_DESIGN_DEFAULT}) if arr[r].kind == RUNG_WIENER
                 else (arr[r].window.width, arr[r].window.height) for r in range(n.value)]
@@ -829,14 +721,12 @@ class RxPhy:
         """Rung `rung` of the ladder in force (a Wiener rung) chooses per frame among entries = [(design dict, rho_min or None: the
         default), ...] (a bare design dict is (design, None)); the last entry is the fallback. [] or None removes the bank."""
         arr, n = _bank_array(entries)
-        self.lib.mgpu_set_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t]
         self._ck(self.lib.mgpu_set_wiener_bank(self.h, int(rung), arr if n else None, n, C.sizeof(WienerBankEntry)))
 
     def wiener_bank(self, rung):
         """the bank of a rung with the thresholds as applied: [(design dict, rho_min), ...] (None for a NaN: the fallback's is reported as
         it was given); [] where it has none"""
         arr, n = (WienerBankEntry * WIENER_BANK_MAX)(), C.c_int()
-        self.lib.mgpu_get_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         self._ck(self.lib.mgpu_get_wiener_bank(self.h, int(rung), arr, C.byref(n), C.sizeof(WienerBankEntry)))
         return [({k: getattr(arr[d].design, k) for k in WIENER_DESIGN_DEFAULT}, None if np.isnan(arr[d].rho_min) else arr[d].rho_min) for d in range(n.value)]
 
@@ -845,7 +735,6 @@ class RxPhy:
         dict(design int32 [count], corr float64 [count, 4], n1, n2, rho, delay_us) - rho and delay_us computed here from corr"""
         count = self.max_batch - int(first) if count is None else int(count)
         design, corr, n1, n2 = np.zeros(count, np.int32), np.zeros((count, 4), np.float64), C.c_int(), C.c_int()
-        self.lib.mgpu_get_wiener_choice.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_wiener_choice(self.h, int(first), count, _ptr(design), _ptr(corr), C.byref(n1), C.byref(n2)))
         _, s = host_wiener_bank_thresholds(self._mode[0], self.wiener_bank(0), explicit=self._mode[1])
         rho, delay = wiener_sounding(corr, n1.value, n2.value, s)
@@ -854,14 +743,12 @@ class RxPhy:
     def last_rungs(self, F):
         """winning rung of each of the first F frames of the last receive call, -1 where no rung decoded: int32 [F]"""
         out = np.zeros(F, np.int32)
-        self.lib.mgpu_estimator_rungs_last.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self._ck(self.lib.mgpu_estimator_rungs_last(self.h, _ptr(out), F))
         return out
 
     def ladder_counters(self, reset=False):
         """(frames decoded by each rung: int64 [LADDER_MAX], frames seen) since the ladder was set or the last reset"""
         by, n = np.zeros(LADDER_MAX, np.int64), C.c_longlong()
-        self.lib.mgpu_estimator_ladder_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         self._ck(self.lib.mgpu_estimator_ladder_counters(self.h, _ptr(by), C.byref(n), 1 if reset else 0))
         return by, int(n.value)
 
@@ -879,18 +766,15 @@ class RxPhy:
             dead_band = spec["dead_band"] if dead_band is None else dead_band
             smooth = spec["smooth"] if smooth is None else smooth
         if dead_band is None and smooth is None:
-            self.lib.mgpu_set_demapper.argtypes = [C.c_void_p, C.c_int]
             self._ck(self.lib.mgpu_set_demapper(self.h, DEMAPPERS[name]))
             return
         prm = DemapperParams(float(NMAP_DEFAULT["dead_band"] if dead_band is None else dead_band), int(NMAP_DEFAULT["smooth"] if smooth is None else smooth))
-        self.lib.mgpu_set_demapper_ex.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         self._ck(self.lib.mgpu_set_demapper_ex(self.h, DEMAPPERS[name], C.byref(prm), C.sizeof(prm)))
 
     @property
     def demapper_ex(self):
         """(name, {dead_band, smooth}): the demapper and the noise map's parameters as last set (the defaults before)"""
         v, prm = C.c_int(), DemapperParams()
-        self.lib.mgpu_get_demapper_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         self._ck(self.lib.mgpu_get_demapper_ex(self.h, C.byref(v), C.byref(prm), C.sizeof(prm)))
         return {n: k for k, n in DEMAPPERS.items()}[v.value], {"dead_band": prm.dead_band, "smooth": prm.smooth}
 
@@ -899,14 +783,12 @@ class RxPhy:
         (default: to max_batch) of the last call that ran with the "nmap" demapper; rung 0's under an estimator ladder."""
         count = self.max_batch - int(first) if count is None else int(count)
         fc, fs = np.zeros((count, self.Nc), np.float64), np.zeros((count, self.Nsymb), np.float64)
-        self.lib.mgpu_get_noise_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_noise_map(self.h, int(first), count, _ptr(fc), _ptr(fs)))
         return fc, fs
 
     @property
     def demapper(self):
         v = C.c_int()
-        self.lib.mgpu_get_demapper.argtypes = [C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_demapper(self.h, C.byref(v)))
         return {n: k for k, n in DEMAPPERS.items()}[v.value]
 
@@ -916,20 +798,17 @@ class RxPhy:
         own pilots measure, between the AGC and the channel estimate, in every receive entry point of this context."""
         if name not in CFO_MODES:
             raise MgpuError("cfo must be one of %s" % sorted(CFO_MODES))
-        self.lib.mgpu_set_cfo.argtypes = [C.c_void_p, C.c_int]
         self._ck(self.lib.mgpu_set_cfo(self.h, CFO_MODES[name]))
 
     @property
     def cfo(self):
         v = C.c_int()
-        self.lib.mgpu_get_cfo.argtypes = [C.c_void_p, C.c_void_p]
         self._ck(self.lib.mgpu_get_cfo(self.h, C.byref(v)))
         return {n: k for k, n in CFO_MODES.items()}[v.value]
 
     def cfo_steps(self, F):
         """the steps (radians per symbol; Hz = step * 12000 / (2 pi Nofdm)) of rows 0 .. F-1 of the last span that ran with the mode on"""
         out = np.zeros(int(F), np.float64)
-        self.lib.mgpu_get_cfo_steps.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._ck(self.lib.mgpu_get_cfo_steps(self.h, int(F), _ptr(out)))
         return out
 
@@ -945,14 +824,12 @@ class RxPhy:
         spec = spec or BLANKER_DEFAULT
         prm = _blanker_params(spec["threshold"] if threshold is None else threshold, spec["guard"] if guard is None else guard,
                               spec["max_share"] if max_share is None else max_share)
-        self.lib.mgpu_set_blanker.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         self._ck(self.lib.mgpu_set_blanker(self.h, BLANKER_MODES[name], C.byref(prm), C.sizeof(prm)))
 
     @property
     def blanker(self):
         """(name, {threshold, guard, max_share}): the mode and the parameters as last set (the defaults before)"""
         v, prm = C.c_int(), BlankerParams()
-        self.lib.mgpu_get_blanker.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         self._ck(self.lib.mgpu_get_blanker(self.h, C.byref(v), C.byref(prm), C.sizeof(prm)))
         return {n: k for k, n in BLANKER_MODES.items()}[v.value], {"threshold": prm.threshold, "guard": prm.guard, "max_share": prm.max_share}
 
@@ -961,7 +838,6 @@ class RxPhy:
         ran with the blanker on"""
         count = self.max_batch - int(first) if count is None else int(count)
         out = np.zeros(count, BLANKER_REPORT_DTYPE)
-        self.lib.mgpu_get_blanker_report.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         self._ck(self.lib.mgpu_get_blanker_report(self.h, int(first), count, _ptr(out)))
         return out
 
@@ -973,31 +849,27 @@ class RxPhy:
         bb = np.ascontiguousarray(baseband, np.complex128).reshape(-1, width)
         F = bb.shape[0]
         out, rep = np.zeros((F, self.frame_samples), np.complex128), np.zeros(F, BLANKER_REPORT_DTYPE)
+        if F:       # (the copies take the context's stream for None; mgpu_blank_dev takes the null stream)
+            self._staged([bb], [out, rep], "mgpu_device_malloc failed", lambda d_bb, d_out, d_rep: self._ck(self.lib.mgpu_blank_dev(
+                self.h, d_bb, F, 0 if frame_stride is None else width, d_out, d_rep, self.lib.mgpu_context_stream(self.h))))
+        return out, rep
+
+    def _staged(self, inputs, outputs, error, run):
+        """run(device pointers of inputs + outputs) between the inputs' copy to the device and the outputs' copy back, all on the
+        context's stream; the device buffers are freed whatever happens"""
         lib = self.lib
-        lib.mgpu_device_malloc.restype = C.c_void_p
-        lib.mgpu_device_malloc.argtypes = [C.c_void_p, C.c_size_t]
-        lib.mgpu_device_free.argtypes = [C.c_void_p, C.c_void_p]
-        lib.mgpu_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mgpu_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mgpu_blank_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mgpu_context_stream.restype = C.c_void_p
-        lib.mgpu_context_stream.argtypes = [C.c_void_p]
-        if F == 0:
-            return out, rep
-        bufs = [lib.mgpu_device_malloc(self.h, a.nbytes) for a in (bb, out, rep)]
+        bufs = [lib.mgpu_device_malloc(self.h, max(a.nbytes, 16)) for a in inputs + outputs]
         try:
             if not all(bufs):
-                raise MgpuError("mgpu_device_malloc failed")
-            s = lib.mgpu_context_stream(self.h)
-            self._ck(lib.mgpu_copy_to_device(self.h, bufs[0], _ptr(bb), bb.nbytes, s))
-            self._ck(lib.mgpu_blank_dev(self.h, bufs[0], F, 0 if frame_stride is None else width, bufs[1], bufs[2], s))
-            self._ck(lib.mgpu_copy_to_host(self.h, _ptr(out), bufs[1], out.nbytes, s))
-            self._ck(lib.mgpu_copy_to_host(self.h, _ptr(rep), bufs[2], rep.nbytes, s))
+                raise MgpuError(error)
+            for a, d in zip(inputs, bufs):
+                self._ck(lib.mgpu_copy_to_device(self.h, d, _ptr(a), a.nbytes, None))
+            run(*bufs)
+            for a, d in zip(outputs, bufs[len(inputs):]):
+                self._ck(lib.mgpu_copy_to_host(self.h, _ptr(a), d, a.nbytes, None))
         finally:
-            for b in bufs:
-                if b:
-                    lib.mgpu_device_free(self.h, b)
-        return out, rep
+            for d in bufs:
+                lib.mgpu_device_free(self.h, d)
 
     # ---- host-buffer entry points -------------------------------------------------------------
     def receive(self, baseband, taps=False, want_llr=False):
@@ -1017,11 +889,11 @@ class RxPhy:
                 for k in ("H", "eq", "syms"):
                     del t[k]
             ts = Taps(**{k: v.ctypes.data for k, v in t.items()})
-            self._ck(self.lib.mgpu_rx_batch_taps(self.h, _ptr(bb), C.c_int(F), _ptr(payload), _ptr(stats), C.byref(ts)))
+            self._ck(self.lib.mgpu_rx_batch_taps(self.h, _ptr(bb), F, _ptr(payload), _ptr(stats), C.byref(ts)))
             out.update(t)
         else:
             llr = np.zeros((F, 1600), np.float32) if want_llr else None
-            self._ck(self.lib.mgpu_rx_batch(self.h, _ptr(bb), C.c_int(F), _ptr(payload), _ptr(stats), _ptr(llr)))
+            self._ck(self.lib.mgpu_rx_batch(self.h, _ptr(bb), F, _ptr(payload), _ptr(stats), _ptr(llr)))
             if want_llr:
                 out["llr_ldpc"] = llr
         return out
@@ -1056,21 +928,7 @@ class RxPhy:
         F = l.shape[0]
         rows = _group_args(F, D, groups)[4]
         out = np.zeros((rows, 1600), np.float32)
-        self.lib.mgpu_device_malloc.restype = C.c_void_p
-        self.lib.mgpu_device_malloc.argtypes = [C.c_void_p, C.c_size_t]
-        self.lib.mgpu_device_free.argtypes = [C.c_void_p, C.c_void_p]
-        self.lib.mgpu_copy_to_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        self.lib.mgpu_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        d_in, d_out = self.lib.mgpu_device_malloc(self.h, max(l.nbytes, 16)), self.lib.mgpu_device_malloc(self.h, max(out.nbytes, 16))
-        try:
-            if not d_in or not d_out:
-                raise MgpuError("device allocation failed")
-            self._ck(self.lib.mgpu_copy_to_device(self.h, d_in, _ptr(l), l.nbytes, None))
-            self.llr_combine_dev(d_in, F, d_out, D=D, groups=groups)
-            self._ck(self.lib.mgpu_copy_to_host(self.h, _ptr(out), d_out, out.nbytes, None))
-        finally:
-            self.lib.mgpu_device_free(self.h, d_in)
-            self.lib.mgpu_device_free(self.h, d_out)
+        self._staged([l], [out], "device allocation failed", lambda d_in, d_out: self.llr_combine_dev(d_in, F, d_out, D=D, groups=groups))
         return out
 
     def ldpc_decode(self, llr):
@@ -1079,7 +937,7 @@ class RxPhy:
         F = l.shape[0]
         bits = np.zeros((F, self.K), np.uint8)
         iters = np.zeros(F, np.int32)
-        self._ck(self.lib.mgpu_ldpc_batch(self.h, _ptr(l), C.c_int(F), _ptr(bits), _ptr(iters)))
+        self._ck(self.lib.mgpu_ldpc_batch(self.h, _ptr(l), F, _ptr(bits), _ptr(iters)))
         return bits, iters
 
     # ---- device-buffer entry points (raw device pointers, e.g. torch tensor.data_ptr()) --------
@@ -1090,7 +948,7 @@ class RxPhy:
         if b.shape[1] != self.K:
             raise MgpuError("a data word is K = %d bits" % self.K)
         out = np.zeros((b.shape[0], self.N), np.uint8)
-        self._ck(self.lib.mgpu_ldpc_encode_batch(self.h, _ptr(b), C.c_int(b.shape[0]), _ptr(out)))
+        self._ck(self.lib.mgpu_ldpc_encode_batch(self.h, _ptr(b), b.shape[0], _ptr(out)))
         return out
 
     def receive_dev(self, d_baseband, F, d_payload, d_stats, d_llr=None, stream=None):
@@ -1118,8 +976,7 @@ class RxPhy:
             ch = _hf("awgn" if hf_channel is None else hf_channel)
             self._ck(self.lib.mgpu_baseband_test_esn0_div(self.h, _ptr(pts), pts.size, frames_per_point, seed, frame0, C.byref(ch), int(diversity), out))
         elif hf_channel is None:
-            self._ck(self.lib.mgpu_baseband_test_esn0(self.h, _ptr(pts), C.c_int(pts.size), C.c_longlong(frames_per_point), C.c_uint64(seed),
-                                                      C.c_uint64(frame0), C.c_int(channel), out))
+            self._ck(self.lib.mgpu_baseband_test_esn0(self.h, _ptr(pts), pts.size, frames_per_point, seed, frame0, channel, out))
         else:
             if channel != 0:
                 raise MgpuError("hf_channel replaces the generator's static echo: channel must be 0")
@@ -1150,12 +1007,12 @@ class RxPhy:
         W, nslots = e.shape[0], e.shape[1]
         ss = None if search_start is None else np.ascontiguousarray(search_start, np.int32)
         d = np.zeros(W, np.int32)
-        self._ck(self.lib.mgpu_debug_mfsk_sync(self.h, _ptr(e), C.c_int(W), C.c_int(nslots), C.c_int(size), _ptr(ss), C.c_int(variant), _ptr(d)))
+        self._ck(self.lib.mgpu_debug_mfsk_sync(self.h, _ptr(e), W, nslots, size, _ptr(ss), variant, _ptr(d)))
         return d
 
     def debug_p2b_variant(self, variant):
         """Test hook (process-wide): -1 = sliding-tap passband_to_baseband kernels where they apply, 0 = generic kernel. Returns the old value."""
-        return int(self.lib.mgpu_debug_p2b_variant(C.c_int(variant)))
+        return int(self.lib.mgpu_debug_p2b_variant(variant))
 
     def debug_span_energy(self, z, wv, off, length, variant):
         """Test hook: (sum, count) of |z|^2 over `length` samples from off[j] in window wv[j] (clipped at the window end), sample order."""
@@ -1164,8 +1021,7 @@ class RxPhy:
         off = np.ascontiguousarray(off, np.int32)
         s = np.zeros(wv.size, np.float64)
         c = np.zeros(wv.size, np.int32)
-        self._ck(self.lib.mgpu_debug_span_energy(self.h, _ptr(z), C.c_int(z.shape[0]), C.c_int(z.shape[1]), _ptr(wv), _ptr(off), C.c_int(wv.size),
-                                                 C.c_int(length), C.c_int(variant), _ptr(s), _ptr(c)))
+        self._ck(self.lib.mgpu_debug_span_energy(self.h, _ptr(z), z.shape[0], z.shape[1], _ptr(wv), _ptr(off), wv.size, length, variant, _ptr(s), _ptr(c)))
         return s, c
 
     def passband_test_esn0(self, esn0_db, frames_per_point, carrier_hz, seed=1, frame0=0, want_windows=False, output_power_watt=0.1, hf_channel=None):
@@ -1178,8 +1034,7 @@ class RxPhy:
             win = np.zeros((pts.size * frames_per_point, self.receive_buffer_samples()), np.float64)
             sent = np.zeros((pts.size * frames_per_point, self.payload_stride), np.uint8)
         if hf_channel is None:
-            self._ck(self.lib.mgpu_passband_test_esn0(self.h, _ptr(pts), C.c_int(pts.size), C.c_longlong(frames_per_point), C.c_uint64(seed),
-                                                      C.c_uint64(frame0), C.c_double(carrier_hz), C.c_double(output_power_watt), out,
+            self._ck(self.lib.mgpu_passband_test_esn0(self.h, _ptr(pts), pts.size, frames_per_point, seed, frame0, carrier_hz, output_power_watt, out,
                                                       _ptr(win) if want_windows else None, _ptr(sent) if want_windows else None))
         else:
             self._ck(self.lib.mgpu_passband_test_esn0_hf(self.h, _ptr(pts), pts.size, frames_per_point, seed, frame0, carrier_hz, output_power_watt,
@@ -1199,8 +1054,7 @@ class RxPhy:
         if count is None:
             count = (n + decimation - 1) // decimation
         out = np.zeros((W, count), np.complex128)
-        self._ck(self.lib.mgpu_passband_to_baseband(self.h, _ptr(x), C.c_int(W), C.c_int(n), _ptr(fc), C.c_int(which), _ptr(st),
-                                                    C.c_int(count), C.c_int(decimation), _ptr(out)))
+        self._ck(self.lib.mgpu_passband_to_baseband(self.h, _ptr(x), W, n, _ptr(fc), which, _ptr(st), count, decimation, _ptr(out)))
         return out
 
     def time_sync_preamble(self, baseband_interp, step, location_to_return=0, nTrials_max=1):
@@ -1209,8 +1063,7 @@ class RxPhy:
         W, size = z.shape
         delay = np.zeros(W, np.int32)
         corr = np.zeros(W, np.float64)
-        self._ck(self.lib.mgpu_time_sync_preamble(self.h, _ptr(z), C.c_int(W), C.c_int(size), C.c_int(step), C.c_int(location_to_return),
-                                                  C.c_int(nTrials_max), _ptr(delay), _ptr(corr)))
+        self._ck(self.lib.mgpu_time_sync_preamble(self.h, _ptr(z), W, size, step, location_to_return, nTrials_max, _ptr(delay), _ptr(corr)))
         return delay, corr
 
     def debug_tsync_metric(self, baseband_interp, step, variant=-1, start=None, sub_size=None):
@@ -1224,7 +1077,7 @@ class RxPhy:
         vals = np.zeros((W, ncand), np.float64)
         st = None if start is None else np.ascontiguousarray(start, np.int32)
         sz = None if sub_size is None else np.ascontiguousarray(sub_size, np.int32)
-        self._ck(self.lib.mgpu_debug_tsync_metric(self.h, _ptr(z), C.c_int(W), C.c_int(size), C.c_int(step), C.c_int(variant),
+        self._ck(self.lib.mgpu_debug_tsync_metric(self.h, _ptr(z), W, size, step, variant,
                                                   _ptr(st) if st is not None else None, _ptr(sz) if sz is not None else None, _ptr(vals)))
         return vals
 
@@ -1233,7 +1086,7 @@ class RxPhy:
         z = z.reshape(1, -1) if z.ndim == 1 else z
         W, stride = z.shape
         out = np.zeros(W, np.float64)
-        self._ck(self.lib.mgpu_freq_sync(self.h, _ptr(z), C.c_int(W), C.c_int(stride), _ptr(out)))
+        self._ck(self.lib.mgpu_freq_sync(self.h, _ptr(z), W, stride, _ptr(out)))
         return out
 
     def time_sync_mfsk(self, baseband_interp, search_start_symb=0):
@@ -1242,7 +1095,7 @@ class RxPhy:
         z = z.reshape(1, -1) if z.ndim == 1 else z
         W, size = z.shape
         delay = np.zeros(W, np.int32)
-        self._ck(self.lib.mgpu_time_sync_mfsk(self.h, _ptr(z), C.c_int(W), C.c_int(size), C.c_int(search_start_symb), _ptr(delay)))
+        self._ck(self.lib.mgpu_time_sync_mfsk(self.h, _ptr(z), W, size, search_start_symb, _ptr(delay)))
         return delay
 
     def detect_ack_pattern(self, baseband_interp, pattern=1):
@@ -1252,7 +1105,7 @@ class RxPhy:
         W, size = z.shape
         metric = np.zeros(W, np.float64)
         matched = np.zeros(W, np.int32)
-        self._ck(self.lib.mgpu_detect_ack_pattern(self.h, _ptr(z), C.c_int(W), C.c_int(size), C.c_int(pattern), _ptr(metric), _ptr(matched)))
+        self._ck(self.lib.mgpu_detect_ack_pattern(self.h, _ptr(z), W, size, pattern, _ptr(metric), _ptr(matched)))
         return metric, matched
 
     def detect_ack_pattern_from_passband(self, passband, carrier_hz, pattern=1):
@@ -1262,8 +1115,7 @@ class RxPhy:
         W, size = x.shape
         metric = np.zeros(W, np.float64)
         matched = np.zeros(W, np.int32)
-        self._ck(self.lib.mgpu_detect_ack_pattern_from_passband(self.h, _ptr(x), C.c_int(W), C.c_int(size), C.c_double(carrier_hz),
-                                                                C.c_int(pattern), _ptr(metric), _ptr(matched)))
+        self._ck(self.lib.mgpu_detect_ack_pattern_from_passband(self.h, _ptr(x), W, size, carrier_hz, pattern, _ptr(metric), _ptr(matched)))
         return metric, matched
 
     # ---- the whole of receive_byte on capture windows (include/mercury_rxloop.h) -------------
@@ -1288,9 +1140,9 @@ class RxPhy:
         payload = np.zeros((W, self.payload_stride), np.uint8)
         stats = np.zeros(W, RECEIVE_STATS_DTYPE)
         if fmt:
-            self._ck(self.lib.mgpu_receive_byte_batch_samples(self.h, _ptr(x), C.c_int(fmt), C.c_int(W), C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
+            self._ck(self.lib.mgpu_receive_byte_batch_samples(self.h, _ptr(x), fmt, W, C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
         else:
-            self._ck(self.lib.mgpu_receive_byte_batch(self.h, _ptr(x), C.c_int(W), C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
+            self._ck(self.lib.mgpu_receive_byte_batch(self.h, _ptr(x), W, C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
         return {"payload": payload, "stats": stats, "state": st}
 
     def transmit_frame_samples(self):
@@ -1308,18 +1160,18 @@ class RxPhy:
         n = 3 * self.transmit_frame_samples()
         if buffer is None:
             out = np.zeros(n)
-            self._ck(self.lib.mgpu_transmit_buffer(self.h, _ptr(out), C.c_int(0)))
+            self._ck(self.lib.mgpu_transmit_buffer(self.h, _ptr(out), 0))
             return out
         b = np.ascontiguousarray(buffer, np.float64)
         if b.size != n:
             raise MgpuError("the transmit buffer is 3 frames = %d samples" % n)
-        self._ck(self.lib.mgpu_transmit_buffer(self.h, _ptr(b), C.c_int(1)))
+        self._ck(self.lib.mgpu_transmit_buffer(self.h, _ptr(b), 1))
         return b
 
     def pre_equalization_channel(self, carrier_hz):
         """cl_telecom_system::get_pre_equalization_channel for this mode and carrier (host computation): complex128 [Nc]."""
         out = np.zeros(self.Nc, np.complex128)
-        self._ck(self.lib.mgpu_context_pre_equalization_channel(self.h, C.c_double(carrier_hz), _ptr(out)))
+        self._ck(self.lib.mgpu_context_pre_equalization_channel(self.h, carrier_hz, _ptr(out)))
         return out
 
     def set_pre_equalization_channel(self, channel):
@@ -1339,7 +1191,7 @@ class RxPhy:
         cfg = self.transmit_config(carrier_hz, **kw)
         nb = None if nbytes is None else np.ascontiguousarray(nbytes, np.int32)
         out = np.zeros((F, self.transmit_frame_samples()), np.float64)
-        self._ck(self.lib.mgpu_transmit_byte_batch(self.h, _ptr(pl), C.c_int(stride), None if nb is None else _ptr(nb), C.c_int(F), C.byref(cfg),
+        self._ck(self.lib.mgpu_transmit_byte_batch(self.h, _ptr(pl), stride, None if nb is None else _ptr(nb), F, C.byref(cfg),
                                                    _ptr(out)))
         return out
 
@@ -1348,26 +1200,25 @@ class RxPhy:
         b = np.ascontiguousarray(bits, np.uint8).reshape(-1, self.nReal)
         cfg = self.transmit_config(carrier_hz, **kw)
         out = np.zeros((b.shape[0], self.transmit_frame_samples()), np.float64)
-        self._ck(self.lib.mgpu_transmit_bit_batch(self.h, _ptr(b), C.c_int(b.shape[0]), C.byref(cfg), _ptr(out)))
+        self._ck(self.lib.mgpu_transmit_bit_batch(self.h, _ptr(b), b.shape[0], C.byref(cfg), _ptr(out)))
         return out
 
     def transmit_byte_dev(self, d_payload, payload_stride, F, d_passband, carrier_hz, d_nbytes=None, stream=None, **kw):
         cfg = self.transmit_config(carrier_hz, **kw)
-        self._ck(self.lib.mgpu_transmit_byte_batch_dev(self.h, C.c_void_p(d_payload), C.c_int(payload_stride), C.c_void_p(d_nbytes), C.c_int(F),
-                                                       C.byref(cfg), C.c_void_p(d_passband), C.c_void_p(stream)))
+        self._ck(self.lib.mgpu_transmit_byte_batch_dev(self.h, d_payload, payload_stride, d_nbytes, F, C.byref(cfg), d_passband, stream))
 
     def generate_ack_pattern_passband(self, pattern=1, carrier_hz=None, **kw):
         """cl_telecom_system::generate_ack_pattern_passband (pattern 1) / generate_break_pattern_passband (2) -> float64 [16*Nofdm*4]."""
         cfg = self.transmit_config(carrier_hz, **kw)
         out = np.zeros(16 * self.Nofdm * 4, np.float64)
-        self._ck(self.lib.mgpu_generate_ack_pattern_passband(self.h, C.c_int(pattern), C.byref(cfg), _ptr(out)))
+        self._ck(self.lib.mgpu_generate_ack_pattern_passband(self.h, pattern, C.byref(cfg), _ptr(out)))
         return out
 
     def symbol_mod(self, carriers):
         """cl_ofdm::symbol_mod: complex128 [n, Nc] -> [n, Nofdm]."""
         x = np.ascontiguousarray(carriers, np.complex128).reshape(-1, self.Nc)
         out = np.zeros((x.shape[0], self.Nofdm), np.complex128)
-        self._ck(self.lib.mgpu_symbol_mod(self.h, _ptr(x), C.c_int(x.shape[0]), _ptr(out)))
+        self._ck(self.lib.mgpu_symbol_mod(self.h, _ptr(x), x.shape[0], _ptr(out)))
         return out
 
     def measure_signal_only(self, passband, carrier_hz):
@@ -1377,7 +1228,7 @@ class RxPhy:
         if x.shape[1] != self.receive_buffer_samples():
             raise MgpuError("a capture window is %d samples" % self.receive_buffer_samples())
         out = np.zeros(x.shape[0], np.float64)
-        self._ck(self.lib.mgpu_measure_signal_only(self.h, _ptr(x), C.c_int(x.shape[0]), C.c_double(carrier_hz), _ptr(out)))
+        self._ck(self.lib.mgpu_measure_signal_only(self.h, _ptr(x), x.shape[0], carrier_hz, _ptr(out)))
         return out
 
     def receive_byte_dev(self, d_passband, W, carrier_hz, trials_max=2, use_last_good_time_sync=1, use_last_good_freq_offset=1, state=None,
@@ -1389,7 +1240,7 @@ class RxPhy:
             st["delay_of_last_decoded_message"] = -1
         payload = np.zeros((W, self.payload_stride), np.uint8)
         stats = np.zeros(W, RECEIVE_STATS_DTYPE)
-        self._ck(self.lib.mgpu_receive_byte_batch(self.h, C.c_void_p(d_passband), C.c_int(W), C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
+        self._ck(self.lib.mgpu_receive_byte_batch(self.h, d_passband, W, C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
         return {"payload": payload, "stats": stats, "state": st}
 
     def receive_byte_samples_dev(self, d_capture, sample_format, W, carrier_hz, trials_max=2, use_last_good_time_sync=1, use_last_good_freq_offset=1,
@@ -1401,7 +1252,7 @@ class RxPhy:
             st["delay_of_last_decoded_message"] = -1
         payload = np.zeros((W, self.payload_stride), np.uint8)
         stats = np.zeros(W, RECEIVE_STATS_DTYPE)
-        self._ck(self.lib.mgpu_receive_byte_batch_samples(self.h, C.c_void_p(d_capture), C.c_int(sample_format), C.c_int(W), C.byref(cfg), _ptr(st),
+        self._ck(self.lib.mgpu_receive_byte_batch_samples(self.h, d_capture, sample_format, W, C.byref(cfg), _ptr(st),
                                                           _ptr(payload), _ptr(stats)))
         return {"payload": payload, "stats": stats, "state": st}
 
@@ -1414,7 +1265,7 @@ class RxPhy:
         """Device atan / sin / cos (csrc/glibc_trig.h) of a float64 array."""
         xin = np.ascontiguousarray(x, np.float64)
         a, s, c = np.zeros_like(xin), np.zeros_like(xin), np.zeros_like(xin)
-        self._ck(self.lib.mgpu_debug_glibc_trig(self.h, _ptr(xin), C.c_int(xin.size), _ptr(a), _ptr(s), _ptr(c)))
+        self._ck(self.lib.mgpu_debug_glibc_trig(self.h, _ptr(xin), xin.size, _ptr(a), _ptr(s), _ptr(c)))
         return a, s, c
 
     def debug_spa_math(self, x):
@@ -1422,11 +1273,11 @@ class RxPhy:
         xin = np.ascontiguousarray(x, np.float64).ravel()
         t = np.zeros_like(xin)
         a = np.zeros_like(xin)
-        self._ck(self.lib.mgpu_debug_spa_math(self.h, _ptr(xin), C.c_int(xin.size), _ptr(t), _ptr(a)))
+        self._ck(self.lib.mgpu_debug_spa_math(self.h, _ptr(xin), xin.size, _ptr(t), _ptr(a)))
         return t, a
 
     def enable_timing(self, on=True):
-        self._ck(self.lib.mgpu_enable_timing(self.h, C.c_int(1 if on else 0)))
+        self._ck(self.lib.mgpu_enable_timing(self.h, 1 if on else 0))
 
     def host_path_last(self):
         """Profile of the last chunked mgpu_rx_batch call: dict(chunk_frames, n_chunks, fill_ms, drain_ms, total_ms)."""
@@ -1469,7 +1320,7 @@ def pool_shard(F, G, g):
     """Frames of device g of G: (first, count) — mgpu_pool_shard, callable without a GPU."""
     lib = load_library()
     a, n = C.c_int(), C.c_int()
-    lib.mgpu_pool_shard(C.c_int(F), C.c_int(G), C.c_int(g), C.byref(a), C.byref(n))
+    lib.mgpu_pool_shard(F, G, g, C.byref(a), C.byref(n))
     return a.value, n.value
 
 
@@ -1479,26 +1330,26 @@ class RxPool:
     def __init__(self, cfg, devices, max_iters=50, decoder=DEC_SPA, agc=1, variance_source=1, max_batch=4096, minsum_alpha=0.0,
                  mfsk_ctrl_mode=False):
         self.lib = load_library()
-        self.lib.mgpu_pool_context.restype = C.c_void_p
-        self.lib.mgpu_pool_last_error.restype = C.c_char_p
         self.h = C.c_void_p()
         c = Config(cfg, max_iters, decoder, agc, variance_source, 0, max_batch, minsum_alpha, 1 if mfsk_ctrl_mode else 0)
         devs = (C.c_int * len(devices))(*devices)
-        rc = self.lib.mgpu_pool_create(C.byref(c), devs, C.c_int(len(devices)), C.byref(self.h))
+        rc = self.lib.mgpu_pool_create(C.byref(c), devs, len(devices), C.byref(self.h))
         if rc != 0:
             raise MgpuError("mgpu_pool_create failed (%d): %s" % (rc, self.lib.mgpu_pool_last_error(None).decode()))
         self.n_devices = len(devices)
         i = Info()
-        ctx0 = C.c_void_p(self.lib.mgpu_pool_context(self.h, 0))
-        if self.lib.mgpu_get_info(ctx0, C.byref(i)) != 0:
+        self._ctx0 = self._ctx(0)
+        if self.lib.mgpu_get_info(self._ctx0, C.byref(i)) != 0:
             raise MgpuError("mgpu_get_info failed")
         for n in INFO_FIELDS:
             setattr(self, n, getattr(i, n))
-        self._ctx0 = ctx0
+
+    def _ctx(self, g):
+        return self.lib.mgpu_pool_context(self.h, g)
 
     def numa_nodes(self):
         """NUMA node of every context's device (mgpu_pool_device_numa_node; -1: the platform names none)."""
-        return [int(self.lib.mgpu_pool_device_numa_node(self.h, C.c_int(g))) for g in range(self.n_devices)]
+        return [int(self.lib.mgpu_pool_device_numa_node(self.h, g)) for g in range(self.n_devices)]
 
     def _ck(self, rc):
         if rc != 0:
@@ -1526,7 +1377,7 @@ class RxPool:
         F = bb.shape[0]
         payload = np.zeros((F, self.payload_stride), np.uint8)
         stats = np.zeros(F, STATS_DTYPE)
-        self._ck(self.lib.mgpu_pool_rx_batch(self.h, _ptr(bb), C.c_int(F), _ptr(payload), _ptr(stats)))
+        self._ck(self.lib.mgpu_pool_rx_batch(self.h, _ptr(bb), F, _ptr(payload), _ptr(stats)))
         return {"payload": payload, "stats": stats}
 
     def ldpc_decode(self, llr):
@@ -1534,7 +1385,7 @@ class RxPool:
         F = l.shape[0]
         bits = np.zeros((F, self.K), np.uint8)
         iters = np.zeros(F, np.int32)
-        self._ck(self.lib.mgpu_pool_ldpc_batch(self.h, _ptr(l), C.c_int(F), _ptr(bits), _ptr(iters)))
+        self._ck(self.lib.mgpu_pool_ldpc_batch(self.h, _ptr(l), F, _ptr(bits), _ptr(iters)))
         return bits, iters
 
     # ---- device-resident shards: one pointer and one count per pool device (mercury_pool.h) ----
@@ -1550,40 +1401,36 @@ class RxPool:
         out = []
         for g in range(self.n_devices):
             a, b = C.c_int(), C.c_int()
-            self.lib.mgpu_pool_shard(C.c_int(F), C.c_int(self.n_devices), C.c_int(g), C.byref(a), C.byref(b))
+            self.lib.mgpu_pool_shard(F, self.n_devices, g, C.byref(a), C.byref(b))
             out.append((a.value, b.value))
         return out
 
     def device_malloc(self, g, nbytes):
-        self.lib.mgpu_device_malloc.restype = C.c_void_p
-        ctx = C.c_void_p(self.lib.mgpu_pool_context(self.h, g))
-        p = self.lib.mgpu_device_malloc(ctx, C.c_size_t(nbytes))
+        p = self.lib.mgpu_device_malloc(self._ctx(g), nbytes)
         if not p:
             raise MgpuError("mgpu_device_malloc(%d bytes) failed on pool device %d" % (nbytes, g))
         return p
 
     def device_free(self, g, ptr):
-        self.lib.mgpu_device_free(C.c_void_p(self.lib.mgpu_pool_context(self.h, g)), C.c_void_p(ptr))
+        self.lib.mgpu_device_free(self._ctx(g), ptr)
 
     def copy_to_host(self, g, dst, d_src):
         """dst: a numpy array; blocking copy from pool device g."""
-        ctx = C.c_void_p(self.lib.mgpu_pool_context(self.h, g))
-        rc = self.lib.mgpu_copy_to_host(ctx, _ptr(dst), C.c_void_p(d_src), C.c_size_t(dst.nbytes), None)
+        rc = self.lib.mgpu_copy_to_host(self._ctx(g), _ptr(dst), d_src, dst.nbytes, None)
         if rc != 0:
             raise MgpuError("mgpu_copy_to_host failed (%d)" % rc)
         return dst
 
     def copy_to_device(self, g, d_dst, src):
         src = np.ascontiguousarray(src)
-        ctx = C.c_void_p(self.lib.mgpu_pool_context(self.h, g))
-        rc = self.lib.mgpu_copy_to_device(ctx, C.c_void_p(d_dst), _ptr(src), C.c_size_t(src.nbytes), None)
+        rc = self.lib.mgpu_copy_to_device(self._ctx(g), d_dst, _ptr(src), src.nbytes, None)
         if rc != 0:
             raise MgpuError("mgpu_copy_to_device failed (%d)" % rc)
 
     def txgen_dev(self, seed, frame0, counts, noise_amp, d_bb, d_payload=None, channel=0):
         n = self.n_devices
         cnt = (C.c_int * n)(*counts)
-        self._ck(self.lib.mgpu_pool_txgen_dev(self.h, C.c_uint64(seed), C.c_uint64(frame0), cnt, C.c_double(noise_amp), C.c_int(channel),
+        self._ck(self.lib.mgpu_pool_txgen_dev(self.h, seed, frame0, cnt, noise_amp, channel,
                                               self._ptrs(d_bb, n), self._ptrs(d_payload, n)))
 
     def receive_dev(self, d_bb, counts, d_payload, d_stats):
@@ -1598,14 +1445,14 @@ class RxPool:
 
     def enable_timing(self, on=True):
         for g in range(self.n_devices):
-            self.lib.mgpu_enable_timing(C.c_void_p(self.lib.mgpu_pool_context(self.h, g)), C.c_int(1 if on else 0))
+            self.lib.mgpu_enable_timing(self._ctx(g), 1 if on else 0)
 
     def decoder_hard_frames(self):
         """Frames the pool's fp64 decoders have decided without iterating since the pool was created (sum over its devices)."""
         total = 0
         for g in range(self.n_devices):
             n = C.c_longlong(0)
-            self.lib.mgpu_decoder_hard_frames(C.c_void_p(self.lib.mgpu_pool_context(self.h, g)), C.byref(n))
+            self.lib.mgpu_decoder_hard_frames(self._ctx(g), C.byref(n))
             total += int(n.value)
         return total
 
@@ -1613,7 +1460,7 @@ class RxPool:
         """(front-end ms, decoder ms, launches) averaged since enable_timing on pool device g."""
         ms = (C.c_float * 2)()
         n = C.c_int()
-        self.lib.mgpu_kernel_ms_avg(C.c_void_p(self.lib.mgpu_pool_context(self.h, g)), ms, C.byref(n))
+        self.lib.mgpu_kernel_ms_avg(self._ctx(g), ms, C.byref(n))
         return float(ms[0]), float(ms[1]), n.value
 
     def receive_buffer_samples(self):
@@ -1628,21 +1475,19 @@ class RxPool:
             x = x.reshape(1, -1) if x.ndim == 1 else x
             W, src = x.shape[0], _ptr(x)
         else:
-            src = C.c_void_p(passband)
+            src = passband
         cfg = ReceiveConfig(carrier_hz, trials_max, use_last_good_time_sync, use_last_good_freq_offset, coarse_freq_sync)
         st = np.zeros(W, LINK_STATE_DTYPE) if state is None else np.ascontiguousarray(state, LINK_STATE_DTYPE)
         if state is None:
             st["delay_of_last_decoded_message"] = -1
         payload = np.zeros((W, self.payload_stride), np.uint8)
         stats = np.zeros(W, RECEIVE_STATS_DTYPE)
-        self._ck(self.lib.mgpu_pool_receive_byte_batch(self.h, src, C.c_int(W), C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
+        self._ck(self.lib.mgpu_pool_receive_byte_batch(self.h, src, W, C.byref(cfg), _ptr(st), _ptr(payload), _ptr(stats)))
         return {"payload": payload, "stats": stats, "state": st}
 
 
 # ---- the receive loop over continuous captures (include/mercury_capture.h) ------------------------------------------------------------
-CAPTURE_SYMBOLS = ["mgpu_capture_create", "mgpu_capture_destroy", "mgpu_capture_geometry_get", "mgpu_capture_feed", "mgpu_capture_process",
-                   "mgpu_capture_run", "mgpu_capture_get_state", "mgpu_capture_set_state", "mgpu_capture_window", "mgpu_host_capture_prep",
-                   "mgpu_host_capture_process", "mgpu_host_capture_init_state"]
+CAPTURE_SYMBOLS = names("mercury_capture.h")
 CAPTURE_HELD_DTYPE = np.dtype([("iterations_done", "<i4"), ("message_decoded", "<i4"), ("crc", "<i4"), ("all_zeros", "<i4"), ("delay", "<i4"),
                                ("sync_trials", "<i4"), ("frame_overflow_symbols", "<i4"), ("snr_db", "<f8"), ("freq_offset", "<f8"),
                                ("coarse_metric", "<f8"), ("signal_strength_dbm", "<f8")], align=True)
@@ -1677,7 +1522,7 @@ def host_capture_prep(geometry, window, samples, state):
     x = np.ascontiguousarray(samples)
     assert window.dtype == np.float64 and window.flags.c_contiguous and window.size == geometry.buffer_nsymb * geometry.symbol_period
     assert x.size == geometry.symbol_period and state.dtype == CAPTURE_STATE_DTYPE
-    if load_library().mgpu_host_capture_prep(C.byref(geometry), _ptr(window), _ptr(x), C.c_int(_sample_format(x.dtype)), _ptr(state)) != 0:
+    if load_library().mgpu_host_capture_prep(C.byref(geometry), _ptr(window), _ptr(x), _sample_format(x.dtype), _ptr(state)) != 0:
         raise MgpuError("mgpu_host_capture_prep: bad argument")
 
 
@@ -1708,7 +1553,7 @@ class RxCapture:
         init = None
         if initial_windows is not None:
             init = np.ascontiguousarray(initial_windows, np.float64).reshape(S, -1)
-        rx._ck(self.lib.mgpu_capture_create(rx.h, C.c_int(S), C.byref(cfg), _ptr(init), C.c_int(max_hops), C.byref(self.h)))
+        rx._ck(self.lib.mgpu_capture_create(rx.h, S, C.byref(cfg), _ptr(init), max_hops, C.byref(self.h)))
         self.geometry = CaptureGeometry()
         rx._ck(self.lib.mgpu_capture_geometry_get(self.h, C.byref(self.geometry)))
         self.P = self.geometry.symbol_period
@@ -1734,7 +1579,7 @@ class RxCapture:
             if fmt is None or not samples.is_contiguous():
                 raise MgpuError("device samples: a contiguous float64 / int32 / int16 / float32 tensor")
             n = samples.numel()
-            ptr, keep = C.c_void_p(samples.data_ptr()), samples
+            ptr, keep = samples.data_ptr(), samples
         else:
             x = np.ascontiguousarray(samples)
             fmt, n, ptr, keep = _sample_format(x.dtype), x.size, _ptr(x), x
@@ -1744,7 +1589,7 @@ class RxCapture:
 
     def feed(self, samples):
         ptr, fmt, H, _keep = self._samples(samples)
-        self.rx._ck(self.lib.mgpu_capture_feed(self.h, ptr, C.c_int(fmt), C.c_int(H)))
+        self.rx._ck(self.lib.mgpu_capture_feed(self.h, ptr, fmt, H))
 
     def process(self):
         """-> dict(ran [S] bool, stats [S] RECEIVE_STATS_DTYPE, payload [S, stride]); stats / payload are zero where ran is False"""
@@ -1761,7 +1606,7 @@ class RxCapture:
         ev = np.zeros(m, CAPTURE_EVENT_DTYPE)
         pl = np.zeros((m, self.payload_stride), np.uint8)
         n = C.c_int()
-        self.rx._ck(self.lib.mgpu_capture_run(self.h, ptr, C.c_int(fmt), C.c_int(H), _ptr(ev), _ptr(pl), C.c_int(m), C.byref(n)))
+        self.rx._ck(self.lib.mgpu_capture_run(self.h, ptr, fmt, H, _ptr(ev), _ptr(pl), m, C.byref(n)))
         nb = self.rx.payload_bytes
         return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
 
@@ -1776,22 +1621,22 @@ class RxCapture:
         ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
         pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
         n = C.c_int()
-        self.rx._ck(_chan_argtypes(self.lib).mgpu_capture_run_wideband(self.h, chan.h, ptr, fmt, H, _ptr(ev), _ptr(pl), m, C.byref(n)))
+        self.rx._ck(self.lib.mgpu_capture_run_wideband(self.h, chan.h, ptr, fmt, H, _ptr(ev), _ptr(pl), m, C.byref(n)))
         nb = self.rx.payload_bytes
         return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
 
     def state(self, s):
         st = np.zeros((), CAPTURE_STATE_DTYPE)
-        self.rx._ck(self.lib.mgpu_capture_get_state(self.h, C.c_int(s), _ptr(st)))
+        self.rx._ck(self.lib.mgpu_capture_get_state(self.h, s, _ptr(st)))
         return st
 
     def set_state(self, s, st):
         st = np.ascontiguousarray(st, CAPTURE_STATE_DTYPE)
-        self.rx._ck(self.lib.mgpu_capture_set_state(self.h, C.c_int(s), _ptr(st)))
+        self.rx._ck(self.lib.mgpu_capture_set_state(self.h, s, _ptr(st)))
 
     def window(self, s):
         out = np.zeros(self.window_samples)
-        self.rx._ck(self.lib.mgpu_capture_window(self.h, C.c_int(s), _ptr(out)))
+        self.rx._ck(self.lib.mgpu_capture_window(self.h, s, _ptr(out)))
         return out
 
 
@@ -1800,7 +1645,6 @@ def host_hf_stream_noise(seed, signal, position, n):
     """g(seed, signal, position + i), i < n: the streaming channel's unit noise (host-only twin, no GPU)."""
     out = np.zeros(n)
     lib = load_library()
-    lib.mgpu_host_hf_stream_noise.argtypes = [C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
     if lib.mgpu_host_hf_stream_noise(seed, signal, position, n, _ptr(out)) != 0:
         raise MgpuError("mgpu_host_hf_stream_noise: bad argument")
     return out
@@ -1815,12 +1659,6 @@ class HfStream:
         self.rx, self.lib, self.S = rx, rx.lib, S
         self.h = C.c_void_p()
         lib = self.lib
-        lib.mgpu_hf_stream_create.argtypes = [C.c_void_p, C.POINTER(HfChannel), C.c_double, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
-        lib.mgpu_hf_stream_destroy.argtypes = [C.c_void_p]
-        lib.mgpu_hf_stream_seek.argtypes = [C.c_void_p, C.c_uint64]
-        lib.mgpu_hf_stream_latency.argtypes = [C.c_void_p]
-        lib.mgpu_hf_stream_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        lib.mgpu_hf_stream_apply_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         rx._ck(lib.mgpu_hf_stream_create(rx.h, C.byref(_hf(ch)), fs, S, seed, realisation0, C.byref(self.h)))
         self.latency = int(lib.mgpu_hf_stream_latency(self.h))
 
@@ -1854,8 +1692,7 @@ class HfStream:
 
 
 # ---- link simulator (include/mercury_linksim.h) --------------------------------------------------------------------------------------
-LINKSIM_SYMBOLS = ["mgpu_linksim_create", "mgpu_linksim_destroy", "mgpu_linksim_run", "mgpu_linksim_counters_get", "mgpu_linksim_capture",
-                   "mgpu_linksim_noise_amp", "mgpu_host_linksim_frame_start", "mgpu_host_linksim_payload"]
+LINKSIM_SYMBOLS = names("mercury_linksim.h")
 LINKSIM_COUNTERS_DTYPE = np.dtype([("hops", "<i8"), ("frames_sent", "<i8"), ("delivered", "<i8"), ("duplicates", "<i8"), ("false_decodes", "<i8"),
                                    ("iterations_sum", "<i8"), ("snr_db_sum", "<f8")], align=True)
 
@@ -1880,7 +1717,6 @@ def host_linksim_frame_start(config, frame_samples, symbol_period, link, frame):
     """transmit position of frame `frame` of link `link` (host only)"""
     out = C.c_longlong()
     lib = load_library()
-    lib.mgpu_host_linksim_frame_start.argtypes = [C.POINTER(LinkSimConfig), C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_longlong)]
     if lib.mgpu_host_linksim_frame_start(C.byref(config), frame_samples, symbol_period, link, frame, C.byref(out)) != 0:
         raise MgpuError("mgpu_host_linksim_frame_start: bad argument")
     return out.value
@@ -1890,7 +1726,6 @@ def host_linksim_payload(seed, link, frame, nbytes):
     """the payload link `link` sends in its frame `frame`: uint8 [nbytes] (host only)"""
     out = np.zeros(nbytes, np.uint8)
     lib = load_library()
-    lib.mgpu_host_linksim_payload.argtypes = [C.c_uint64, C.c_int, C.c_longlong, C.c_int, C.c_void_p]
     if lib.mgpu_host_linksim_payload(seed, link, frame, nbytes, _ptr(out)) != 0:
         raise MgpuError("mgpu_host_linksim_payload: bad argument")
     return out
@@ -1922,11 +1757,6 @@ class LinkSim:
             rx.set_estimator_ladder(ladder)
         self.h = C.c_void_p()
         lib = self.lib
-        lib.mgpu_linksim_create.argtypes = [C.c_void_p, C.POINTER(LinkSimConfig), C.c_void_p, C.POINTER(C.c_void_p)]
-        lib.mgpu_linksim_destroy.argtypes = [C.c_void_p]
-        lib.mgpu_linksim_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
-        lib.mgpu_linksim_counters_get.argtypes = [C.c_void_p, C.c_void_p]
-        lib.mgpu_linksim_capture.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         es = None if esn0_db is None else np.ascontiguousarray(np.broadcast_to(np.asarray(esn0_db, np.float64), (self.S,)))
         self.esn0_db = es
         rx._ck(lib.mgpu_linksim_create(rx.h, C.byref(config), _ptr(es), C.byref(self.h)))
@@ -1958,7 +1788,7 @@ class LinkSim:
         pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
         n = C.c_int()
         audio = np.zeros((self.S, H * self.P)) if want_samples else None
-        self.rx._ck(self.lib.mgpu_linksim_run(self.h, C.c_int(H), _ptr(ev), _ptr(pl), C.c_int(m), C.byref(n), _ptr(audio)))
+        self.rx._ck(self.lib.mgpu_linksim_run(self.h, H, _ptr(ev), _ptr(pl), m, C.byref(n), _ptr(audio)))
         nb = self.rx.payload_bytes
         events = [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
         return (events, audio) if want_samples else events
@@ -1971,7 +1801,6 @@ class LinkSim:
     def noise_amp(self):
         """the streaming channel's noise amplitude per link (zeros without noise)"""
         out = np.zeros(self.S)
-        self.lib.mgpu_linksim_noise_amp.argtypes = [C.c_void_p, C.c_void_p]
         self.rx._ck(self.lib.mgpu_linksim_noise_amp(self.h, _ptr(out)))
         return out
 
@@ -1983,9 +1812,7 @@ class LinkSim:
 
 
 # ---- wideband channeliser (include/mercury_channelizer.h) ---------------------------------------------------------------
-CHANNELIZER_SYMBOLS = ["mgpu_chan_create", "mgpu_chan_destroy", "mgpu_chan_latency", "mgpu_chan_seek", "mgpu_chan_retune", "mgpu_chan_process",
-                       "mgpu_chan_process_dev", "mgpu_capture_run_wideband", "mgpu_host_chan_design", "mgpu_host_chan_default_taps",
-                       "mgpu_host_chan_tables", "mgpu_host_chan_process"]
+CHANNELIZER_SYMBOLS = names("mercury_channelizer.h")
 IQ_CS16, IQ_CF32, IQ_CF64 = 0, 1, 2
 CHAN_DEFAULT_TP, CHAN_PHASOR_LEN = 320, 48000
 
@@ -2000,19 +1827,7 @@ class ChanConfig(C.Structure):          # mgpu_chan_config
 
 
 def _chan_argtypes(lib):
-    K, Ch, V = C.POINTER(ChanConfig), C.POINTER(ChanChannel), C.c_void_p
-    lib.mgpu_chan_create.argtypes = [V, K, Ch, C.POINTER(V)]
-    lib.mgpu_chan_destroy.argtypes = [V]
-    lib.mgpu_chan_latency.argtypes = [V]
-    lib.mgpu_chan_seek.argtypes = [V, C.c_uint64]
-    lib.mgpu_chan_retune.argtypes = [V, C.c_int, Ch]
-    lib.mgpu_chan_process.argtypes = [V, V, C.c_int, C.c_int, V]
-    lib.mgpu_chan_process_dev.argtypes = [V, V, C.c_int, C.c_int, V, V]
-    lib.mgpu_capture_run_wideband.argtypes = [V, V, V, C.c_int, C.c_int, V, V, C.c_int, C.POINTER(C.c_int)]
-    lib.mgpu_host_chan_design.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, V, C.POINTER(C.c_int)]
-    lib.mgpu_host_chan_default_taps.argtypes = [C.c_int, V, C.POINTER(C.c_int)]
-    lib.mgpu_host_chan_tables.argtypes = [K, Ch, V, V]
-    lib.mgpu_host_chan_process.argtypes = [K, Ch, V, C.c_int, C.c_int, C.c_uint64, V]
+    """what typed the channeliser's functions before abi.py did it at load; kept, as the identity, for tests written against that binding"""
     return lib
 
 
@@ -2045,7 +1860,7 @@ def _iq(iq):
         if fmt is None or not iq.is_contiguous() or (fmt == IQ_CS16 and (iq.dim() < 1 or iq.shape[-1] != 2)):
             raise MgpuError("device IQ: a contiguous complex64 / complex128 tensor, or int16 with a last axis of 2")
         n = iq.numel() // (2 if fmt == IQ_CS16 else 1)
-        return C.c_void_p(iq.data_ptr()), fmt, n, iq
+        return iq.data_ptr(), fmt, n, iq
     x = np.ascontiguousarray(iq)
     fmt = {np.dtype(np.complex64): IQ_CF32, np.dtype(np.complex128): IQ_CF64, np.dtype(np.int16): IQ_CS16}.get(x.dtype)
     if fmt is None or (fmt == IQ_CS16 and (x.ndim < 1 or x.shape[-1] != 2)):
@@ -2058,7 +1873,7 @@ def host_chan_design(D, tp=None, cutoff_hz=1500.0, atten_db=60.0):
     tp = CHAN_DEFAULT_TP if tp is None else int(tp)
     taps = np.zeros(max(tp, 0) * max(int(D), 0) + 1)
     n = C.c_int()
-    if _chan_argtypes(load_library()).mgpu_host_chan_design(int(D), tp, cutoff_hz, atten_db, _ptr(taps), C.byref(n)) != 0:
+    if load_library().mgpu_host_chan_design(int(D), tp, cutoff_hz, atten_db, _ptr(taps), C.byref(n)) != 0:
         raise MgpuError("mgpu_host_chan_design: bad argument", 1)
     return taps[: n.value]
 
@@ -2069,7 +1884,7 @@ def host_chan_tables(D, channel, taps=None, audio_centre_hz=1472, want_phasor=Fa
     T = keep.size if keep is not None else CHAN_DEFAULT_TP * max(int(D), 0) + 1
     g = np.zeros(T, np.complex128)
     W = np.zeros(CHAN_PHASOR_LEN, np.complex128) if want_phasor else None
-    if _chan_argtypes(load_library()).mgpu_host_chan_tables(C.byref(k), chan_channels([channel]), _ptr(g), _ptr(W)) != 0:
+    if load_library().mgpu_host_chan_tables(C.byref(k), chan_channels([channel]), _ptr(g), _ptr(W)) != 0:
         raise MgpuError("mgpu_host_chan_tables: bad argument", 1)
     return (g, W) if want_phasor else g
 
@@ -2082,7 +1897,7 @@ def host_chan_process(D, channels, iq, position=0, taps=None, audio_centre_hz=14
         k.struct_size = struct_size
     ptr, fmt, n_in, _x = _iq(iq)
     out = np.zeros((len(chs), max(n_in // max(int(D), 1), 1)))
-    if _chan_argtypes(load_library()).mgpu_host_chan_process(C.byref(k), chs, ptr, fmt, n_in, int(position), _ptr(out)) != 0:
+    if load_library().mgpu_host_chan_process(C.byref(k), chs, ptr, fmt, n_in, int(position), _ptr(out)) != 0:
         raise MgpuError("mgpu_host_chan_process: bad argument", 1)
     return out
 
@@ -2093,7 +1908,7 @@ class Channelizer:
     samples (numpy, or a torch tensor on the context's device), a multiple of D of them, and returns float64 [S, n_in // D]."""
 
     def __init__(self, rx, D, channels, taps=None, audio_centre_hz=1472, max_out=0):
-        self.rx, self.lib, self.D = rx, _chan_argtypes(rx.lib), int(D)
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
         self._chs = chan_channels(channels)
         self.S = len(self._chs)
         self.config, self._taps = chan_config(D, self.S, taps, audio_centre_hz, max_out)
@@ -2126,7 +1941,7 @@ class Channelizer:
             import torch
             if not hasattr(iq, "data_ptr") or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() * self.D != self.S * n_in:
                 raise MgpuError("device output: device input and a contiguous float64 tensor [S, n_in // D]")
-            self.rx._ck(self.lib.mgpu_chan_process_dev(self.h, ptr, fmt, n_in, C.c_void_p(out.data_ptr()), stream))
+            self.rx._ck(self.lib.mgpu_chan_process_dev(self.h, ptr, fmt, n_in, out.data_ptr(), stream))
             return out
         if out is None:
             out = np.zeros((self.S, max(n_in // self.D, 1)))

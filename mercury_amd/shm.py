@@ -13,24 +13,10 @@ PAYLOAD_BUFFER_SIZE = 131072         # SHM_PAYLOAD_BUFFER_SIZE, :208
 class ShmRing:
     def __init__(self, base_name=PAYLOAD_NAME, size=PAYLOAD_BUFFER_SIZE, create=True):
         self.lib = load_library()
-        l = self.lib
-        l.mgpu_shm_create.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
-        l.mgpu_shm_connect.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
-        for f in ("close", "destroy", "clear"):
-            getattr(l, "mgpu_shm_" + f).argtypes = [C.c_void_p]
-            getattr(l, "mgpu_shm_" + f).restype = None
-        for f in ("used", "free", "capacity"):
-            getattr(l, "mgpu_shm_" + f).argtypes = [C.c_void_p]
-            getattr(l, "mgpu_shm_" + f).restype = C.c_size_t
-        l.mgpu_shm_write.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-        l.mgpu_shm_read_all.argtypes = [C.c_void_p, C.c_char_p]
-        l.mgpu_shm_read_all.restype = C.c_long
-        l.mgpu_shm_publish_decoded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]
         self.h = C.c_void_p()
         self.size = size
         self.created = create
-        rc = (l.mgpu_shm_create if create else l.mgpu_shm_connect)(base_name.encode(), size, C.byref(self.h))
+        rc = (self.lib.mgpu_shm_create if create else self.lib.mgpu_shm_connect)(base_name.encode(), size, C.byref(self.h))
         if rc != 0:
             raise MgpuError("cannot %s shared-memory ring %s (%d)" % ("create" if create else "connect to", base_name, rc))
 

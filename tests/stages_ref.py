@@ -6,38 +6,16 @@
   tests/test_stages_host.py proves them against the CPU oracle (and the reference's own objects where they were built) before they judge a
   kernel.
 """
-import ctypes as C
-
 import numpy as np
+
+from mercury_amd.abi import PROTOTYPES
 
 from demapper_csi_ref import same_bits  # noqa: F401  (shared with the tests)
 
 MGPU_OK, MGPU_ERR_ARG = 0, 1            # include/mercury_gpu.h
-P, I = C.c_void_p, C.c_int
-SIGNATURES = {                          # include/mercury_stages.h, the context first
-    "mgpu_symbol_demod": [P, P, I, P],
-    "mgpu_automatic_gain_control": [P, P, I],
-    "mgpu_channel_estimator": [P, P, I, P],
-    "mgpu_restore_channel_amplitude": [P, P, I],
-    "mgpu_channel_equalizer": [P, P, P, I, P],
-    "mgpu_measure_variance": [P, P, I, P],
-    "mgpu_deframer": [P, P, I, P],
-    "mgpu_deinterleaver_c128": [P, P, I, I, I, P],
-    "mgpu_deinterleaver_f32": [P, P, I, I, I, P],
-    "mgpu_psk_demod": [P, P, I, P, P],
-    "mgpu_bit_energy_dispersal": [P, P, I, I, P],
-    "mgpu_bit_to_byte": [P, P, I, I, P],
-    "mgpu_crc16_modbus_rtu": [P, P, I, I, P],
-}
+SIGNATURES = PROTOTYPES["mercury_stages.h"]     # the 13 entry points, the context first
 OFDM_ONLY = ("mgpu_automatic_gain_control", "mgpu_channel_estimator", "mgpu_restore_channel_amplitude", "mgpu_channel_equalizer",
              "mgpu_measure_variance", "mgpu_deframer", "mgpu_psk_demod")
-
-
-def bind(lib):
-    for name, args in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = C.c_int, args
-    return lib
 
 
 _NOTHING = np.zeros(16, np.uint8)
@@ -52,7 +30,6 @@ def ptr(a):
 
 def call(rx, name, *args):
     """the raw status of one entry point: arrays go in by address, None as a null pointer, integers as they are"""
-    bind(rx.lib)
     return getattr(rx.lib, name)(rx.h, *[ptr(a) if a is None or isinstance(a, np.ndarray) else int(a) for a in args])
 
 
@@ -76,7 +53,6 @@ class Stages:
 
     def __init__(self, rx):
         self.rx, self.G = rx, rx.Nsymb * rx.Nc
-        bind(rx.lib)
 
     def _go(self, name, *args):
         self.rx._ck(call(self.rx, name, *args))

@@ -1,6 +1,7 @@
 """CPU tests of the drop-in boundary: the C-ABI library loads, exports exactly what include/mercury_gpu.h and
 include/mercury_shm.h declare, and refuses loudly (error code + message, no crash, no CPU fallback) when it cannot run."""
 import ctypes as C
+import glob
 import os
 import re
 
@@ -10,23 +11,114 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_functions():
+SIX_HEADERS = ("mercury_gpu.h", "mercury_shm.h", "mercury_rxloop.h", "mercury_stages.h", "mercury_tx.h", "mercury_pool.h")    # EXPORTED_SYMBOLS
+ALL_HEADERS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "include", "*.h")))
+
+
+def _header_text(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.sub(r"//[^\n]*", " ", text)
+
+
+def _header_functions(headers):
     names = set()
-    for header in ("mercury_gpu.h", "mercury_shm.h", "mercury_rxloop.h", "mercury_stages.h", "mercury_tx.h", "mercury_pool.h"):
-        text = open(os.path.join(ROOT, "include", header)).read()
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-        names |= set(re.findall(r"\b(mgpu_[a-z_0-9]+)\s*\(", text))
+    for header in headers:
+        names |= set(re.findall(r"\b(mgpu_[a-z_0-9]+)\s*\(", _header_text(header)))
     return sorted(names)
 
 
 def test_library_exports_every_declared_symbol():
     from mercury_amd import EXPORTED_SYMBOLS, load_library
     lib = load_library()
-    declared = _header_functions()
+    declared = _header_functions(ALL_HEADERS)
     assert declared, "no declarations parsed"
     for name in declared:
         assert hasattr(lib, name), "declared in include/*.h but not exported: " + name
-    assert sorted(EXPORTED_SYMBOLS) == declared
+    assert sorted(EXPORTED_SYMBOLS) == _header_functions(SIX_HEADERS)
+
+
+# ---- mercury_amd/abi.py against the headers ---------------------------------------------------------------------------------------------
+SCALARS = {"int": "i", "size_t": "z", "uint64_t": "u", "long long": "q", "double": "d"}
+RETURNS = {"int": "i", "void": "v", "size_t": "z", "long": "l"}
+PROTOTYPE = re.compile(r"([A-Za-z_][A-Za-z_0-9 *]*?)\b(mgpu_[a-z_0-9]+)\s*\(([^()]*)\)\s*;")
+
+
+def _parameter_class(decl):
+    """one parameter's letter: const char* is s, every other pointer or array p, a scalar by its type"""
+    decl = " ".join(decl.split())
+    if "*" in decl or "[" in decl:
+        return "s" if re.fullmatch(r"const char ?\* ?\w*", decl) else "p"
+    words = [w for w in decl.split() if w != "const"]
+    return SCALARS[" ".join(words[:-1]) if len(words) > 1 else words[0]]          # (the last word is the parameter's name)
+
+
+def _return_class(decl):
+    decl = " ".join(decl.split())
+    if "*" in decl:
+        return "s" if re.fullmatch(r"const char ?\*", decl) else "p"
+    return RETURNS[decl]
+
+
+def _header_prototypes(header):
+    """{name: signature string} of every mgpu_* prototype the header declares, and how many prototypes that was"""
+    text = re.sub(r"^[ \t]*#.*$", " ", _header_text(header), flags=re.M)
+    found = PROTOTYPE.findall(text)
+    sigs = {}
+    for ret, name, params in found:
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sig = _return_class(ret) + ":" + "".join(_parameter_class(p) for p in params)
+        assert sigs.setdefault(name, sig) == sig, (header, name, "declared twice, differently")
+    return sigs, len(found)
+
+
+def test_prototype_table_matches_every_header():
+    """mercury_amd/abi.py states every prototype by hand; the headers state it in C. Both directions: every declared function is in its
+    header's group with the signature the header gives it, and no group holds a name its header does not declare."""
+    from mercury_amd.abi import PROTOTYPES
+    assert sorted(PROTOTYPES) == ALL_HEADERS
+    parsed = 0
+    for header in ALL_HEADERS:
+        sigs, n = _header_prototypes(header)
+        parsed += n
+        assert sorted(sigs) == _header_functions([header]), header           # the prototype pattern misses no declared name
+        assert sorted(PROTOTYPES[header]) == sorted(sigs), header
+        for name, sig in sigs.items():
+            assert PROTOTYPES[header][name] == sig, (header, name, sig)
+    assert parsed == 189 and parsed >= len(_header_functions(ALL_HEADERS))
+
+
+CHILD = """
+import ctypes as C
+import mercury_amd
+from mercury_amd import abi
+lib = mercury_amd.load_library()
+want = {"i": C.c_int, "z": C.c_size_t, "u": C.c_uint64, "q": C.c_longlong, "d": C.c_double, "s": C.c_char_p, "p": C.c_void_p,
+        "I": C.c_uint, "l": C.c_long, "v": None}
+groups = dict(abi.PROTOTYPES, **{"not ABI": abi.NOT_ABI})
+bad, seen = [], 0
+for group, sigs in groups.items():
+    for name, sig in sigs.items():
+        if not hasattr(lib, name):
+            assert group == "not ABI", name
+            continue
+        seen += 1
+        fn, (ret, _, params) = getattr(lib, name), sig.partition(":")
+        if fn.restype is not want[ret] or fn.argtypes is None or list(fn.argtypes) != [want[p] for p in params]:
+            bad.append(name)
+print(seen, len(bad), " ".join(bad))
+"""
+
+
+def test_every_function_is_typed_at_load():
+    """In a fresh process that imports nothing but the package, load_library() alone gives every function of the table its restype
+    and argtypes: no call depends on which method or test ran before it."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, "-c", CHILD], cwd=ROOT, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    seen, bad, *names = out.stdout.split()
+    assert int(seen) >= 189 and int(bad) == 0, names
 
 
 def test_struct_layouts_match_header():

@@ -54,7 +54,6 @@ def test_twin_equals_the_numpy_restatement_on_the_rules_edges(cfg, explicit):
         frame = hand_made(orc)["a NaN sample"]
         want, work = host_blank(cfg, frame)[0], frame.copy()
         lib = load_library()
-        lib.mgpu_host_blank.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         assert lib.mgpu_host_blank(int(cfg), None, None, work.ctypes.data_as(C.c_void_p), work.ctypes.data_as(C.c_void_p), None) == 0
         assert work.tobytes() == want.tobytes()
 

@@ -10,7 +10,7 @@ import pytest
 import channelizer_ref as cz
 from mercury_amd import (CHANNELIZER_SYMBOLS, MgpuError, chan_channels, chan_config, host_chan_design, host_chan_process, host_chan_tables,
                          load_library)
-from mercury_amd.physical_layer import ChanConfig, _chan_argtypes
+from mercury_amd.physical_layer import ChanConfig
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,7 +40,7 @@ def test_default_design_meets_its_mask(D):
     # the default of mgpu_host_chan_default_taps is this design
     taps = np.zeros(h.size)
     n = C.c_int()
-    assert _chan_argtypes(load_library()).mgpu_host_chan_default_taps(D, taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
+    assert load_library().mgpu_host_chan_default_taps(D, taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
     assert n.value == h.size and np.array_equal(taps, h)
 
 
@@ -167,7 +167,7 @@ def test_refusals_need_no_device():
 
 def test_create_without_a_device_refuses_bad_arguments_and_reports_the_device():
     """without a context (no device could be opened: tests/test_abi.py) a bad configuration is still MGPU_ERR_ARG, a good one MGPU_ERR_DEVICE"""
-    lib = _chan_argtypes(load_library())
+    lib = load_library()
     out = C.c_void_p()
     chs = chan_channels([(0, 0, 1.0), (3000, 1, 1.0)])
     k, _ = chan_config(4, 2)

@@ -80,11 +80,8 @@ def test_library_exports_what_mercury_demapper_h_declares():
 
 def test_the_csi_carve_fits_every_mode_and_keeps_two_workgroups_in_the_bpsk_modes():
     """the carve the new kernels ask for (two more arrays in the work area) against a compute unit's 160 KB, at either workgroup size"""
-    import ctypes as C
     from mercury_amd import load_library
     lib = load_library()
-    lib.mgpu_frontend_csi_lds_bytes.restype = lib.mgpu_frontend_lds_bytes.restype = C.c_size_t
-    lib.mgpu_frontend_lds_workgroups.argtypes = [C.c_size_t]
     for cfg, explicit in [(c, None) for c in range(17)] + [(8, dict(Dy=5, Nsymb=20))]:
         orc = Oracle(cfg, 50, explicit=dict(explicit or {}))
         G = orc.Nsymb * orc.Nc

@@ -88,7 +88,6 @@ def test_argument_validation():
     from mercury_amd.physical_layer import ExplicitParams
     lib = load_library()
     fn = lib.mgpu_host_ls_estimate
-    fn.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     grid = np.zeros(48 * 50, np.complex128)
     out = np.zeros(48 * 50, np.complex128)
     g, o = grid.ctypes.data, out.ctypes.data
@@ -125,7 +124,6 @@ def test_the_front_end_carve_fits_a_compute_unit_at_either_workgroup_size():
     kernels run under the variable only (tests/test_gpu_frontend_shapes.py)."""
     from mercury_amd import load_library
     fn = load_library().mgpu_frontend_lds_bytes
-    fn.restype, fn.argtypes = C.c_size_t, [C.c_int] * 4
     lds_cu = 160 * 1024
     carve, by_default_1024 = {}, []
     for cfg, x in _geometries():

@@ -1,7 +1,6 @@
 """CPU tests of the front-end's form table (csrc/ls_rect.h, csrc/frontend.hip): which bit sets are forms, that each form has a kernel of
 its own at either workgroup size, that a form's LDS carve is the plain, the CSI or the noise-map one by its CSI and NMAP bits alone - and
 of the yardstick tests/test_gpu_frontend_form_order.py measures the kernels with, against the CPU oracle."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -15,15 +14,7 @@ GEOMETRIES = [(c, None) for c in range(17)] + [(8, dict(Dy=5, Nsymb=20))]       
 
 def _lib():
     from mercury_amd import load_library
-    lib = load_library()
-    for name in ("mgpu_frontend_lds_bytes", "mgpu_frontend_csi_lds_bytes", "mgpu_frontend_nmap_lds_bytes"):
-        getattr(lib, name).restype = C.c_size_t
-        getattr(lib, name).argtypes = [C.c_int] * 4
-    lib.mgpu_frontend_form_lds_bytes.restype = C.c_size_t
-    lib.mgpu_frontend_form_lds_bytes.argtypes = [C.c_int] * 4 + [C.c_uint]
-    lib.mgpu_frontend_form_kernel.restype = C.c_void_p
-    lib.mgpu_frontend_form_kernel.argtypes = [C.c_int, C.c_uint]
-    return lib
+    return load_library()
 
 
 def test_thirteen_bit_sets_are_forms():

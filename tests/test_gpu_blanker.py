@@ -239,7 +239,6 @@ def test_refusals_leave_the_context_as_it_was():
     rx = _rx(8, max_batch=2)
     with pytest.raises(MgpuError):
         rx.blanker_report()                                               # never set: no report
-    rx.lib.mgpu_set_blanker.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     for before in (("off", {}), ("median", dict(threshold=30.0, guard=2, max_share=0.25))):
         rx.set_blanker(before[0], **before[1])
         state = rx.blanker

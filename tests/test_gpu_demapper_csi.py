@@ -4,7 +4,6 @@ Yardsticks: with the demapper off every byte is what it was; with it on the dema
 tests/test_demapper_csi_host.py holds against a numpy restatement on the CPU oracle) bit for bit, the H tap against the oracle's full
 estimate, the reported variance / SNR / mean_H against the plain run; the decode against twin -> the oracle's decoder -> the oracle's tail on
 two-path frames the plain demapper loses; under an estimator ladder against one-rung runs; under diversity against the sum of its parts."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -260,7 +259,6 @@ def test_refusals_leave_the_setting_in_place():
         assert rx.demapper == "maxlog"
         rx.close()
     rx = _rx(8, max_batch=2)
-    rx.lib.mgpu_set_demapper.argtypes = [C.c_void_p, C.c_int]
     for before in ("csi", "maxlog"):
         rx.set_demapper(before)
         assert rx.lib.mgpu_set_demapper(rx.h, 7) == 1                     # MGPU_ERR_ARG

@@ -78,7 +78,6 @@ def test_rung_0_estimate_equals_the_host_twin_bit_for_bit(cfg, explicit):
         assert np.array_equal(out["grid"][f], square["grid"][f])
         want[f, pilots] = host_ls_estimate(cfg, out["grid"][f], 5, 21, explicit=explicit)
     if rx.amp_restore:
-        rx.lib.mgpu_restore_channel_amplitude.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         rx._ck(rx.lib.mgpu_restore_channel_amplitude(rx.h, want.ctypes.data_as(C.c_void_p), 4))
     assert np.array_equal(out["H"][:, pilots], want[:, pilots]), np.abs(out["H"][:, pilots] - want[:, pilots]).max()
     assert not np.array_equal(out["H"], square["H"])

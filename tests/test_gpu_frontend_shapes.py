@@ -40,9 +40,7 @@ def _lds_fe(rx):
 
 
 def _carve(rx, threads):
-    fn = rx.lib.mgpu_frontend_lds_bytes
-    fn.restype, fn.argtypes = C.c_size_t, [C.c_int] * 4
-    return fn(rx.Nsymb * rx.Nc, rx.nPilots, rx.nBits, threads)
+    return rx.lib.mgpu_frontend_lds_bytes(rx.Nsymb * rx.Nc, rx.nPilots, rx.nBits, threads)
 
 
 # ---- A: 1024 threads ---------------------------------------------------------------------------------------------------------------
@@ -131,7 +129,6 @@ def _twin_H(rx, cfg, explicit, grid, w, h, pilots):
         want[f, pilots] = host_ls_estimate(cfg, grid[f], w, h, explicit=explicit)
     est = want[:, pilots]
     if rx.amp_restore:
-        rx.lib.mgpu_restore_channel_amplitude.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         rx._ck(rx.lib.mgpu_restore_channel_amplitude(rx.h, want.ctypes.data_as(C.c_void_p), grid.shape[0]))
     return want[:, pilots], est
 

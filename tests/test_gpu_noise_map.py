@@ -280,7 +280,6 @@ def test_refusals_leave_the_context_as_it_was():
     rx = _rx(8, max_batch=2)
     with pytest.raises(MgpuError):
         rx.noise_map()                                                    # never set: no map
-    rx.lib.mgpu_set_demapper_ex.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     for before in (("csi", None), ("nmap", dict(dead_band=3.0, smooth=2))):
         rx.set_demapper(before[0], **(before[1] or {}))
         state = rx.demapper_ex

@@ -1174,7 +1174,7 @@ def test_entry_points_reject_bad_arguments_without_crashing():
         lambda: lib.mgpu_rx_batch_dev(h, None, 1, None, None, None, None),
         lambda: lib.mgpu_frontend_dev(h, None, 1, None, None, None),
         lambda: lib.mgpu_ldpc_batch_dev(h, None, 1, None, None, None, None, None, None),
-        lambda: lib.mgpu_txgen_dev(h, C.c_uint64(1), C.c_uint64(0), 1, C.c_double(0.1), 7, None, None, None),
+        lambda: lib.mgpu_txgen_dev(h, 1, 0, 1, 0.1, 7, None, None, None),
         lambda: lib.mgpu_passband_to_baseband(h, None, 1, 100, None, 0, None, 10, 1, None),
         lambda: lib.mgpu_passband_to_baseband(h, p(buf), 1, 100, p(buf), 3, None, 10, 1, p(buf)),   # filter id
         lambda: lib.mgpu_time_sync_preamble(h, p(buf), 1, 10, 1, 0, 1, p(st), None),                # window shorter than the preamble
@@ -1192,8 +1192,7 @@ def test_entry_points_reject_bad_arguments_without_crashing():
         rc = call()
         assert rc in (1, 4), (i, rc)
         assert lib.mgpu_last_error(h), i
-    for fn in (lib.mgpu_get_info, lib.mgpu_enable_timing):
-        assert fn(None, None) == 1
+    assert lib.mgpu_get_info(None, None) == 1 and lib.mgpu_enable_timing(None, 0) == 1
     lib.mgpu_destroy(None)                                        # no-op
     out = rx.receive(np.zeros((1, rx.frame_samples), np.complex128))   # the context is still usable afterwards
     assert out["stats"]["iterations_done"][0] == 0

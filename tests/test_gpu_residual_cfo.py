@@ -105,14 +105,6 @@ def test_grid_tap_and_steps_equal_the_host_twin_bit_for_bit(cfg, explicit, threa
 def _stage_chain(rx, grid):
     """the one-stage entry points of mercury_stages.h (the plain stages) on a grid [F, G]: H, eq, variance, llr_demod"""
     lib, h, F = rx.lib, rx.h, grid.shape[0]
-    v, i = C.c_void_p, C.c_int
-    lib.mgpu_channel_estimator.argtypes = [v, v, i, v]
-    lib.mgpu_restore_channel_amplitude.argtypes = [v, v, i]
-    lib.mgpu_channel_equalizer.argtypes = [v, v, v, i, v]
-    lib.mgpu_measure_variance.argtypes = [v, v, i, v]
-    lib.mgpu_deframer.argtypes = [v, v, i, v]
-    lib.mgpu_deinterleaver_c128.argtypes = [v, v, i, i, i, v]
-    lib.mgpu_psk_demod.argtypes = [v, v, i, v, v]
     grid = np.ascontiguousarray(grid, np.complex128)
     H, eq = np.zeros_like(grid), np.zeros_like(grid)
     rx._ck(lib.mgpu_channel_estimator(h, _p(grid), F, _p(H)))
@@ -154,7 +146,6 @@ def test_behind_the_turned_grid_the_stages_are_the_plain_ones(cfg, explicit):
         for f in range(F):
             want[f, pilots] = host_ls_estimate(cfg, grid[f], width, height, explicit=explicit)
         if rx.amp_restore:
-            rx.lib.mgpu_restore_channel_amplitude.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
             rx._ck(rx.lib.mgpu_restore_channel_amplitude(rx.h, _p(want), F))
         return want[:, pilots]
 
@@ -337,7 +328,6 @@ def test_refusals_leave_the_setting_in_place():
         assert rx.cfo == "off"
         rx.close()
     rx = _rx(8, max_batch=2)
-    rx.lib.mgpu_set_cfo.argtypes = [C.c_void_p, C.c_int]
     with pytest.raises(MgpuError):
         rx.cfo_steps(2)                                                   # the mode has never been on
     for before in ("pilots", "off"):

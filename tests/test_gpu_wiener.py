@@ -74,7 +74,6 @@ def test_estimate_equals_the_host_twin_bit_for_bit(cfg, explicit, threads, monke
             if cfo == "off":
                 assert np.array_equal(out["grid"], ls["grid"])
             if demapper == "maxlog" and rx.amp_restore:      # the plain H tap is the estimate after restore_channel_amplitude (the device's own atan / sincos)
-                rx.lib.mgpu_restore_channel_amplitude.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
                 rx._ck(rx.lib.mgpu_restore_channel_amplitude(rx.h, want.ctypes.data_as(C.c_void_p), F))
             assert np.array_equal(out["H"][:, pilots], want[:, pilots]), (cfo, demapper, np.abs(out["H"][:, pilots] - want[:, pilots]).max())
             assert not np.array_equal(out["H"][:, pilots], ls["H"][:, pilots])
@@ -251,7 +250,6 @@ def _set_ex(rx, rungs, size=None):
     arr = (EstimatorRung * max(len(rungs), 1))()
     for i, (kind, window, d) in enumerate(rungs):
         arr[i] = EstimatorRung(kind, LsWindow(*window), WienerDesign(*d))
-    rx.lib.mgpu_set_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
     return rx.lib.mgpu_set_estimator_ladder_ex(rx.h, arr, len(rungs), C.sizeof(EstimatorRung) if size is None else size)
 
 
@@ -311,7 +309,6 @@ def test_refusals_leave_the_context_untouched():
         assert rx.estimator_ladder_ex == set_to
     from mercury_amd.physical_layer import EstimatorRung
     arr, n = (EstimatorRung * 4)(), C.c_int()
-    rx.lib.mgpu_get_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     assert rx.lib.mgpu_get_estimator_ladder_ex(rx.h, arr, C.byref(n), 40) == 1
     with pytest.raises(MgpuError):
         rx.set_estimator_ladder([("wiener", dict(bandwidth=3.0))])

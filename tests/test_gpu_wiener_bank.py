@@ -98,7 +98,6 @@ def test_choice_and_estimate_equal_the_host_twins_bit_for_bit(cfg, explicit, thr
             for f in range(F):
                 want[f, pilots] = host_wiener_estimate(cfg, out["grid"][f], DESIGNS[design[f]], explicit=explicit)
             if demapper == "maxlog" and rx.amp_restore:      # the plain H tap is the estimate after restore_channel_amplitude
-                rx.lib.mgpu_restore_channel_amplitude.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
                 rx._ck(rx.lib.mgpu_restore_channel_amplitude(rx.h, want.ctypes.data_as(C.c_void_p), F))
             assert np.array_equal(out["H"][:, pilots], want[:, pilots]), (cfo, demapper, np.abs(out["H"][:, pilots] - want[:, pilots]).max())
             seen.add(out["llr_ldpc"].tobytes())
@@ -291,7 +290,6 @@ def test_value_on_the_device_is_the_cpu_verdict_frame_by_frame():
 def _set_bank(rx, rung, entries, n=None, size=None):
     from mercury_amd.physical_layer import WienerBankEntry, _bank_array
     arr, count = _bank_array(entries)
-    rx.lib.mgpu_set_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t]
     return rx.lib.mgpu_set_wiener_bank(rx.h, rung, arr, count if n is None else n, C.sizeof(WienerBankEntry) if size is None else size)
 
 
@@ -325,7 +323,6 @@ def test_refusals_leave_the_context_untouched():
     for size in (0, 32, 48):
         assert _set_bank(rx, 2, BANK, size=size) == 1, size
     arr, n = (physical_layer.WienerBankEntry * 4)(), C.c_int()
-    rx.lib.mgpu_get_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     assert rx.lib.mgpu_get_wiener_bank(rx.h, 2, arr, C.byref(n), 32) == 1 and rx.lib.mgpu_get_wiener_bank(rx.h, 0, arr, C.byref(n), 40) == 1
     with pytest.raises(MgpuError):
         rx.wiener_choice(0, 1)                               # rung 0 is an LS rung

@@ -199,7 +199,7 @@ def test_host_select_peak_matches_the_reference_selection():
         ntrials = min(ntrials, size)
         cand = np.array(data.draw(st.lists(st.sampled_from([-1.0, -0.25, 0.0, 0.125, 0.5, 0.5, 0.75, 1.0]), min_size=ncand, max_size=ncand)))
         delay, corr = C.c_int(-7), C.c_double(-7)
-        rc = lib.mgpu_host_select_peak(cand.ctypes.data_as(C.c_void_p), C.c_int(ncand), C.c_int(step), C.c_int(size), C.c_int(loc), C.c_int(ntrials),
+        rc = lib.mgpu_host_select_peak(cand.ctypes.data_as(C.c_void_p), ncand, step, size, loc, ntrials,
                                        C.byref(delay), C.byref(corr))
         assert rc == 0
         assert (delay.value, corr.value) == _reference_selection(cand, step, size, loc, ntrials), (cand, step, size, loc, ntrials)
@@ -215,7 +215,7 @@ def test_host_filter_designs_and_preamble_match_the_oracle():
     orc = oraclelib.Oracle(8)
     taps, n = np.zeros(128), C.c_int(0)
     for which in (0, 1):
-        assert lib.mgpu_host_fir_taps(C.c_int(which), C.c_double(0.0), taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
+        assert lib.mgpu_host_fir_taps(which, 0.0, taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
         assert np.array_equal(taps[: n.value], orc.fir_taps(which))
     f = orc.lib.morc_tx_fir_taps
     f.restype = C.c_int
@@ -223,14 +223,14 @@ def test_host_filter_designs_and_preamble_match_the_oracle():
         for which in (0, 1):
             want = np.zeros(128)
             nw = f(C.c_double(carrier), C.c_int(which), want.ctypes.data_as(C.c_void_p))
-            assert lib.mgpu_host_fir_taps(C.c_int(2 + which), C.c_double(carrier), taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
+            assert lib.mgpu_host_fir_taps(2 + which, carrier, taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
             assert n.value == nw == 97 and np.array_equal(taps[:97], want[:97])
     for cfg in (0, 8, 13, 16):
         o = oraclelib.Oracle(cfg)
         out, ns = np.zeros((8, 50), np.complex128), C.c_int(0)
-        assert lib.mgpu_host_preamble_carriers(C.c_int(cfg), out.ctypes.data_as(C.c_void_p), C.byref(ns)) == 0
+        assert lib.mgpu_host_preamble_carriers(cfg, out.ctypes.data_as(C.c_void_p), C.byref(ns)) == 0
         assert ns.value == o.preamble_nsymb and np.array_equal(out[: ns.value].ravel(), o.preamble())
-    assert lib.mgpu_host_preamble_carriers(C.c_int(55), out.ctypes.data_as(C.c_void_p), C.byref(ns)) != 0
+    assert lib.mgpu_host_preamble_carriers(55, out.ctypes.data_as(C.c_void_p), C.byref(ns)) != 0
 
 
 def test_numa_placement_lookups_without_a_gpu(tmp_path, monkeypatch):
@@ -240,7 +240,6 @@ def test_numa_placement_lookups_without_a_gpu(tmp_path, monkeypatch):
     from mercury_amd import load_library
     from mercury_amd.physical_layer import DeviceProps
     lib = load_library()
-    lib.mgpu_host_numa_node_of_pci.argtypes = [C.c_char_p]
     root = tmp_path / "sys"
     (root / "bus/pci/devices/0000:c1:00.0").mkdir(parents=True)
     (root / "bus/pci/devices/0000:c1:00.0/numa_node").write_text("1\n")
@@ -253,13 +252,13 @@ def test_numa_placement_lookups_without_a_gpu(tmp_path, monkeypatch):
     assert lib.mgpu_host_numa_node_of_pci(b"0000:05:00.0") == -1         # the platform reports no affinity
     assert lib.mgpu_host_numa_node_of_pci(b"0000:ff:00.0") == -1         # no such device
     cpus = (C.c_int * 16)()
-    n = lib.mgpu_host_numa_cpus(C.c_int(1), cpus, C.c_int(16))
+    n = lib.mgpu_host_numa_cpus(1, cpus, 16)
     assert n == 7 and list(cpus[:7]) == [16, 17, 18, 19, 48, 49, 63]
-    assert lib.mgpu_host_numa_cpus(C.c_int(5), cpus, C.c_int(16)) == 0
+    assert lib.mgpu_host_numa_cpus(5, cpus, 16) == 0
     import torch
     if not torch.cuda.is_available():
         p = DeviceProps()
-        assert lib.mgpu_device_props_get(C.c_int(0), C.byref(p)) == 2   # MGPU_ERR_DEVICE
+        assert lib.mgpu_device_props_get(0, C.byref(p)) == 2   # MGPU_ERR_DEVICE
 
 
 def test_bench_dry_run_prints_the_shard_map_without_a_gpu():
@@ -293,7 +292,7 @@ def test_fp32_decoder_placement_keeps_its_gathers_off_each_others_banks():
     lib = load_library()
     out = (C.c_double * 4)()
     for cfg in (0, 1, 2, 3, 4, 8, 13, 16):
-        assert lib.mgpu_host_layout_stats(C.c_int(cfg), out) == 0
+        assert lib.mgpu_host_layout_stats(cfg, out) == 0
         assert 1.0 <= out[0] < 2.0 and 1.0 <= out[1] < 2.2, (cfg, list(out))
         assert 0.6 < out[3] <= 1.0
-    assert lib.mgpu_host_layout_stats(C.c_int(16), out) == 0 and out[1] == 1.0
+    assert lib.mgpu_host_layout_stats(16, out) == 0 and out[1] == 1.0

@@ -177,7 +177,6 @@ def test_refusals():
     for kw in (dict(dead_band=1.0), dict(dead_band=INF), dict(smooth=0), dict(smooth=4)):
         host_demap_nmap(8, g, g + 1, **kw)
     lib = load_library()
-    lib.mgpu_host_demap_nmap.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     prm, llr = DemapperParams(2.0, 1), np.zeros(6000, np.float32)
     h = g + 1
     args = (8, None, g.ctypes.data, h.ctypes.data, C.byref(prm))
@@ -190,8 +189,6 @@ def test_refusals():
 def test_the_noise_map_carve_fits_and_keeps_the_csi_forms_workgroups():
     from mercury_amd import load_library
     lib = load_library()
-    lib.mgpu_frontend_nmap_lds_bytes.restype = lib.mgpu_frontend_csi_lds_bytes.restype = C.c_size_t
-    lib.mgpu_frontend_lds_workgroups.argtypes = [C.c_size_t]
     for cfg, explicit in [(c, None) for c in range(15)] + [(8, dict(Dy=5, Nsymb=20))]:         # every LS mode
         orc = Oracle(cfg, 50, explicit=dict(explicit or {}))
         G = orc.Nsymb * orc.Nc

@@ -60,7 +60,7 @@ def test_mode_table_equals_what_the_compiled_reference_printed():
         want = dict(tab["modes"][str(cfg)], **tab["fixed"])
         orc = oraclelib.Oracle(cfg)
         info = Info()
-        assert lib.mgpu_host_mode_info(C.c_int(cfg), C.c_int(0), C.byref(info)) == 0
+        assert lib.mgpu_host_mode_info(cfg, 0, C.byref(info)) == 0
         for k, v in want.items():
             if k != "E":                                   # the oracle's info carries the table widths, not the edge count
                 assert getattr(orc, k) == v, ("oracle", cfg, k, getattr(orc, k), v)
@@ -68,7 +68,7 @@ def test_mode_table_equals_what_the_compiled_reference_printed():
         assert info.payload_bytes == (want["nBits"] - want["P"] - 16) // 8 == orc.payload_bytes      # telecom_system.cc:332-340
         assert info.frame_samples == want["Nsymb"] * want["Nofdm"]
     bad = Info()
-    assert lib.mgpu_host_mode_info(C.c_int(55), C.c_int(0), C.byref(bad)) != 0
+    assert lib.mgpu_host_mode_info(55, 0, C.byref(bad)) != 0
 
 
 @pytest.mark.parametrize("cfg", list(range(17)))

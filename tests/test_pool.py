@@ -241,7 +241,6 @@ def test_device_props_and_numa_placed_staging():
     assert p["lds_bytes_per_cu"] == 160 * 1024 and p["hbm_bytes"] > 200e9 and 1_000_000 < p["clock_khz"] < 3_000_000
     assert len(p["pci_bus_id"]) >= 7 and p["numa_node"] >= -1
     lib = RxPhy(8, max_batch=1).lib
-    lib.mgpu_host_numa_node_of_pci.argtypes = [C.c_char_p]
     assert lib.mgpu_host_numa_node_of_pci(p["pci_bus_id"].encode()) == p["numa_node"]
     orc = oraclelib.Oracle(8, 50)
     frames = [orc.gen_frame(SEED, 900 + f, oraclelib.noise_amp_for(OPERATING_ESN0[8] + 1.0)) for f in range(6)]

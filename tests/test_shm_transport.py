@@ -28,21 +28,7 @@ def _name():
 @pytest.fixture(scope="module")
 def lib():
     from mercury_amd import load_library
-    l = load_library()
-    l.mgpu_shm_create.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    l.mgpu_shm_connect.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    for f in ("close", "destroy", "clear"):
-        getattr(l, "mgpu_shm_" + f).argtypes = [C.c_void_p]
-        getattr(l, "mgpu_shm_" + f).restype = None
-    for f in ("used", "free", "capacity"):
-        getattr(l, "mgpu_shm_" + f).argtypes = [C.c_void_p]
-        getattr(l, "mgpu_shm_" + f).restype = C.c_size_t
-    l.mgpu_shm_write.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    l.mgpu_shm_read.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-    l.mgpu_shm_read_all.argtypes = [C.c_void_p, C.c_char_p]
-    l.mgpu_shm_read_all.restype = C.c_long
-    l.mgpu_shm_publish_decoded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    return l
+    return load_library()
 
 
 @pytest.fixture(scope="module")

@@ -35,7 +35,6 @@ def _blob():
 
 def _build(K):
     lib = load_library()
-    lib.mgpu_debug_spa_bins.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     dims = (C.c_int * 6)()
     assert lib.mgpu_debug_spa_bins(K, dims, None, None, None) == 0
     S, DM, rounds = dims[0], dims[1], dims[2]

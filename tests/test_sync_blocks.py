@@ -467,8 +467,8 @@ def test_gpu_peak_selection_kernel_matches_the_reference_selection():
         size = np.maximum(size, ntrials).astype(np.int32)
         delay = np.zeros(n, np.int32)
         corr = np.zeros(n, np.float64)
-        rc = rx.lib.mgpu_debug_select_peak(rx.h, vals.ctypes.data_as(C.c_void_p), C.c_int(n), C.c_int(ncmax), ncand.ctypes.data_as(C.c_void_p),
-                                           size.ctypes.data_as(C.c_void_p), loc.ctypes.data_as(C.c_void_p), C.c_int(step), C.c_int(ntrials),
+        rc = rx.lib.mgpu_debug_select_peak(rx.h, vals.ctypes.data_as(C.c_void_p), n, ncmax, ncand.ctypes.data_as(C.c_void_p),
+                                           size.ctypes.data_as(C.c_void_p), loc.ctypes.data_as(C.c_void_p), step, ntrials,
                                            delay.ctypes.data_as(C.c_void_p), corr.ctypes.data_as(C.c_void_p))
         assert rc == 0
         for w in range(n):

@@ -141,12 +141,12 @@ def test_library_pre_equalization_channel_matches_the_reference_fixture(cfg):
     orc = Oracle(cfg)
     for tag, fc in (("pre_eq", CARRIER), ("pre_eq_1650", 1650.0)):
         h = np.zeros(50, np.complex128)
-        assert lib.mgpu_host_pre_equalization_channel(C.c_int(cfg), C.c_double(fc), h.ctypes.data_as(C.c_void_p)) == 0
+        assert lib.mgpu_host_pre_equalization_channel(cfg, fc, h.ctypes.data_as(C.c_void_p)) == 0
         assert MG.digest(h) == want[tag][0], (cfg, tag)
         assert np.array_equal(h, orc.get_pre_equalization_channel(fc))
         assert 1.0 < np.abs(h).min() and np.abs(h).max() < 6.0           # far from "all ones": the band edges need 4.8x
-    assert lib.mgpu_host_pre_equalization_channel(C.c_int(100), C.c_double(CARRIER), h.ctypes.data_as(C.c_void_p)) == 1      # MFSK: none
-    assert lib.mgpu_host_pre_equalization_channel(C.c_int(8), C.c_double(CARRIER), None) == 1
+    assert lib.mgpu_host_pre_equalization_channel(100, CARRIER, h.ctypes.data_as(C.c_void_p)) == 1      # MFSK: none
+    assert lib.mgpu_host_pre_equalization_channel(8, CARRIER, None) == 1
 
 
 @needs_ref

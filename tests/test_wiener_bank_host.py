@@ -233,15 +233,11 @@ def test_the_twins_refusals():
     lib = load_library()
     arr, n = physical_layer._bank_array(B.bank())
     fn = lib.mgpu_host_wiener_select
-    fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert fn(8, None, arr, n, 40, g.ctypes.data, None, None, None, None) == 0          # every output may be NULL
     for size in (0, 32, 48):
         assert fn(8, None, arr, n, size, g.ctypes.data, None, None, None, None) == 1
     assert fn(8, None, None, n, 40, g.ctypes.data, None, None, None, None) == 1 and fn(8, None, arr, n, 40, None, None, None, None, None) == 1
     # the context's entry points refuse a missing context before anything else
-    lib.mgpu_set_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t]
     assert lib.mgpu_set_wiener_bank(None, 0, arr, n, C.sizeof(WienerBankEntry)) == 1
-    lib.mgpu_get_wiener_bank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     assert lib.mgpu_get_wiener_bank(None, 0, arr, None, 40) == 1
-    lib.mgpu_get_wiener_choice.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.mgpu_get_wiener_choice(None, 0, 0, None, None, None, None) == 1

@@ -181,17 +181,13 @@ def test_the_twins_refusals():
     host_wiener_estimate(8, g, W.design(snr_db=40.0)), host_wiener_estimate(8, g, W.design(snr_db=-20.0), explicit=W.DY5)   # the ends are inside
     lib = load_library()
     fn = lib.mgpu_host_wiener_tables
-    fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     n = C.c_int()
     assert fn(8, None, None, 0, 0, C.byref(n), None, None, None) == 0 and n.value == 3
     assert fn(8, None, None, 2, 0, C.byref(n), None, None, None) == 1                  # neither time nor frequency
     assert fn(8, None, None, 0, 3, None, C.byref(n), None, None) == 1 and fn(8, None, None, 1, -1, None, C.byref(n), None, None) == 1
-    lib.mgpu_host_wiener_estimate.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.mgpu_host_wiener_estimate(8, None, None, None, g.ctypes.data) == 1 and lib.mgpu_host_wiener_estimate(8, None, None, g.ctypes.data, None) == 1
     # the setters refuse a missing context before anything else
-    lib.mgpu_set_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
     assert lib.mgpu_set_estimator_ladder_ex(None, None, 0, 48) == 1
-    lib.mgpu_get_estimator_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     assert lib.mgpu_get_estimator_ladder_ex(None, None, None, 48) == 1
 
 
@@ -216,9 +212,6 @@ def test_the_wiener_kernels_carve_is_the_rect_and_csi_forms():
     use, and leave the workgroups per compute unit what they are."""
     from mercury_amd import load_library
     lib = load_library()
-    for fn in (lib.mgpu_frontend_wiener_lds_bytes, lib.mgpu_frontend_csi_lds_bytes, lib.mgpu_frontend_lds_bytes):
-        fn.restype = C.c_size_t
-    lib.mgpu_frontend_lds_workgroups.argtypes = [C.c_size_t]
     for cfg, explicit in [(c, None) for c in range(15)] + [(8, W.DY5)]:
         orc = Oracle(cfg, 50, explicit=dict(explicit or {}))
         G = orc.Nsymb * orc.Nc

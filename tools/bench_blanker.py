@@ -57,7 +57,6 @@ def main():
     res["span_off_ms"] = round(timed(span), 4)
     res["decoded_off"] = int((stats.cpu().numpy().view(STATS_DTYPE)["message_decoded"] != 0).sum())
     if hasattr(rx.lib, "mgpu_set_blanker"):
-        rx.lib.mgpu_blank_dev.argtypes = [__import__("ctypes").c_void_p] * 2 + [__import__("ctypes").c_int] * 2 + [__import__("ctypes").c_void_p] * 3
         alone = lambda: rx._ck(rx.lib.mgpu_blank_dev(rx.h, bb.data_ptr(), F, 0, out.data_ptr(), None, s.cuda_stream))
         res["blanker_ms"] = round(timed(alone), 4)
         traffic = 32.0 * n * F

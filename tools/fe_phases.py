@@ -23,7 +23,7 @@ for rep in range(5):
     cyc = np.zeros(16, np.int64)
     payload = np.zeros((F, pl.payload_stride), np.uint8)
     ts = Taps(**{k: (cyc.ctypes.data if k == "cycles" else None) for k in "grid H eq syms llr_demod llr_ldpc variance agc_gain cycles".split()})
-    pl._ck(pl.lib.mgpu_rx_batch_taps(pl.h, _ptr(bb), C.c_int(F), _ptr(payload), None, C.byref(ts)))
+    pl._ck(pl.lib.mgpu_rx_batch_taps(pl.h, _ptr(bb), F, _ptr(payload), None, C.byref(ts)))
     d = np.diff(cyc[:9]).astype(float)
     if rep:
         acc += d

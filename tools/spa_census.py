@@ -8,7 +8,6 @@ Every branch counts the wavefronts entering it and the lanes they enter it with 
 tanh / atanh calls (one call = one wavefront working one 64-slot bin, or 64 variables of the start-up pass) whose instruction stream
 contains the branch, and the fraction of lanes that needed it: the gap between the two is what the wavefront pays for its lanes' spread
 over fdlibm's cases."""
-import ctypes as C
 import os
 import sys
 
@@ -30,11 +29,11 @@ payload = torch.empty((F, rx.payload_stride), dtype=torch.uint8, device="cuda")
 stats = torch.empty((F, 6), dtype=torch.int32, device="cuda")
 rx.txgen_dev(0x4D455243, 1 << 40, F, float(10.0 ** (-es / 20.0) / np.sqrt(2.0)), bb.data_ptr(), None)
 torch.cuda.synchronize()
-rx.lib.mgpu_debug_spa_census(None, C.c_int(1))
+rx.lib.mgpu_debug_spa_census(None, 1)
 rx.receive_dev(bb.data_ptr(), F, payload.data_ptr(), stats.data_ptr())
 torch.cuda.synchronize()
 buf = np.zeros(64, np.uint64)
-rx.lib.mgpu_debug_spa_census(C.c_void_p(buf.ctypes.data), C.c_int(0))
+rx.lib.mgpu_debug_spa_census(buf.ctypes.data, 0)
 w, l = buf[:32].astype(float), buf[32:].astype(float)
 names = {0: "tanh: calls", 1: "  k == 0 ending", 2: "  k != 0: c, e", 4: "    |x| >= 1, k < 20", 5: "    |x| >= 1, k 20..56", 7: "    |x| < 1, k == 1", 8: "    |x| < 1, k >= 2",
          9: "  1 - 2/(t+2)  (|x| >= 1)", 10: "  -t/(t+2)  (|x| < 1)", 11: "  |x| >= 22 / NaN", 12: "atanh: calls", 13: "  clamp of +-1", 14: "  |x| < 0.5", 15: "  |x| >= 0.5",

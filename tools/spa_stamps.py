@@ -7,7 +7,6 @@
 Lane 0 of every wavefront of eight workgroups spread over the launch stamps s_memrealtime (100 MHz) at the phase boundaries
 (ldpc.hip: SPA_STAMP). Printed: per sampled workgroup its iteration count and the time between boundaries (mean over its
 wavefronts, microseconds), and the sum per phase over the sampled workgroups."""
-import ctypes as C
 import json
 import os
 import sys
@@ -40,7 +39,7 @@ rx.enable_timing(True)
 rx.receive_dev(bb.data_ptr(), F, payload.data_ptr(), stats.data_ptr())
 torch.cuda.synchronize()
 fe_ms, dec_ms, _ = rx.kernel_ms_avg()
-rx.lib.mgpu_debug_spa_stamps(C.c_void_p(buf.ctypes.data), 0)
+rx.lib.mgpu_debug_spa_stamps(buf.ctypes.data, 0)
 buf = buf.reshape(WGS, WAVES, MAXS)
 it_all = stats[:, 0].clamp(max=50).cpu().numpy()
 names = {(1, 2): "load LLRs, zero messages, fetch records", (2, 3): "syndrome pass", (3, 4): "barrier (syndrome)", (4, 5): "check pass", (8, 5): "check pass",
