@@ -13,7 +13,8 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              DIVERSITY_SYMBOLS, DIVERSITY_MAX, host_llr_combine, DEMAPPER_SYMBOLS, DEMAPPERS, host_demap_csi, host_demap_nmap, parse_demapper, NMAP_DEFAULT, DemapperParams,
                              CFO_SYMBOLS, CFO_MODES, host_cfo_pilots, BLANKER_SYMBOLS, BLANKER_MODES, BLANKER_DEFAULT, BLANKER_REPORT_DTYPE, BlankerParams, host_blank, parse_blanker,
                              WIENER_BANK_SYMBOLS, WIENER_BANK_MAX, WienerBankEntry, host_wiener_select, host_wiener_bank_thresholds, wiener_sounding, bank_entries,
-                             CHANNELIZER_SYMBOLS, Channelizer, ChanChannel, ChanConfig, chan_channels, chan_config, host_chan_design, host_chan_tables, host_chan_process)
+                             CHANNELIZER_SYMBOLS, Channelizer, ChanChannel, ChanConfig, chan_channels, chan_config, host_chan_design, host_chan_tables, host_chan_process,
+                             EXCISOR_SYMBOLS, EXCISOR_MODES, EXCISOR_DEFAULT, EXCISOR_REPORT_DTYPE, ExcisorParams, host_excise, parse_excisor)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -24,4 +25,5 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "parse_ladder", "host_wiener_estimate", "host_wiener_tables", "WIENER_DESIGN_DEFAULT", "DIVERSITY_SYMBOLS", "DIVERSITY_MAX", "host_llr_combine", "DEMAPPER_SYMBOLS", "DEMAPPERS", "host_demap_csi", "host_demap_nmap", "parse_demapper", "NMAP_DEFAULT", "DemapperParams",
            "CFO_SYMBOLS", "CFO_MODES", "host_cfo_pilots", "BLANKER_SYMBOLS", "BLANKER_MODES", "BLANKER_DEFAULT", "BLANKER_REPORT_DTYPE", "BlankerParams", "host_blank", "parse_blanker",
            "WIENER_BANK_SYMBOLS", "WIENER_BANK_MAX", "WienerBankEntry", "host_wiener_select", "host_wiener_bank_thresholds", "wiener_sounding", "bank_entries",
-           "CHANNELIZER_SYMBOLS", "Channelizer", "ChanChannel", "ChanConfig", "chan_channels", "chan_config", "host_chan_design", "host_chan_tables", "host_chan_process"]
+           "CHANNELIZER_SYMBOLS", "Channelizer", "ChanChannel", "ChanConfig", "chan_channels", "chan_config", "host_chan_design", "host_chan_tables", "host_chan_process",
+           "EXCISOR_SYMBOLS", "EXCISOR_MODES", "EXCISOR_DEFAULT", "EXCISOR_REPORT_DTYPE", "ExcisorParams", "host_excise", "parse_excisor"]

@@ -1,5 +1,5 @@
 """The C ABI of ``libmercury_gpu.so`` as Python states it: one prototype per ``mgpu_*`` function, grouped by the header under
-``include/`` that declares it, and ``load_library()``, which applies all of them once.
+``include/`` (``PROTOTYPES``) or ``include/ext/`` (``EXTENSIONS``) that declares it, and ``load_library()``, which applies all of them once.
 
 A signature is ``"<return>:<one letter per parameter>"``:
 
@@ -112,6 +112,16 @@ PROTOTYPES = {
     },
 }
 
+# The ABI's extensions: headers under include/ext/, keyed by their path below include/. The set of prototypes under include/*.h is closed
+# (tests/test_abi.py pins it); what the ABI gains later is declared here, typed by load_library() like the rest and checked against its
+# header by tests/test_abi_extensions.py.
+EXTENSIONS = {
+    "ext/mercury_excisor.h": {
+        "mgpu_set_excisor": "i:pipz", "mgpu_get_excisor": "i:pppz", "mgpu_get_excisor_report": "i:piip", "mgpu_excise_dev": "i:ppiidppp",
+        "mgpu_host_excise": "i:pdpipp",
+    },
+}
+
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of
 # their own is I, `unsigned` (a set of MGPU_FE_* form bits). A build that does not export one of them (the census and stamps hooks
 # exist in variant builds only) goes without it.
@@ -133,7 +143,7 @@ def prototype(signature):
 
 def names(*headers):
     """the functions the given headers declare, in the headers' order"""
-    return [name for header in headers for name in PROTOTYPES[header]]
+    return [name for header in headers for name in (PROTOTYPES.get(header) or EXTENSIONS[header])]
 
 
 _lib = None
@@ -155,10 +165,10 @@ def load_library():
         except Exception:  # torch is plumbing, not a dependency of the library itself
             pass
         lib = C.CDLL(LIB_PATH)
-        missing = [name for name in names(*PROTOTYPES) if not hasattr(lib, name)]
+        missing = [name for name in names(*PROTOTYPES, *EXTENSIONS) if not hasattr(lib, name)]
         if missing:
             raise RuntimeError("%s does not export %s, which include/ declares" % (LIB_PATH, ", ".join(missing)))
-        for group in list(PROTOTYPES.values()) + [{n: s for n, s in NOT_ABI.items() if hasattr(lib, n)}]:
+        for group in list(PROTOTYPES.values()) + list(EXTENSIONS.values()) + [{n: s for n, s in NOT_ABI.items() if hasattr(lib, n)}]:
             for name, signature in group.items():
                 fn = getattr(lib, name)
                 fn.restype, fn.argtypes = prototype(signature)

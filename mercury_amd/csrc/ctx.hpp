@@ -21,6 +21,7 @@
 #include "../../include/mercury_demapper.h"
 #include "../../include/mercury_cfo.h"
 #include "../../include/mercury_blanker.h"
+#include "../../include/ext/mercury_excisor.h"
 #include "device_tables.h"
 #include "ls_rect.h"
 #include "tables.hpp"
@@ -230,6 +231,18 @@ struct Blanker {
     DevArray<int> d_report;                         // [max_batch] {marked, blanked} of the last span's frames, by the frame's row
 };
 
+// The context's carrier excisor (include/ext/mercury_excisor.h; excisor.hip). MGPU_EXCISE_WELCH: receive_byte excises every capture window
+// into its workspace (rxloop.hip) before the first filter reads it.
+struct Excisor {
+    int mode = MGPU_EXCISE_OFF;
+    mgpu_excisor_params params = MGPU_EXCISOR_PARAMS_DEFAULT;   // as set; the defaults until then
+    DevArray<double> d_tab, d_win;                  // the rule's tables, [1024][2] and [1024]; made with the first launch
+    DevArray<double> d_spec;                        // [windows of a launch][B][3][64] the band bins' re, im and power per block; grows
+    DevArray<mgpu_excisor_report> d_report;         // [max_batch] of the last receive_byte call's windows, by the window's row
+    DevArray<mgpu_excisor_report> d_scratch;        // [kExciseWindows] the reports of a stand-alone call that wants none
+};
+constexpr int kExciseWindows = 64;                  // windows per launch: the spectrum workspace is that many windows' (18 MB in mode 8)
+
 // The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
 struct SpanIo {
     const double* bb = nullptr;         // input frames
@@ -297,6 +310,7 @@ struct mgpu_ctx {
     Demapper dmp;
     Cfo cfo;
     Blanker blk;
+    Excisor exc;
     int pre_eq_version = 0;         // bumped by mgpu_set_pre_equalization_channel: the transmit state rebuilds its preamble
     struct Pipe { Stream stream; Event done, copied; DevArray<double> d_in; };
     // the blocking host-buffer entry points' chunk pipeline (rx_batch.hip rx_batch_pipelined)
@@ -382,6 +396,10 @@ void launch_zf_snr(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s);
 // rows from io.frame0, input_free (if given) recorded right behind it - and the SpanIo the rest of the span runs on.
 void launch_blanker(mgpu_ctx* c, const double* d_in, int F, size_t in_stride, double* d_out, int* d_report, hipStream_t s);
 SpanIo blanked_span(mgpu_ctx* c, const SpanIo& io, int F, hipStream_t s, hipEvent_t input_free);
+// The carrier excisor (excisor.hip): W dense windows of n samples from d_in into d_out and their reports into d_report (null: none), with the
+// context's parameters, on stream s. release_excised_windows (rxloop.hip) frees receive_byte's workspace of cleaned windows.
+void launch_excisor(mgpu_ctx* c, const double* d_in, int W, int n, double carrier_hz, double* d_out, mgpu_excisor_report* d_report, hipStream_t s);
+void release_excised_windows(mgpu_ctx* c);
 // The grouped span's own steps (combine.hip): the context's compact rows, made on first use; the sums of G groups of member rows (uniform
 // groups of D when d_first is null, else the CSR on the device) into d_out; the groups' decode back to the F rows of io.
 void diversity_workspaces(mgpu_ctx* c);
@@ -510,8 +528,9 @@ inline bool is_device_memory(const void* p) {
 }
 
 // receive_byte for W windows in host or device memory, on the context's stream (rxloop.hip)
+// row0: the row of the call's first window in the arrays kept by window row (the excisor's reports): a piece of a pipelined call
 void receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_receive_config* rcp, mgpu_link_state* state, uint8_t* payload,
-                       mgpu_receive_stats* stats);
+                       mgpu_receive_stats* stats, int row0 = 0);
 // Per-component noise amplitude of the audio-path simulations at esn0_db (selfsim.hip): OFDM from Es/N0 alone, MFSK calibrated from the mean
 // power of the first transmitted frame
 double audio_noise_amplitude(const mgpu::ModeTables& t, double esn0_db, double mean_power);

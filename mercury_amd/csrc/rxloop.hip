@@ -59,6 +59,7 @@ namespace mgpu_detail {
 // per call cost more than the kernels). Rebuilt when a call brings more windows, so its streams and events cover every call.
 struct Workspace {
     DevBuf d_pass, d_bbi, d_frames, d_carrier, d_ia, d_ib, d_ic, d_vals, d_sum, d_cnt, d_freq, d_meanh, d_stats_k, d_payload_k, d_snr_k;
+    DevBuf d_exc;                    // the carrier excisor's cleaned windows, sized like d_pass; made by the first call with the stage on
     size_t vals_per_window;
     PinnedBuf h_vals;                // page-locked landing area for the synchroniser metrics (tens of MB per call)
     // page-locked arena for the small index / result arrays of the control rounds: a copy from or to pageable memory holds the calling
@@ -100,6 +101,7 @@ struct Workspace {
     }
 };
 void Release::operator()(Workspace* p) const { delete p; }
+void release_excised_windows(mgpu_ctx* c) { if (c->rxloop_ws) c->rxloop_ws->d_exc = DevBuf(); }
 
 }  // namespace mgpu_detail
 
@@ -126,6 +128,7 @@ struct Loop {
     std::vector<char> fixed_delay; // MFSK: delay given by the caller, no search and no signal level
     bool need_level = true;        // the whole-window signal level is wanted (not when every window comes with a known delay)
     int ncand0 = 0;                // coarse-search candidates per window
+    int row0 = 0;                  // row of window 0 in the context's arrays kept by window row (the excisor's reports)
 
     static Workspace& workspace(mgpu_ctx* ctx, int W, int buffer_nsymb) {
         const auto& t = ctx->tab;
@@ -394,7 +397,15 @@ struct Loop {
         HIPCK(hipStreamWaitEvent(ws.copy, ws.ev_ready, 0));                         // the previous call is done with d_pass
         ncand0 = buf > L ? (buf - L + kCoarseStep - 1) / kCoarseStep : 0;
         need(size_t(std::max(ncand0, 1)) <= ws.vals_per_window, "search window larger than the workspace");
-        pass = on_device ? passband : ws.d_pass.as<double>();
+        // The carrier excisor (include/ext/mercury_excisor.h), when on: each slice is cleaned into d_exc as soon as it has landed, on the main
+        // stream ahead of the slice's filter, and `pass` points there from the first launch_p2b on; the raw windows are read by the excisor alone.
+        const double* const raw = on_device ? passband : ws.d_pass.as<double>();
+        const bool excise = c->exc.mode == MGPU_EXCISE_WELCH;
+        if (excise) {
+            need(size_t(row0) + size_t(W) <= size_t(c->max_batch), "carrier excisor: the call's windows must lie inside max_batch");
+            ws.d_exc.grow(size_t(c->rxloop_ws_windows) * buf * 8);
+        }
+        pass = excise ? ws.d_exc.as<double>() : raw;
         need_level = !mfsk || !state;
         if (!need_level) for (int w = 0; w < W; ++w) if (state[w].fixed_delay_plus_one <= 0) { need_level = true; break; }
         // Windows already in HBM (OFDM): the signal-level chains (one wavefront per window, 0.6 ms of dependent additions) are launched
@@ -412,6 +423,9 @@ struct Loop {
                 HIPCK(hipEventRecord(ws.slice_ev[k], ws.copy));
                 HIPCK(hipStreamWaitEvent(s, ws.slice_ev[k], 0));
             }
+            if (excise)
+                launch_excisor(c, raw + size_t(off) * buf, n, buf, rc.carrier_hz, ws.d_exc.as<double>() + size_t(off) * buf,
+                               c->exc.d_report + size_t(row0 + off), s);
             launch_p2b(pass, buf, ws.d_carrier.as<double>(), nullptr, 0, buf, 1, c->d_fir[0], int(t.fir_time_sync.size()), ws.d_bbi.as<double>(),
                        ws.d_ia.as<int>() + off, mix_cs, nullptr, 0, n, s);
             // :678 the signal level, on the side stream ahead of the group's coarse search so that the two share the compute units
@@ -791,8 +805,9 @@ int mgpu_measure_signal_only(mgpu_ctx* c, const double* passband, int W, double 
 
 // receive_byte for W windows that lie in host or device memory, on the context's stream: the reference's receive_byte, phase by phase
 void mgpu_detail::receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_receive_config* rcp, mgpu_link_state* state,
-                                    uint8_t* payload, mgpu_receive_stats* stats) {
+                                    uint8_t* payload, mgpu_receive_stats* stats, int row0) {
     Loop lp(c, W, *rcp, mgpu_receive_buffer_nsymb(c), state, payload, stats);
+    lp.row0 = row0;
     lp.pt.mark(lp.s, "device buffers");
     ensure_workspaces(c, WS_FRONTEND | WS_LLR | WS_OUT);
     lp.reset_outputs();
@@ -935,7 +950,7 @@ void receive_byte_any(mgpu_ctx* c, const void* capture, int fmt, int W, const mg
                 if (failed != hipSuccess) break;
             }
             receive_byte_impl(c, c->rb_stage + size_t(off) * buf, n, rcp, state ? state + off : nullptr,
-                              payload + size_t(off) * t.payload_stride, stats + off);
+                              payload + size_t(off) * t.payload_stride, stats + off, off);
         }
     } catch (...) {
         uploader.join();

@@ -476,6 +476,59 @@ def host_blank(cfg, frame, explicit=None, **params):
     return out, {"marked": int(rep["marked"][0]), "blanked": int(rep["blanked"][0])}
 
 
+# ---- the carrier excisor (include/ext/mercury_excisor.h) --------------------------------------------------------------
+EXCISOR_SYMBOLS = names("ext/mercury_excisor.h")
+EXCISOR_MODES = {"off": 0, "welch": 1}
+EXCISOR_DEFAULT = {"threshold": 12.0, "guard": 1, "max_bins": 16}
+EXCISOR_REPORT_DTYPE = np.dtype([("exceeding", "<u8"), ("mask", "<u8"), ("band_lo", "<i4"), ("excised", "<i4"), ("nonfinite", "<i4"),
+                                 ("level", "<f8")], align=True)
+
+
+class ExcisorParams(C.Structure):
+    """mgpu_excisor_params (include/ext/mercury_excisor.h)"""
+    _fields_ = [("threshold", C.c_double), ("guard", C.c_int), ("max_bins", C.c_int)]
+
+
+def _excisor_params(threshold=None, guard=None, max_bins=None):
+    d = EXCISOR_DEFAULT
+    return ExcisorParams(float(d["threshold"] if threshold is None else threshold), int(d["guard"] if guard is None else guard),
+                         int(d["max_bins"] if max_bins is None else max_bins))
+
+
+def parse_excisor(text):
+    """"off", "welch" or "welch:thr=12,guard=1,bins=16" (the tools' --excisor) -> (name, {threshold, guard, max_bins} or None)"""
+    name, _, rest = str(text).partition(":")
+    if name not in EXCISOR_MODES or (rest and name != "welch"):
+        raise ValueError("excisor: off, or welch with :thr=T,guard=G,bins=B")
+    if name != "welch":
+        return name, None
+    prm = dict(EXCISOR_DEFAULT)
+    for item in filter(None, rest.split(",")):
+        key, _, value = item.partition("=")
+        if key == "thr":
+            prm["threshold"] = float(value)
+        elif key == "guard":
+            prm["guard"] = int(value)
+        elif key == "bins":
+            prm["max_bins"] = int(value)
+        else:
+            raise ValueError("excisor welch: thr=T, guard=G and bins=B are what it takes, not %r" % item)
+    return name, prm
+
+
+def host_excise(window, carrier_hz, **params):
+    """mgpu_host_excise, no GPU: one window of real samples at 48 kHz (float64 [n], n >= 1) -> (the cleaned window, its report as a dict of
+    EXCISOR_REPORT_DTYPE's fields). params: threshold, guard, max_bins (the defaults where left out)."""
+    lib = load_library()
+    x = np.ascontiguousarray(window, np.float64).ravel()
+    prm = _excisor_params(**params)
+    out, rep = np.zeros_like(x), np.zeros(1, EXCISOR_REPORT_DTYPE)
+    rc = lib.mgpu_host_excise(C.byref(prm), float(carrier_hz), _ptr(x), int(x.size), _ptr(out), _ptr(rep))
+    if rc != 0:
+        raise MgpuError("mgpu_host_excise failed (%d)" % rc, rc)
+    return out, {name: rep[name][0].item() for name in EXCISOR_REPORT_DTYPE.names}
+
+
 # ---- diversity combining (include/mercury_diversity.h, DESIGN.md §3.8) ------------------------------------------------------------
 DIVERSITY_SYMBOLS = names("mercury_diversity.h")
 DIVERSITY_MAX = 8
@@ -852,6 +905,46 @@ class RxPhy:
         if F:       # (the copies take the context's stream for None; mgpu_blank_dev takes the null stream)
             self._staged([bb], [out, rep], "mgpu_device_malloc failed", lambda d_bb, d_out, d_rep: self._ck(self.lib.mgpu_blank_dev(
                 self.h, d_bb, F, 0 if frame_stride is None else width, d_out, d_rep, self.lib.mgpu_context_stream(self.h))))
+        return out, rep
+
+    # ---- the carrier excisor (include/ext/mercury_excisor.h) ----------------------------------------
+    def set_excisor(self, name, threshold=None, guard=None, max_bins=None):
+        """"off": receive_byte reads the capture windows as they are (the default). "welch": every capture window that enters receive_byte
+        on this context is cleaned of narrowband carriers first (threshold, default 12 band medians; guard, default 1 bin; max_bins, default
+        16). name may also be the tools' form, "welch:thr=12,guard=1,bins=16" (parse_excisor)."""
+        try:
+            name, spec = parse_excisor(name)
+        except ValueError:
+            raise MgpuError("excisor must be one of %s" % sorted(EXCISOR_MODES))
+        spec = spec or EXCISOR_DEFAULT
+        prm = _excisor_params(spec["threshold"] if threshold is None else threshold, spec["guard"] if guard is None else guard,
+                              spec["max_bins"] if max_bins is None else max_bins)
+        self._ck(self.lib.mgpu_set_excisor(self.h, EXCISOR_MODES[name], C.byref(prm), C.sizeof(prm)))
+
+    def excisor(self):
+        """(name, {threshold, guard, max_bins}): the mode and the parameters as last set (the defaults before)"""
+        v, prm = C.c_int(), ExcisorParams()
+        self._ck(self.lib.mgpu_get_excisor(self.h, C.byref(v), C.byref(prm), C.sizeof(prm)))
+        return {n: k for k, n in EXCISOR_MODES.items()}[v.value], {"threshold": prm.threshold, "guard": prm.guard, "max_bins": prm.max_bins}
+
+    def excisor_report(self, first=0, count=None):
+        """EXCISOR_REPORT_DTYPE [count]: the reports of rows first .. first + count - 1 (default: to max_batch) of the last receive_byte call
+        that ran with the excisor on, by the window's row"""
+        count = self.max_batch - int(first) if count is None else int(count)
+        out = np.zeros(count, EXCISOR_REPORT_DTYPE)
+        self._ck(self.lib.mgpu_get_excisor_report(self.h, int(first), count, _ptr(out)))
+        return out
+
+    def excise(self, windows, carrier_hz):
+        """mgpu_excise_dev, the stage on its own: windows float64 [W, n] (any n >= 1) -> (cleaned float64 [W, n], report [W]); with the
+        parameters last set, whether or not the mode is on."""
+        x = np.ascontiguousarray(windows, np.float64)
+        x = x.reshape(1, -1) if x.ndim == 1 else x
+        W, n = x.shape
+        out, rep = np.zeros((W, n), np.float64), np.zeros(W, EXCISOR_REPORT_DTYPE)
+        if W:
+            self._staged([x], [out, rep], "mgpu_device_malloc failed", lambda d_x, d_out, d_rep: self._ck(self.lib.mgpu_excise_dev(
+                self.h, d_x, W, n, float(carrier_hz), d_out, d_rep, self.lib.mgpu_context_stream(self.h))))
         return out, rep
 
     def _staged(self, inputs, outputs, error, run):

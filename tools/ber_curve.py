@@ -20,7 +20,9 @@ and noise, decoded from their summed LLRs (include/mercury_diversity.h); frames_
 demapper; --demapper nmap[:band=2,smooth=1]: those divided by a noise factor per carrier and per symbol measured at the pilots.
 --cfo pilots (any form, with any of the above): every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h).
 --blanker median[:thr=24,guard=4,share=0.125] (any form, with any of the above): every frame through the median-gated impulse blanker ahead of
-the front-end (include/mercury_blanker.h). The self-simulations have no impulse source: this measures what the stage costs a clean channel."""
+the front-end (include/mercury_blanker.h). The self-simulations have no impulse source: this measures what the stage costs a clean channel.
+--excisor welch[:thr=12,guard=1,bins=16] (--passband only): every capture window through the carrier excisor ahead of the synchroniser
+(include/ext/mercury_excisor.h). The self-simulations have no tone source either: what the stage costs a clean channel."""
 import json
 import os
 import sys
@@ -41,6 +43,7 @@ LADDER = []          # --ladder
 DEMAPPER = ["maxlog"]   # --demapper
 CFO = ["off"]           # --cfo
 BLANKER = ["off"]       # --blanker
+EXCISOR = ["off"]       # --excisor (the passband forms)
 
 
 def _rung_names(rx):
@@ -61,6 +64,7 @@ def threshold(cfg, n, channel):
     rx.set_demapper(DEMAPPER[0])
     rx.set_cfo(CFO[0])
     rx.set_blanker(BLANKER[0])
+    rx.set_excisor(EXCISOR[0])
     pts = AWGN_FER01.get(cfg, -20.0) - 3.0 + np.arange(44, dtype=np.float64)
     t0 = time.perf_counter()
     res = rx.passband_test_esn0(pts, n, 1500.0, seed=2024, output_power_watt=1.0, hf_channel=channel)
@@ -69,7 +73,7 @@ def threshold(cfg, n, channel):
     fer = [r["FER"] for r in res]
     first = next((float(pts[i]) for i in range(len(pts) - 2) if max(fer[i: i + 3]) < 0.1), None)
     print(json.dumps({"cfg": cfg, "channel": channel or "awgn", "frames_per_point": n, "fer01_esn0_db": first,
-                      "awgn_reference_db": AWGN_FER01.get(cfg), "demapper": DEMAPPER[0], "cfo": CFO[0], "blanker": BLANKER[0], "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
+                      "awgn_reference_db": AWGN_FER01.get(cfg), "demapper": DEMAPPER[0], "cfo": CFO[0], "blanker": BLANKER[0], "excisor": EXCISOR[0], "fer_by_esn0": [[float(e), f] for e, f in zip(pts, fer)],
                       "seconds": round(time.perf_counter() - t0, 2), **extra}), flush=True)
 
 
@@ -83,6 +87,7 @@ def passband(argv, channel):
     rx.set_demapper(DEMAPPER[0])
     rx.set_cfo(CFO[0])
     rx.set_blanker(BLANKER[0])
+    rx.set_excisor(EXCISOR[0])
     pts = np.arange(31) * 1.0 - 25.0 if cfg >= 100 else np.arange(25) * 0.5 - 10.0
     rx.passband_test_esn0(pts[-1:], min(n, 1024), 1500.0, output_power_watt=1.0, hf_channel=channel)
     t0 = time.perf_counter()
@@ -91,7 +96,7 @@ def passband(argv, channel):
     for r in res:
         print("%.1f;%.3e;%.3e;%d" % (r["esn0_db"], r["BER"], r["FER"], r["crc_ok_frames"]))
     print(json.dumps({"cfg": cfg, "mode": "passband", "channel": channel or "awgn", "points": len(res), "frames_per_point": n, "seconds": dt,
-                      "frames_per_s": len(res) * n / dt, "demapper": DEMAPPER[0], "cfo": CFO[0], "blanker": BLANKER[0], **_ladder_fields(rx)}), file=sys.stderr)
+                      "frames_per_s": len(res) * n / dt, "demapper": DEMAPPER[0], "cfo": CFO[0], "blanker": BLANKER[0], "excisor": EXCISOR[0], **_ladder_fields(rx)}), file=sys.stderr)
 
 
 def baseband(cfg, n, dec=pl.DEC_SPA, channel=None, diversity=None, pts=None, seed=2024, warm=True):
@@ -144,6 +149,13 @@ def main():
         pl.parse_blanker(BLANKER[0])
     except ValueError as e:
         sys.exit("--" + str(e))
+    EXCISOR[0] = _option(argv, "--excisor") or "off"
+    try:
+        pl.parse_excisor(EXCISOR[0])
+    except ValueError as e:
+        sys.exit("--" + str(e))
+    if EXCISOR[0] != "off" and "--passband" not in argv:
+        sys.exit("--excisor: the stage sits ahead of the synchroniser, --passband only")
     for i, a in enumerate(argv):
         if a == "--channel" or a.startswith("--channel="):
             channel = a.split("=", 1)[1] if "=" in a else argv[i + 1]

@@ -35,6 +35,16 @@ def ladder(text, S):
     return pts, np.array([pts[s * len(pts) // S] for s in range(S)])
 
 
+def _excisor(text):
+    """--excisor: the spec as RxPhy.set_excisor takes it, checked by the library's one parser"""
+    from mercury_amd import parse_excisor
+    try:
+        parse_excisor(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _blanker(text):
     """--blanker: the spec as RxPhy.set_blanker takes it, checked by the library's one parser"""
     from mercury_amd import parse_blanker
@@ -189,6 +199,8 @@ def main():
     ap.add_argument("--cfo", default="off", choices=["off", "pilots"], help="pilots: every frame's grid turned back by the phase step its own pilots measure (include/mercury_cfo.h)")
     ap.add_argument("--blanker", default="off", type=_blanker,
                     help="median[:thr=24,guard=4,share=0.125]: every frame through the median-gated impulse blanker ahead of the front-end (include/mercury_blanker.h)")
+    ap.add_argument("--excisor", default="off", type=_excisor,
+                    help="welch[:thr=12,guard=1,bins=16]: every capture window through the carrier excisor ahead of the synchroniser (include/ext/mercury_excisor.h)")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--compare", action="store_true", help="simulator and baseline alternating, --repeats times each")
@@ -206,6 +218,7 @@ def main():
     rx.set_demapper(a.demapper)
     rx.set_cfo(a.cfo)
     rx.set_blanker(a.blanker)
+    rx.set_excisor(a.excisor)
     if a.stream_bench:
         stream_bench(rx, a, info)
         rx.close()
@@ -229,7 +242,7 @@ def main():
                                       "delivered_share": d / max(1, int(c["frames_sent"][m].sum()))}))
             rates[which].append(sim_seconds / wall)
     out = {"cfg": a.cfg, "links": a.links, "channel": a.channel, "gap_hops": a.gap_hops, "simulated_seconds_per_link": hops * p["symbol_period"] / FS,
-           "max_iters": a.max_iters, "ladder": a.ladder, "demapper": a.demapper, "cfo": a.cfo, "blanker": a.blanker}
+           "max_iters": a.max_iters, "ladder": a.ladder, "demapper": a.demapper, "cfo": a.cfo, "blanker": a.blanker, "excisor": a.excisor}
     if a.ladder:
         by, frames = rx.ladder_counters()
         out["decoded_by_rung"], out["ladder_frames"] = [int(v) for v in by], frames
