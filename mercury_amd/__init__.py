@@ -14,7 +14,9 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              CFO_SYMBOLS, CFO_MODES, host_cfo_pilots, BLANKER_SYMBOLS, BLANKER_MODES, BLANKER_DEFAULT, BLANKER_REPORT_DTYPE, BlankerParams, host_blank, parse_blanker,
                              WIENER_BANK_SYMBOLS, WIENER_BANK_MAX, WienerBankEntry, host_wiener_select, host_wiener_bank_thresholds, wiener_sounding, bank_entries,
                              CHANNELIZER_SYMBOLS, Channelizer, ChanChannel, ChanConfig, chan_channels, chan_config, host_chan_design, host_chan_tables, host_chan_process,
-                             EXCISOR_SYMBOLS, EXCISOR_MODES, EXCISOR_DEFAULT, EXCISOR_REPORT_DTYPE, ExcisorParams, host_excise, parse_excisor)
+                             EXCISOR_SYMBOLS, EXCISOR_MODES, EXCISOR_DEFAULT, EXCISOR_REPORT_DTYPE, ExcisorParams, host_excise, parse_excisor,
+                             RESAMPLER_SYMBOLS, Resampler, ResampConfig, ResampStatus, resamp_config, resamp_ratio, host_resamp_design, host_resamp_process,
+                             host_resamp_count)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -26,4 +28,6 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "CFO_SYMBOLS", "CFO_MODES", "host_cfo_pilots", "BLANKER_SYMBOLS", "BLANKER_MODES", "BLANKER_DEFAULT", "BLANKER_REPORT_DTYPE", "BlankerParams", "host_blank", "parse_blanker",
            "WIENER_BANK_SYMBOLS", "WIENER_BANK_MAX", "WienerBankEntry", "host_wiener_select", "host_wiener_bank_thresholds", "wiener_sounding", "bank_entries",
            "CHANNELIZER_SYMBOLS", "Channelizer", "ChanChannel", "ChanConfig", "chan_channels", "chan_config", "host_chan_design", "host_chan_tables", "host_chan_process",
-           "EXCISOR_SYMBOLS", "EXCISOR_MODES", "EXCISOR_DEFAULT", "EXCISOR_REPORT_DTYPE", "ExcisorParams", "host_excise", "parse_excisor"]
+           "EXCISOR_SYMBOLS", "EXCISOR_MODES", "EXCISOR_DEFAULT", "EXCISOR_REPORT_DTYPE", "ExcisorParams", "host_excise", "parse_excisor",
+           "RESAMPLER_SYMBOLS", "Resampler", "ResampConfig", "ResampStatus", "resamp_config", "resamp_ratio", "host_resamp_design", "host_resamp_process",
+           "host_resamp_count"]

@@ -120,6 +120,12 @@ EXTENSIONS = {
         "mgpu_set_excisor": "i:pipz", "mgpu_get_excisor": "i:pppz", "mgpu_get_excisor_report": "i:piip", "mgpu_excise_dev": "i:ppiidppp",
         "mgpu_host_excise": "i:pdpipp",
     },
+    "ext/mercury_resampler.h": {
+        "mgpu_resamp_create": "i:ppp", "mgpu_resamp_destroy": "i:p", "mgpu_resamp_info": "i:pp", "mgpu_resamp_seek": "i:pu",
+        "mgpu_resamp_process": "i:ppiipzp", "mgpu_resamp_process_dev": "i:ppiipzpp", "mgpu_capture_run_resampled": "i:pppiippipp",
+        "mgpu_host_resamp_design": "i:iiiddpp", "mgpu_host_resamp_default_taps": "i:iipp", "mgpu_host_resamp_process": "i:ppiiupzp",
+        "mgpu_host_resamp_count": "i:iiuip",
+    },
 }
 
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of

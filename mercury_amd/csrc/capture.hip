@@ -229,6 +229,8 @@ struct mgpu_capture {
     }
 };
 
+mgpu_ctx* capture_context(mgpu_capture* cap) { return cap->c; }
+
 namespace {
 void check_feed_args(mgpu_capture* k, const void* samples, int fmt, int H) {
     need(samples != nullptr && H > 0, "bad argument (samples must be non-null, H >= 1)");

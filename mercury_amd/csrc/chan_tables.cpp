@@ -52,20 +52,29 @@ double bessel_i0(double x) {
     return sum;
 }
 
-void design(int D, int tp, double cutoff_hz, double atten_db, double* h) {
-    const int T = tp * D + 1, c = (T - 1) / 2;
-    const double R = 48000.0 * D, beta = atten_db > 8.7 ? 0.1102 * (atten_db - 8.7) : 0.0, fc = 2 * cutoff_hz / R;
+}  // namespace
+
+void windowed_sinc(int T, double fc, double atten_db, double gain, double* h) {
+    const int c = (T - 1) / 2;
+    const double beta = atten_db > 8.7 ? 0.1102 * (atten_db - 8.7) : 0.0;
     const double i0b = bessel_i0(beta);
     for (int k = 0; k <= c; ++k) {
         const double t = double(k - c), x = M_PI * fc * t, r = t / c;
         const double ideal = k == c ? fc : fc * std::sin(x) / x;
         h[k] = ideal * bessel_i0(beta * std::sqrt(1 - r * r)) / i0b;
     }
-    // unit DC gain over the mirrored taps, each pair added once so that the two halves are equal to the bit
+    // DC gain `gain` over the mirrored taps, each pair added once so that the two halves are equal to the bit
     double sum = h[c];
     for (int k = 0; k < c; ++k) sum += 2 * h[k];
-    for (int k = 0; k <= c; ++k) h[k] /= sum;
+    for (int k = 0; k <= c; ++k) h[k] = h[k] / sum * gain;
     for (int k = 0; k < c; ++k) h[T - 1 - k] = h[k];
+}
+
+namespace {
+
+void design(int D, int tp, double cutoff_hz, double atten_db, double* h) {
+    const double R = 48000.0 * D;
+    windowed_sinc(tp * D + 1, 2 * cutoff_hz / R, atten_db, 1.0, h);
 }
 
 template <typename Fn> bool with_iq(int format, const void* iq, Fn&& fn) {

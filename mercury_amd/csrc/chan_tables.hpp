@@ -20,6 +20,9 @@ const char* config_error(const mgpu_chan_config* k, bool need_s);
 const char* channel_error(int D, int a_c, const mgpu_chan_channel* ch);
 // the prototype of a checked configuration: its own taps, or the default design
 std::vector<double> prototype(const mgpu_chan_config* k);
+// A windowed-sinc low-pass of T (odd) taps: cutoff fc as a fraction of the Nyquist frequency, Kaiser window with
+// beta = 0.1102 * (atten_db - 8.7), symmetric to the bit, the taps summing to `gain` (the resampler's prototype is made by it too)
+void windowed_sinc(int T, double fc, double atten_db, double gain, double* h);
 // g[k] = h[k] * (cos, sin)(2 pi ((F (k - c)) mod R) / R), interleaved re, im
 void tap_row(const std::vector<double>& h, int D, int a_c, const mgpu_chan_channel& ch, double* g);
 // W[p] = (cos, sin)(2 pi p / 48000), interleaved

@@ -536,3 +536,7 @@ void receive_byte_impl(mgpu_ctx* c, const double* passband, int W, const mgpu_re
 double audio_noise_amplitude(const mgpu::ModeTables& t, double esn0_db, double mean_power);
 
 }  // namespace mgpu_detail
+
+// the context a capture was made on (capture.hip): mgpu_capture_run_resampled holds it against the resampler's
+struct mgpu_capture;
+mgpu_ctx* capture_context(mgpu_capture* cap);

@@ -11,6 +11,7 @@ the span of ``receive_byte`` after synchronisation (telecom_system.cc:1132-1345)
 frames, ``ldpc_decode`` is ``cl_ldpc::decode`` (ldpc.h:90) on a batch of LLR vectors.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -1718,6 +1719,18 @@ class RxCapture:
         nb = self.rx.payload_bytes
         return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
 
+    def run_resampled(self, rs, samples, max_events=None):
+        """run() on audio at the Resampler `rs`'s input rate (mgpu_capture_run_resampled): [S, n_in] samples, any n_in up to rs.max_in ->
+        (the decoded frames as run() lists them, hops numbered from the call's first, and how many hops the call ran)"""
+        ptr, fmt, n_in, _keep = _resamp_input(samples, self.S, 1)
+        m = self.S * (rs.max_out // self.P + 1) if max_events is None else max_events
+        ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
+        pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
+        n, hops = C.c_int(), C.c_int()
+        self.rx._ck(self.lib.mgpu_capture_run_resampled(self.h, rs.h, ptr, fmt, n_in, _ptr(ev), _ptr(pl), m, C.byref(n), C.byref(hops)))
+        nb = self.rx.payload_bytes
+        return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))], hops.value
+
     def state(self, s):
         st = np.zeros((), CAPTURE_STATE_DTYPE)
         self.rx._ck(self.lib.mgpu_capture_get_state(self.h, s, _ptr(st)))
@@ -2042,3 +2055,153 @@ class Channelizer:
             raise MgpuError("out: a contiguous float64 array [S, n_in // D]")
         self.rx._ck(self.lib.mgpu_chan_process(self.h, ptr, fmt, n_in, _ptr(out)))
         return out
+
+
+# ---- rational resampler (include/ext/mercury_resampler.h) ----------------------------------------------------------------
+RESAMPLER_SYMBOLS = names("ext/mercury_resampler.h")
+
+
+class ResampConfig(C.Structure):        # mgpu_resamp_config
+    _fields_ = [("struct_size", C.c_int), ("fin", C.c_int), ("fout", C.c_int), ("S", C.c_int), ("components", C.c_int), ("tp", C.c_int),
+                ("ntaps", C.c_int), ("taps", C.c_void_p), ("max_in", C.c_int)]
+
+
+class ResampStatus(C.Structure):        # mgpu_resamp_status
+    _fields_ = [("L", C.c_int), ("M", C.c_int), ("tp", C.c_int), ("S", C.c_int), ("components", C.c_int), ("max_in", C.c_int),
+                ("max_out", C.c_int), ("tile", C.c_int), ("fifo", C.c_int), ("pad", C.c_int), ("delay", C.c_double), ("m0", C.c_uint64),
+                ("n0", C.c_uint64)]
+
+
+def resamp_ratio(fin, fout):
+    """(L, M) = (fout / g, fin / g), g = gcd(fin, fout)"""
+    g = math.gcd(int(fin), int(fout))
+    return int(fout) // g, int(fin) // g
+
+
+def resamp_config(fin, fout=48000, S=1, components=1, tp=None, taps=None, max_in=None):
+    """-> (mgpu_resamp_config, keep-alive of its taps). With taps and no tp, tp is (len(taps) - 1) / L."""
+    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
+    if h is not None and tp is None and fin > 0 and fout > 0:
+        tp = (h.size - 1) // resamp_ratio(fin, fout)[0]
+    k = ResampConfig(C.sizeof(ResampConfig), int(fin), int(fout), int(S), int(components), int(tp or 0), 0 if h is None else h.size,
+                     None if h is None else h.ctypes.data, int(max_in or 0))
+    return k, h
+
+
+def _resamp_input(x, S, components):
+    """-> (pointer, format, samples per stream, keep-alive): [S, n_in] real samples in a capture format (components 1) or IQ as
+    Channelizer.process takes it (components 2); a numpy array or a torch tensor (read in place)"""
+    if components == 2:
+        ptr, fmt, n, keep = _iq(x)
+    elif hasattr(x, "data_ptr"):
+        import torch
+        fmt = {torch.float64: 0, torch.int32: 1, torch.int16: 2, torch.float32: 3}.get(x.dtype)
+        if fmt is None or not x.is_contiguous():
+            raise MgpuError("device samples: a contiguous float64 / int32 / int16 / float32 tensor")
+        ptr, n, keep = x.data_ptr(), x.numel(), x
+    else:
+        keep = np.ascontiguousarray(x)
+        ptr, fmt, n = _ptr(keep), _sample_format(keep.dtype), keep.size
+    if n % S:
+        raise MgpuError("samples must be [S, n_in] with S = %d" % S)
+    return ptr, fmt, n // S, keep
+
+
+def host_resamp_design(fin, fout=48000, tp=None, cutoff_hz=None, atten_db=None):
+    """the prototype low-pass (mgpu_host_resamp_design; None: the default of each parameter): float64 [tp * L + 1]"""
+    lib = load_library()
+    n = C.c_int()
+    args = (int(fin), int(fout), int(tp or 0), float(cutoff_hz or 0.0), float(atten_db or 0.0))
+    if lib.mgpu_host_resamp_design(*args, None, C.byref(n)) != 0:
+        raise MgpuError("mgpu_host_resamp_design: bad argument", 1)
+    taps = np.zeros(n.value)
+    if lib.mgpu_host_resamp_design(*args, _ptr(taps), C.byref(n)) != 0:
+        raise MgpuError("mgpu_host_resamp_design: bad argument", 1)
+    return taps
+
+
+def host_resamp_count(fin, fout, m0, n_in):
+    """outputs of a call of n_in inputs at input position m0 (mgpu_host_resamp_count)"""
+    n = C.c_int()
+    if load_library().mgpu_host_resamp_count(int(fin), int(fout), int(m0), int(n_in), C.byref(n)) != 0:
+        raise MgpuError("mgpu_host_resamp_count: bad argument", 1)
+    return n.value
+
+
+def _resamp_result(out, n, components):
+    out = out[:, : n * components]
+    return out if components == 1 else np.ascontiguousarray(out).view(np.complex128)
+
+
+def host_resamp_process(fin, fout, x, position=0, components=1, tp=None, taps=None, S=None, struct_size=None, fmt=None):
+    """the twin (mgpu_host_resamp_process): a fresh resampler seeked to input position `position` and fed x ([S, n_in], or [n_in] for
+    one stream) whole -> float64 [S, n_out] (components 1) or complex128 [S, n_out] (components 2)"""
+    if S is None:
+        a = x if hasattr(x, "shape") else np.asarray(x)
+        lead = a.ndim - (1 if components == 2 and a.dtype == np.int16 else 0)
+        S = a.shape[0] if lead >= 2 else 1
+    k, _keep = resamp_config(fin, fout, S, components, tp, taps)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    ptr, f, n_in, _x = _resamp_input(x, S, 2 if components == 2 else 1)
+    try:
+        cap = host_resamp_count(fin, fout, position, n_in)
+    except MgpuError:
+        cap = 0
+    out = np.zeros((S, max(cap, 1) * max(int(components), 1)))
+    n = C.c_int()
+    if load_library().mgpu_host_resamp_process(C.byref(k), ptr, f if fmt is None else fmt, n_in, int(position), _ptr(out), max(cap, 1),
+                                               C.byref(n)) != 0:
+        raise MgpuError("mgpu_host_resamp_process: bad argument", 1)
+    return _resamp_result(out, n.value, components)
+
+
+class Resampler:
+    """S streams at fin into S streams at fout on an RxPhy context (include/ext/mercury_resampler.h). process() takes [S, n_in] samples,
+    real in a capture format (components 1) or IQ as Channelizer.process takes it (components 2), numpy or a torch tensor on the
+    context's device, cut anywhere, and returns float64 / complex128 [S, n_out]."""
+
+    def __init__(self, rx, fin, fout=48000, S=1, components=1, tp=None, taps=None, max_in=None):
+        self.rx, self.lib, self.fin, self.fout, self.S, self.components = rx, rx.lib, int(fin), int(fout), int(S), int(components)
+        self.config, self._taps = resamp_config(fin, fout, S, components, tp, taps, max_in)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_resamp_create(rx.h, C.byref(self.config), C.byref(self.h)))
+        st = self.info()
+        self.L, self.M, self.tp, self.max_in, self.max_out, self.tile, self.delay = st.L, st.M, st.tp, st.max_in, st.max_out, st.tile, st.delay
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.mgpu_resamp_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        st = ResampStatus()
+        self.rx._ck(self.lib.mgpu_resamp_info(self.h, C.byref(st)))
+        return st
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_resamp_seek(self.h, int(position)))
+
+    def process(self, x, out=None, stream=None, fmt=None):
+        """out None: a new numpy array [S, n_out] (blocking call). out a float64 torch tensor [S, stride * components] on the device, with
+        x one too: mgpu_resamp_process_dev, asynchronous on `stream` (None: the context's stream); returns n_out."""
+        ptr, f, n_in, _keep = _resamp_input(x, self.S, self.components)
+        f = f if fmt is None else fmt
+        n = C.c_int()
+        if out is not None and hasattr(out, "data_ptr"):
+            import torch
+            if not hasattr(x, "data_ptr") or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() % (self.S * self.components):
+                raise MgpuError("device output: device input and a contiguous float64 tensor [S, stride * components]")
+            stride = out.numel() // (self.S * self.components)
+            self.rx._ck(self.lib.mgpu_resamp_process_dev(self.h, ptr, f, n_in, out.data_ptr(), stride, C.byref(n), stream))
+            return n.value
+        stride = max(self.max_out, 1)
+        host = np.zeros((self.S, stride * self.components))
+        self.rx._ck(self.lib.mgpu_resamp_process(self.h, ptr, f, n_in, _ptr(host), stride, C.byref(n)))
+        return _resamp_result(host, n.value, self.components)
