@@ -3,14 +3,12 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
-#include <mutex>
 
 #include "ctx.hpp"
 
 namespace {
 constexpr int kBlankThreads = 256;      // four wavefronts per frame
 constexpr int kBlankOwn = 8;            // samples of a block a lane owns at most: blocks (symbol lengths) up to 512 samples
-constexpr unsigned long long kKeyMask = 0x7fffffffffffffffull;
 }  // namespace
 
 // One workgroup per frame. LDS, in 64-bit words, W = ceil(n / 64): the exceed flags of the frame, one bit per sample, with a zero word on
@@ -150,14 +148,8 @@ extern "C" {
 
 int mgpu_set_blanker(mgpu_ctx* c, int mode, const mgpu_blanker_params* params, size_t params_size) {
     if (!c) return MGPU_ERR_ARG;
-    if (params_size != sizeof(mgpu_blanker_params)) {
-        c->err = "blanker: params_size is not this library's sizeof(mgpu_blanker_params)";
-        return MGPU_ERR_ARG;
-    }
-    if (mode != MGPU_BLANK_OFF && mode != MGPU_BLANK_MEDIAN) {
-        c->err = "blanker mode must be MGPU_BLANK_OFF or MGPU_BLANK_MEDIAN";
-        return MGPU_ERR_ARG;
-    }
+    if (params_size != sizeof(mgpu_blanker_params)) return refuse(c, MGPU_ERR_ARG, "blanker: params_size is not this library's sizeof(mgpu_blanker_params)");
+    if (mode != MGPU_BLANK_OFF && mode != MGPU_BLANK_MEDIAN) return refuse(c, MGPU_ERR_ARG, "blanker mode must be MGPU_BLANK_OFF or MGPU_BLANK_MEDIAN");
     Blanker& B = c->blk;
     return guard(c, [&] {
         const mgpu_blanker_params q = params ? *params : mgpu_blanker_params MGPU_BLANKER_PARAMS_DEFAULT;
@@ -193,10 +185,8 @@ int mgpu_get_blanker(mgpu_ctx* c, int* mode, mgpu_blanker_params* params, size_t
 int mgpu_get_blanker_report(mgpu_ctx* c, int first, int count, mgpu_blanker_report* report) {
     if (!c || first < 0 || count < 0 || (count && !report)) return MGPU_ERR_ARG;
     return guard(c, [&] {
-        need(size_t(first) + size_t(count) <= size_t(c->max_batch), "bad argument (first + count must be <= max_batch)");
-        need(bool(c->blk.d_report.p), "MGPU_BLANK_MEDIAN was never set on this context");
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (count) HIPCK(hipMemcpy(report, c->blk.d_report + size_t(first) * 2, size_t(count) * sizeof(mgpu_blanker_report), hipMemcpyDeviceToHost));
+        static_assert(sizeof(mgpu_blanker_report) == 2 * sizeof(int), "a report is two ints");
+        read_rows(c, c->blk.d_report, 2, first, count, report, "MGPU_BLANK_MEDIAN was never set on this context");
     });
 }
 
@@ -212,43 +202,18 @@ int mgpu_blank_dev(mgpu_ctx* c, const void* d_in, int F, int frame_stride, void*
 
 }  // extern "C"
 
-// What the twin needs of a mode's tables, kept for the last geometry asked for (a sweep over frames builds the tables once).
+// What the twin needs of a mode's tables (geometry_cache.hpp)
 namespace {
-struct BlankGeometry {
-    int cfg = -1;
-    mgpu::ExplicitParams xp;
-    int n = 0, L = 0;
-};
-std::mutex blank_mutex;
-std::shared_ptr<const BlankGeometry> blank_last;
-
-std::shared_ptr<const BlankGeometry> blank_geometry(int cfg, const mgpu::ExplicitParams& xp) {
-    std::lock_guard<std::mutex> lock(blank_mutex);
-    const auto same = [&](const BlankGeometry& g) {
-        return g.cfg == cfg && g.xp.pilot_boost == xp.pilot_boost && g.xp.ls_window == xp.ls_window && g.xp.pilot_seed == xp.pilot_seed &&
-               g.xp.scrambler_seed == xp.scrambler_seed && g.xp.preamble_seed == xp.preamble_seed && g.xp.Nsymb == xp.Nsymb && g.xp.Dy == xp.Dy;
-    };
-    if (blank_last && same(*blank_last)) return blank_last;
-    const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
-    auto g = std::make_shared<BlankGeometry>();
-    g->cfg = cfg; g->xp = xp;
-    g->n = t.frame_samples; g->L = t.Nofdm;
-    blank_last = g;
-    return g;
-}
+struct BlankGeometry { int n = 0, L = 0; };
 }  // namespace
 
 extern "C" int mgpu_host_blank(int cfg, const mgpu_explicit_params* p, const mgpu_blanker_params* params, const double* in, double* out,
                                mgpu_blanker_report* report) {
     if (!in || !out) return MGPU_ERR_ARG;
-    mgpu::ExplicitParams xp;
-    std::string err;
-    int rc = MGPU_OK;
-    if (!explicit_params_from(p, xp, err, &rc)) return rc;
-    try {
+    return host_twin(p, [&](const mgpu::ExplicitParams& xp) -> int {
         const mgpu_blanker_params q = params ? *params : mgpu_blanker_params MGPU_BLANKER_PARAMS_DEFAULT;
         blanker_check(q);
-        const std::shared_ptr<const BlankGeometry> geometry = blank_geometry(cfg, xp);
+        const auto geometry = cached_geometry<BlankGeometry>(cfg, xp, [](const mgpu::ModeTables& t) { return BlankGeometry{t.frame_samples, t.Nofdm}; });
         const int n = geometry->n, L = geometry->L;
         if (n <= 0 || L <= 0) return MGPU_ERR_ARG;
         const size_t frame = size_t(n), block = size_t(L);
@@ -284,5 +249,5 @@ extern "C" int mgpu_host_blank(int cfg, const mgpu_explicit_params* p, const mgp
         }
         if (report) { report->marked = marked; report->blanked = blank ? marked : 0; }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }

@@ -23,11 +23,6 @@ namespace {
 
 constexpr int kDefaultHops = 16;
 
-// the capture thread's widening (audioio.c:893-936), as mgpu_widen_capture_kernel does it
-double widen(const void* samples, int fmt, size_t i) {
-    return with_samples(fmt, samples, [i](auto* in, double divisor) { return divisor == 1.0 ? double(in[i]) : double(in[i]) / divisor; });
-}
-
 bool good_geometry(const mgpu_capture_geometry* g) {
     return g && g->symbol_period > 1 && g->nsymb > 0 && g->preamble_nsymb >= 0 && g->buffer_nsymb > 1;
 }
@@ -97,8 +92,7 @@ __global__ __launch_bounds__(256) void mgpu_capture_feed_kernel(const T* __restr
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         size_t p = pos0 + size_t(i);
         if (p >= cap) p -= cap;
-        const double x = double(src[i]);
-        dst[p] = divisor == 1.0 ? x : x / divisor;
+        dst[p] = mgpu_fmt::widen(src[i], divisor);
     }
 }
 
@@ -147,7 +141,7 @@ struct mgpu_capture {
 
     // hops [h0, h0 + n) of the call's samples ([S][H * P], host or device) into every ring; the counters are the caller's
     void feed_chunk(const void* samples, int fmt, int H, int h0, int n, bool dev) {
-        const size_t sb = sample_bytes(fmt), row = size_t(n) * P, in_row = size_t(H) * P;
+        const size_t sb = mgpu_fmt::element_bytes(mgpu_fmt::element(1, fmt)), row = size_t(n) * P, in_row = size_t(H) * P;
         const char* src = static_cast<const char*>(samples) + size_t(h0) * P * sb;
         size_t stride = in_row;
         if (!dev) {
@@ -173,7 +167,7 @@ struct mgpu_capture {
             const dim3 grid(gx, unsigned(ns)), block(256);
             double* r = ring + size_t(k0) * cap;
             const char* in = src + size_t(k0) * stride * sb;
-            with_samples(fmt, in, [&](auto* typed, double divisor) {
+            mgpu_fmt::with_elements(mgpu_fmt::element(1, fmt), in, [&](auto* typed, double divisor) {
                 using T = std::remove_cv_t<std::remove_pointer_t<decltype(typed)>>;
                 hipLaunchKernelGGL(mgpu_capture_feed_kernel<T>, grid, block, 0, s(), typed, stride, int(row), divisor, r, cap, pos0);
             });
@@ -230,11 +224,12 @@ struct mgpu_capture {
 };
 
 mgpu_ctx* capture_context(mgpu_capture* cap) { return cap->c; }
+int capture_streams(mgpu_capture* cap) { return cap->S; }
 
 namespace {
 void check_feed_args(mgpu_capture* k, const void* samples, int fmt, int H) {
     need(samples != nullptr && H > 0, "bad argument (samples must be non-null, H >= 1)");
-    need(known_format(fmt), "unknown sample format");
+    need(mgpu_fmt::element(1, fmt) != mgpu_fmt::kNone, "unknown sample format");
     need(size_t(H) * k->P < (size_t(1) << 31) / 2, "H too large");
 }
 }  // namespace
@@ -355,14 +350,8 @@ int mgpu_capture_get_state(mgpu_capture* k, int s, mgpu_capture_state* st) {
 
 int mgpu_capture_set_state(mgpu_capture* k, int s, const mgpu_capture_state* st) {
     if (!k || !st || s < 0 || s >= k->S) return MGPU_ERR_ARG;
-    if (st->n_under < 0 || (st->data_ready != 0 && st->data_ready != 1)) {
-        k->c->err = "mgpu_capture_set_state: n_under must be >= 0, data_ready 0 or 1";
-        return MGPU_ERR_ARG;
-    }
-    if (!k->g.mfsk && st->link.fixed_delay_plus_one > 0) {
-        k->c->err = "mgpu_capture_set_state: fixed_delay_plus_one: MFSK modes only";
-        return MGPU_ERR_ARG;
-    }
+    if (st->n_under < 0 || (st->data_ready != 0 && st->data_ready != 1)) return refuse(k->c, MGPU_ERR_ARG, "mgpu_capture_set_state: n_under must be >= 0, data_ready 0 or 1");
+    if (!k->g.mfsk && st->link.fixed_delay_plus_one > 0) return refuse(k->c, MGPU_ERR_ARG, "mgpu_capture_set_state: fixed_delay_plus_one: MFSK modes only");
     k->st[s] = *st;
     return MGPU_OK;
 }
@@ -383,11 +372,12 @@ int mgpu_host_capture_init_state(const mgpu_capture_geometry* g, mgpu_capture_st
 }
 
 int mgpu_host_capture_prep(const mgpu_capture_geometry* g, double* window, const void* samples, int fmt, mgpu_capture_state* st) {
-    if (!good_geometry(g) || !window || !samples || !st || !known_format(fmt)) return MGPU_ERR_ARG;
+    const int e = mgpu_fmt::element(1, fmt);
+    if (!good_geometry(g) || !window || !samples || !st || e == mgpu_fmt::kNone) return MGPU_ERR_ARG;
     const int P = g->symbol_period, sp = g->buffer_nsymb * P, loc = sp - P - 1;   // audioio.c:1035
     if (st->data_ready == 1) st->n_under++;                                      // :1047-1048
     for (int j = 0; j < sp - P; ++j) window[j] = window[j + P];                   // shift_left, misc.cc:26-32
-    for (int i = 0; i < P; ++i) window[loc + i] = widen(samples, fmt, size_t(i)); // :1051
+    for (int i = 0; i < P; ++i) window[loc + i] = mgpu_fmt::widen_at(e, samples, size_t(i)); // :1051
     st->frames_to_read--;                                                        // :1053-1055
     if (st->frames_to_read < 0) st->frames_to_read = 0;
     st->data_ready = 1;

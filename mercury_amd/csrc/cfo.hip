@@ -2,7 +2,6 @@
 // launch.hip's front-end core, the stage's tables, and the host twin. The kernel is frontend.hip's; the twin's arithmetic is cfo_rule.cpp's.
 #include <cstring>
 #include <memory>
-#include <mutex>
 
 #include "ctx.hpp"
 
@@ -41,15 +40,11 @@ extern "C" {
 
 int mgpu_set_cfo(mgpu_ctx* c, int cfo) {
     if (!c) return MGPU_ERR_ARG;
-    if (cfo != MGPU_CFO_OFF && cfo != MGPU_CFO_PILOTS) {
-        c->err = "cfo must be MGPU_CFO_OFF or MGPU_CFO_PILOTS";
-        return MGPU_ERR_ARG;
-    }
+    if (cfo != MGPU_CFO_OFF && cfo != MGPU_CFO_PILOTS) return refuse(c, MGPU_ERR_ARG, "cfo must be MGPU_CFO_OFF or MGPU_CFO_PILOTS");
     const auto& t = c->tab;
     if (t.mfsk_M > 0) {
         if (cfo == MGPU_CFO_OFF) return MGPU_OK;
-        c->err = "the pilot-aided carrier-offset correction needs an OFDM mode (the MFSK modes have no pilots)";
-        return MGPU_ERR_UNSUPPORTED;
+        return refuse(c, MGPU_ERR_UNSUPPORTED, "the pilot-aided carrier-offset correction needs an OFDM mode (the MFSK modes have no pilots)");
     }
     Cfo& K = c->cfo;
     return guard(c, [&] {
@@ -83,55 +78,34 @@ int mgpu_get_cfo_steps(mgpu_ctx* c, int F, double* step) {
     if (!c || !step || F < 0) return MGPU_ERR_ARG;
     return guard(c, [&] {
         need(F <= c->max_batch, "bad argument (F must be <= max_batch)");
-        need(bool(c->cfo.d_step.p), "no span has run with MGPU_CFO_PILOTS on this context");
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (F) HIPCK(hipMemcpy(step, c->cfo.d_step.p, size_t(F) * sizeof(double), hipMemcpyDeviceToHost));
+        read_rows(c, c->cfo.d_step, 1, 0, F, step, "no span has run with MGPU_CFO_PILOTS on this context");
     });
 }
 
-// What the twin needs of a mode's tables, kept for the last geometry asked for (a sweep over frames builds the tables once).
+// What the twin needs of a mode's tables (geometry_cache.hpp)
 namespace {
 struct CfoGeometry {
-    int cfg = -1;
-    mgpu::ExplicitParams xp;
     bool ofdm = false;
     int Ns = 0, Nc = 0, Dy = 0;
     CfoChains chains;
 };
-std::mutex cfo_mutex;
-std::shared_ptr<const CfoGeometry> cfo_last;
-
-std::shared_ptr<const CfoGeometry> cfo_geometry(int cfg, const mgpu::ExplicitParams& xp) {
-    std::lock_guard<std::mutex> lock(cfo_mutex);
-    const auto same = [&](const CfoGeometry& g) {
-        return g.cfg == cfg && g.xp.pilot_boost == xp.pilot_boost && g.xp.ls_window == xp.ls_window && g.xp.pilot_seed == xp.pilot_seed &&
-               g.xp.scrambler_seed == xp.scrambler_seed && g.xp.preamble_seed == xp.preamble_seed && g.xp.Nsymb == xp.Nsymb && g.xp.Dy == xp.Dy;
-    };
-    if (cfo_last && same(*cfo_last)) return cfo_last;
-    const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
-    auto g = std::make_shared<CfoGeometry>();
-    g->cfg = cfg; g->xp = xp;
-    g->ofdm = t.mfsk_M == 0;
-    g->Ns = t.Nsymb; g->Nc = t.Nc; g->Dy = t.xp.Dy;
-    if (g->ofdm) g->chains = cfo_chains(t);
-    cfo_last = g;
-    return g;
-}
 }  // namespace
 
 int mgpu_host_cfo_pilots(int cfg, const mgpu_explicit_params* p, const double* grid_in, double* grid_out, double* step_out) {
     if (!grid_in || !grid_out) return MGPU_ERR_ARG;
-    mgpu::ExplicitParams xp;
-    std::string err;
-    int rc = MGPU_OK;
-    if (!explicit_params_from(p, xp, err, &rc)) return rc;
-    try {
-        const std::shared_ptr<const CfoGeometry> geometry = cfo_geometry(cfg, xp);
+    return host_twin(p, [&](const mgpu::ExplicitParams& xp) -> int {
+        const auto geometry = cached_geometry<CfoGeometry>(cfg, xp, [](const mgpu::ModeTables& t) {
+            CfoGeometry g;
+            g.ofdm = t.mfsk_M == 0;
+            g.Ns = t.Nsymb; g.Nc = t.Nc; g.Dy = t.xp.Dy;
+            if (g.ofdm) g.chains = cfo_chains(t);
+            return g;
+        });
         const CfoGeometry& g = *geometry;
         if (!g.ofdm) return MGPU_ERR_UNSUPPORTED;
         mgpu_internal_cfo_rule(grid_in, grid_out, g.Ns, g.Nc, g.Dy, g.chains.sign.data(), g.chains.pair.data(), g.chains.first.data(), step_out);
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "chan_tables.hpp"
+#include "sample_formats.h"
 #include "../../include/mercury_gpu.h"
 
 namespace mgpu_chan_detail {
@@ -77,15 +78,6 @@ void design(int D, int tp, double cutoff_hz, double atten_db, double* h) {
     windowed_sinc(tp * D + 1, 2 * cutoff_hz / R, atten_db, 1.0, h);
 }
 
-template <typename Fn> bool with_iq(int format, const void* iq, Fn&& fn) {
-    switch (format) {
-        case MGPU_IQ_CS16: fn(static_cast<const int16_t*>(iq), 32768.0); return true;
-        case MGPU_IQ_CF32: fn(static_cast<const float*>(iq), 1.0); return true;
-        case MGPU_IQ_CF64: fn(static_cast<const double*>(iq), 1.0); return true;
-    }
-    return false;
-}
-
 }  // namespace
 
 std::vector<double> prototype(const mgpu_chan_config* k) {
@@ -145,12 +137,10 @@ int mgpu_host_chan_process(const mgpu_chan_config* k, const mgpu_chan_channel* c
     for (int s = 0; s < k->S; ++s)
         if (channel_error(k->D, k->audio_centre_hz, channels + s)) return MGPU_ERR_ARG;
     const int D = k->D;
-    if (n_in < D || n_in % D || position > (1ULL << 62)) return MGPU_ERR_ARG;
+    const int e = mgpu_fmt::element(2, format);
+    if (n_in < D || n_in % D || position > (1ULL << 62) || e == mgpu_fmt::kNone) return MGPU_ERR_ARG;
     std::vector<double> x(size_t(n_in) * 2);
-    if (!with_iq(format, iq, [&](auto* p, double div) {
-            for (size_t i = 0; i < x.size(); ++i) x[i] = double(p[i]) / div;
-        }))
-        return MGPU_ERR_ARG;
+    for (size_t i = 0; i < x.size(); ++i) x[i] = mgpu_fmt::widen_at(e, iq, i);
     const std::vector<double> h = prototype(k);
     const int T = int(h.size()), L = (T - 1) / D / 2, N = n_in / D;
     std::vector<double> g(size_t(T) * 2), W(size_t(MGPU_CHAN_PHASOR_LEN) * 2);

@@ -51,7 +51,8 @@ inline int outputs_per_lane(int D) { return D <= 32 ? 2 : 1; }
 
 }  // namespace
 
-// cur[i] = prev[prev_keep + i] for i < hist (zeros when prev is null), else the chunk's sample i - hist widened
+// cur[i] = prev[prev_keep + i] for i < hist (zeros when prev is null), else the chunk's sample i - hist widened. The formats and the divisor
+// are sample_formats.h's, restated: with that header's dispatch in this loop the call measured slower (profiles/stage_plumbing.md)
 template <typename T>
 __device__ inline double2 chan_widen(const T* iq, size_t i, double div) { return make_double2(double(iq[2 * i]) / div, double(iq[2 * i + 1]) / div); }
 
@@ -175,7 +176,7 @@ struct mgpu_chan {
     DevArray<double2> d_line[2];                  // [T - 1 + max_out * D]
     DevArray<double2> d_g, d_W;                   // [S][T], [48000]
     DevArray<ChanRow> d_rows;                     // [S]
-    DevArray<char> d_stage;                       // host input's landing area (grown)
+    DevArray<char> d_stage;                       // host input's landing area (ctx.hpp staged_on_device)
     DevArray<double> d_out;                       // [S][max_out]: process()'s output and the wideband capture's workspace (made on first use)
 
     void upload_row(int s, hipStream_t st) {
@@ -189,7 +190,7 @@ struct mgpu_chan {
 
     void check_n_in(const void* iq, int format, int n_in, const void* out) const {
         need(iq && out, "null pointer");
-        need(format == MGPU_IQ_CS16 || format == MGPU_IQ_CF32 || format == MGPU_IQ_CF64, "unknown IQ format");
+        need(mgpu_fmt::element(2, format) != mgpu_fmt::kNone, "unknown IQ format");
         need(n_in >= D && n_in % D == 0, "n_in must be a positive multiple of D");
         need(n_in / D <= max_out, "more outputs than max_out in one call");
         need(pos + uint64_t(n_in / D) <= (1ULL << 62), "position beyond 2^62");
@@ -223,14 +224,8 @@ struct mgpu_chan {
         pos += uint64_t(N);
     }
 
-    // the input where the kernels can read it: device memory as it is, host memory through the staging buffer
     const void* on_device(const void* iq, int format, int n_in, hipStream_t st) {
-        if (is_device_memory(iq)) return iq;
-        const size_t bytes = size_t(n_in) * (format == MGPU_IQ_CS16 ? 4 : format == MGPU_IQ_CF32 ? 8 : 16);
-        HIPCK(hipStreamSynchronize(st));          // the last call's reads of the staging buffer
-        d_stage.grow(bytes);
-        HIPCK(hipMemcpyAsync(d_stage.p, iq, bytes, hipMemcpyHostToDevice, st));
-        return d_stage.p;
+        return staged_on_device(d_stage, iq, size_t(n_in) * 2 * mgpu_fmt::element_bytes(mgpu_fmt::element(2, format)), st);
     }
     void need_out() {
         if (!d_out.p) d_out = DevArray<double>(size_t(S) * max_out * 8);
@@ -339,13 +334,8 @@ int mgpu_capture_run_wideband(mgpu_capture* cap, mgpu_chan* k, const void* iq, i
                               uint8_t* payloads, int max_events, int* n_events) {
     if (!cap || !k) return MGPU_ERR_ARG;
     mgpu_capture_geometry g{};
-    mgpu_capture_state probe;
-    // the capture has exactly S captures: S - 1 is one of them, S is not
-    if (mgpu_capture_geometry_get(cap, &g) != MGPU_OK || mgpu_capture_get_state(cap, k->S - 1, &probe) != MGPU_OK ||
-        mgpu_capture_get_state(cap, k->S, &probe) == MGPU_OK) {
-        k->c->err = "mgpu_capture_run_wideband: the capture and the channeliser must have the same S";
-        return MGPU_ERR_ARG;
-    }
+    if (mgpu_capture_geometry_get(cap, &g) != MGPU_OK || capture_streams(cap) != k->S)
+        return refuse(k->c, MGPU_ERR_ARG, "mgpu_capture_run_wideband: the capture and the channeliser must have the same S");
     const int rc = guard(k->c, [&] {
         need(H > 0 && (long long)H * g.symbol_period <= k->max_out, "H * P must be 1..max_out");
         need(n_events != nullptr && max_events >= 0 && (max_events == 0 || events), "bad argument (n_events, events)");

@@ -137,10 +137,9 @@ static int div_refusal(mgpu_ctx* c, int F, int D) {
         } catch (const std::invalid_argument& e) { c->err = e.what(); throw; }
     });
     if (rc != MGPU_OK) return rc;
-    if (c->lad.n > 1) {
-        c->err = "diversity combining with an estimator ladder of more than one rung is not supported (a retry would have to re-estimate whole groups)";
-        return MGPU_ERR_UNSUPPORTED;
-    }
+    if (c->lad.n > 1)
+        return refuse(c, MGPU_ERR_UNSUPPORTED,
+                      "diversity combining with an estimator ladder of more than one rung is not supported (a retry would have to re-estimate whole groups)");
     return MGPU_OK;
 }
 
@@ -196,7 +195,7 @@ int mgpu_llr_combine_dev(mgpu_ctx* c, const void* d_llr, int F, int D, const int
 
 int mgpu_rx_batch_div_dev(mgpu_ctx* c, const void* d_bb, int F, int D, void* d_payload, void* d_stats, void* d_llr_opt, void* stream) {
     if (!c) return MGPU_ERR_ARG;
-    if (!d_bb || !d_payload || !d_stats) { c->err = "bad argument"; return MGPU_ERR_ARG; }
+    if (!d_bb || !d_payload || !d_stats) return refuse(c, MGPU_ERR_ARG, "bad argument");
     if (const int rc = div_refusal(c, F, D)) return rc;
     return guard(c, [&] {
         if (F == 0) return;
@@ -212,7 +211,7 @@ int mgpu_rx_batch_div_dev(mgpu_ctx* c, const void* d_bb, int F, int D, void* d_p
 
 int mgpu_rx_batch_div(mgpu_ctx* c, const double* bb, int F, int D, uint8_t* payload, mgpu_frame_stats* stats, float* llr_opt) {
     if (!c) return MGPU_ERR_ARG;
-    if (!bb) { c->err = "bad argument"; return MGPU_ERR_ARG; }
+    if (!bb) return refuse(c, MGPU_ERR_ARG, "bad argument");
     if (const int rc = div_refusal(c, F, D)) return rc;
     return guard(c, [&] {
         if (F == 0) return;
@@ -236,7 +235,7 @@ int mgpu_rx_batch_div(mgpu_ctx* c, const double* bb, int F, int D, uint8_t* payl
 int mgpu_baseband_test_esn0_div(mgpu_ctx* c, const double* esn0_db, int npoints, long long groups_per_point, uint64_t seed, uint64_t frame0,
                                 const mgpu_hf_channel* ch, int D, mgpu_error_rate* out) {
     if (!c) return MGPU_ERR_ARG;
-    if (!ch) { c->err = "no channel"; return MGPU_ERR_ARG; }
+    if (!ch) return refuse(c, MGPU_ERR_ARG, "no channel");
     if (const int rc = div_refusal(c, 0, D)) return rc;
     return guard(c, [&] {
         hf_check(ch);

@@ -23,11 +23,10 @@
 #include "../../include/mercury_blanker.h"
 #include "../../include/ext/mercury_excisor.h"
 #include "device_tables.h"
+#include "geometry_cache.hpp"
 #include "ls_rect.h"
+#include "sample_formats.h"
 #include "tables.hpp"
-
-extern "C" const unsigned char mgpu_ldpc_blob[];
-extern "C" const unsigned long mgpu_ldpc_blob_size;
 
 extern "C" size_t mgpu_frontend_lds_bytes(int G, int nPilots, int nBits, int threads);
 extern "C" size_t mgpu_frontend_csi_lds_bytes(int G, int nPilots, int nBits, int threads);
@@ -242,6 +241,8 @@ struct Excisor {
     DevArray<mgpu_excisor_report> d_scratch;        // [kExciseWindows] the reports of a stand-alone call that wants none
 };
 constexpr int kExciseWindows = 64;                  // windows per launch: the spectrum workspace is that many windows' (18 MB in mode 8)
+// a double's bits without its sign: the blanker's and the excisor's medians are selected on these keys (non-negative doubles order as them)
+constexpr unsigned long long kKeyMask = 0x7fffffffffffffffull;
 
 // The arrays one fused-span call (launch_span) reads and writes; row 0 = the call's first frame.
 struct SpanIo {
@@ -487,6 +488,31 @@ inline int guard(mgpu_ctx* c, const std::function<void()>& fn) {
     }
 }
 inline void need(bool ok, const char* what) { if (!ok) throw std::invalid_argument(what); }
+// a refusal before any device work: the message where mgpu_last_error finds it, and the code to return
+inline int refuse(mgpu_ctx* c, int code, const char* message) { c->err = message; return code; }
+// Rows [first, first + count) of an array the last call left on the device, one row of `per_row` elements per frame (or window) of
+// max_batch, into dst (null: not wanted). never_set: the message where the array was never made.
+template <typename T>
+void read_rows(mgpu_ctx* c, const DevArray<T>& d, size_t per_row, int first, int count, void* dst, const char* never_set) {
+    need(size_t(first) + size_t(count) <= size_t(c->max_batch), "bad argument (first + count must be <= max_batch)");
+    need(bool(d.p), never_set);
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (count && dst) HIPCK(hipMemcpy(dst, d + size_t(first) * per_row, size_t(count) * per_row * sizeof(T), hipMemcpyDeviceToHost));
+}
+// A host twin has no context to leave a message in: fn's own code, or MGPU_ERR_ARG where it throws
+template <typename Fn> int host_try(Fn&& fn) {
+    try {
+        return fn();
+    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+}
+// ... on a mode's geometry: fn(the caller's explicit parameters as the table builder takes them), or the code they are refused with
+template <typename Fn> int host_twin(const mgpu_explicit_params* p, Fn&& fn) {
+    mgpu::ExplicitParams xp;
+    std::string err;
+    int rc = MGPU_OK;
+    if (!explicit_params_from(p, xp, err, &rc)) return rc;
+    return host_try([&] { return fn(xp); });
+}
 // mfsk.cc:82-95, :120-126, :149-155; the universal ACK/BREAK patterns use M = 16, one stream centred in Nc = 50
 // (telecom_system.cc:3006), hop step 7, 8 tones sent twice.
 constexpr int kAckTones[8] = {4, 7, 5, 12, 13, 1, 9, 15}, kBreakTones[8] = {6, 14, 2, 3, 10, 8, 11, 15};
@@ -506,25 +532,20 @@ struct Io {
     void down(void* h, DevBuf& d, size_t bytes) { back(h, d, bytes); HIPCK(hipStreamSynchronize(s)); }      // the last output: waited for
 };
 
-// The audio device's sample formats (mercury_rxloop.h MGPU_SAMPLES_*; audioio.c:893-936): fn(samples as their element type, the divisor that
-// widens one to the double receive_byte works on)
-inline bool known_format(int fmt) {
-    return fmt == MGPU_SAMPLES_F64 || fmt == MGPU_SAMPLES_INT32 || fmt == MGPU_SAMPLES_INT16 || fmt == MGPU_SAMPLES_F32;
-}
-inline size_t sample_bytes(int fmt) { return fmt == MGPU_SAMPLES_F64 ? 8 : fmt == MGPU_SAMPLES_INT16 ? 2 : 4; }
-template <typename Fn> auto with_samples(int fmt, const void* samples, Fn&& fn) {
-    switch (fmt) {
-        case MGPU_SAMPLES_INT32: return fn(static_cast<const int32_t*>(samples), 2147483647.0);
-        case MGPU_SAMPLES_INT16: return fn(static_cast<const int16_t*>(samples), 32768.0);
-        case MGPU_SAMPLES_F32: return fn(static_cast<const float*>(samples), 1.0);
-        default: return fn(static_cast<const double*>(samples), 1.0);
-    }
-}
 inline bool is_device_memory(const void* p) {
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice) return true;
     (void)hipGetLastError();
     return false;
+}
+// A caller's input where the kernels can read it: device memory as it is, host memory through the staging buffer (grown), once the
+// stream's earlier reads of that buffer are over
+inline const void* staged_on_device(DevArray<char>& stage, const void* in, size_t bytes, hipStream_t st) {
+    if (is_device_memory(in)) return in;
+    HIPCK(hipStreamSynchronize(st));
+    stage.grow(bytes);
+    HIPCK(hipMemcpyAsync(stage.p, in, bytes, hipMemcpyHostToDevice, st));
+    return stage.p;
 }
 
 // receive_byte for W windows in host or device memory, on the context's stream (rxloop.hip)
@@ -537,6 +558,7 @@ double audio_noise_amplitude(const mgpu::ModeTables& t, double esn0_db, double m
 
 }  // namespace mgpu_detail
 
-// the context a capture was made on (capture.hip): mgpu_capture_run_resampled holds it against the resampler's
+// the context a capture was made on and the number of its captures (capture.hip): what the feeders in front of one hold against their own
 struct mgpu_capture;
 mgpu_ctx* capture_context(mgpu_capture* cap);
+int capture_streams(mgpu_capture* cap);

@@ -5,7 +5,6 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <mutex>
 
 #include "ctx.hpp"
 #include "fe_math.h"
@@ -42,41 +41,22 @@ extern "C" {
 
 int mgpu_set_demapper_ex(mgpu_ctx* c, int demapper, const mgpu_demapper_params* params, size_t params_size) {
     if (!c) return MGPU_ERR_ARG;
-    if (params_size != sizeof(mgpu_demapper_params)) {
-        c->err = "demapper: params_size is not this library's sizeof(mgpu_demapper_params)";
-        return MGPU_ERR_ARG;
-    }
-    if (demapper != MGPU_DEMAP_MAXLOG && demapper != MGPU_DEMAP_CSI && demapper != MGPU_DEMAP_NMAP) {
-        c->err = "demapper must be MGPU_DEMAP_MAXLOG, MGPU_DEMAP_CSI or MGPU_DEMAP_NMAP";
-        return MGPU_ERR_ARG;
-    }
+    if (params_size != sizeof(mgpu_demapper_params)) return refuse(c, MGPU_ERR_ARG, "demapper: params_size is not this library's sizeof(mgpu_demapper_params)");
+    if (demapper != MGPU_DEMAP_MAXLOG && demapper != MGPU_DEMAP_CSI && demapper != MGPU_DEMAP_NMAP) return refuse(c, MGPU_ERR_ARG, "demapper must be MGPU_DEMAP_MAXLOG, MGPU_DEMAP_CSI or MGPU_DEMAP_NMAP");
     const mgpu_demapper_params q = params ? *params : kNmapDefaults;
-    if (demapper == MGPU_DEMAP_NMAP && !nmap_params_ok(q)) {
-        c->err = "the noise-map demapper takes a dead_band >= 1 (+Inf included) and a smooth of 0..4";
-        return MGPU_ERR_ARG;
-    }
+    if (demapper == MGPU_DEMAP_NMAP && !nmap_params_ok(q)) return refuse(c, MGPU_ERR_ARG, "the noise-map demapper takes a dead_band >= 1 (+Inf included) and a smooth of 0..4");
     const auto& t = c->tab;
     if (t.mfsk_M > 0) {
         if (demapper == MGPU_DEMAP_MAXLOG) return MGPU_OK;
-        c->err = "the channel-aware demapper needs an OFDM mode (the MFSK modes have no channel estimate)";
-        return MGPU_ERR_UNSUPPORTED;
+        return refuse(c, MGPU_ERR_UNSUPPORTED, "the channel-aware demapper needs an OFDM mode (the MFSK modes have no channel estimate)");
     }
-    if (demapper == MGPU_DEMAP_NMAP && t.estimator != MGPU_EST_LS) {
-        c->err = "the noise-map demapper needs the LS estimator (a zero-forcing estimate passes through its own pilots: no residuals)";
-        return MGPU_ERR_UNSUPPORTED;
-    }
+    if (demapper == MGPU_DEMAP_NMAP && t.estimator != MGPU_EST_LS) return refuse(c, MGPU_ERR_UNSUPPORTED, "the noise-map demapper needs the LS estimator (a zero-forcing estimate passes through its own pilots: no residuals)");
     Demapper& D = c->dmp;
     const size_t lds = mgpu_frontend_csi_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads);
     const size_t nmap_lds = mgpu_frontend_nmap_lds_bytes(c->dev.G, c->dev.nPilots, c->dev.nBits, c->fe_threads);
-    if ((demapper == MGPU_DEMAP_CSI && lds > size_t(160) * 1024) || (demapper == MGPU_DEMAP_NMAP && nmap_lds > size_t(160) * 1024)) {
-        c->err = "frame geometry too large for the LDS carve of the channel-aware demapper's front-end";
-        return MGPU_ERR_TABLES;
-    }
+    if ((demapper == MGPU_DEMAP_CSI && lds > size_t(160) * 1024) || (demapper == MGPU_DEMAP_NMAP && nmap_lds > size_t(160) * 1024)) return refuse(c, MGPU_ERR_TABLES, "frame geometry too large for the LDS carve of the channel-aware demapper's front-end");
     // the noise map's sums and factors have a lane each: carriers on one wavefront, symbols on the five behind it (frontend.hip)
-    if (demapper == MGPU_DEMAP_NMAP && (t.Nc != 50 || t.Nsymb > 255 || c->dev.G != t.Nsymb * t.Nc)) {
-        c->err = "frame geometry outside the noise map's lane assignment";
-        return MGPU_ERR_TABLES;
-    }
+    if (demapper == MGPU_DEMAP_NMAP && (t.Nc != 50 || t.Nsymb > 255 || c->dev.G != t.Nsymb * t.Nc)) return refuse(c, MGPU_ERR_TABLES, "frame geometry outside the noise map's lane assignment");
     return guard(c, [&] {
         HIPCK(hipStreamSynchronize(c->stream));
         if (demapper != MGPU_DEMAP_MAXLOG && !D.d_sym_data) {
@@ -140,22 +120,16 @@ int mgpu_get_demapper_ex(mgpu_ctx* c, int* demapper, mgpu_demapper_params* param
 int mgpu_get_noise_map(mgpu_ctx* c, int first, int count, double* fc, double* fs) {
     if (!c || first < 0 || count < 0) return MGPU_ERR_ARG;
     return guard(c, [&] {
-        need(size_t(first) + size_t(count) <= size_t(c->max_batch), "bad argument (first + count must be <= max_batch)");
-        need(bool(c->dmp.d_fc.p), "MGPU_DEMAP_NMAP was never set on this context");
-        HIPCK(hipStreamSynchronize(c->stream));
-        const size_t Nc = size_t(c->tab.Nc), Ns = size_t(c->tab.Nsymb);
-        if (count && fc) HIPCK(hipMemcpy(fc, c->dmp.d_fc + size_t(first) * Nc, size_t(count) * Nc * sizeof(double), hipMemcpyDeviceToHost));
-        if (count && fs) HIPCK(hipMemcpy(fs, c->dmp.d_fs + size_t(first) * Ns, size_t(count) * Ns * sizeof(double), hipMemcpyDeviceToHost));
+        read_rows(c, c->dmp.d_fc, size_t(c->tab.Nc), first, count, fc, "MGPU_DEMAP_NMAP was never set on this context");
+        read_rows(c, c->dmp.d_fs, size_t(c->tab.Nsymb), first, count, fs, "MGPU_DEMAP_NMAP was never set on this context");
     });
 }
 
 }  // extern "C"
 
-// What the twin needs of a mode's tables, kept for the last geometry asked for (a sweep over frames builds the tables once).
+// What the twins need of a mode's tables (geometry_cache.hpp)
 namespace {
 struct DemapGeometry {
-    int cfg = -1;
-    mgpu::ExplicitParams xp;
     bool ofdm = false;
     int G = 0, nData = 0, nPilots = 0, M = 0, bps = 0, Nsymb = 0, Nc = 0;
     bool ls = false;                                // the LS estimator (the noise map refuses zero-forcing)
@@ -165,28 +139,19 @@ struct DemapGeometry {
     std::vector<double> pilot_val;
     std::vector<mgpu::Cplx> constellation;
 };
-std::mutex demap_mutex;
-std::shared_ptr<const DemapGeometry> demap_last;
 
 std::shared_ptr<const DemapGeometry> demap_geometry(int cfg, const mgpu::ExplicitParams& xp) {
-    std::lock_guard<std::mutex> lock(demap_mutex);
-    const auto same = [&](const DemapGeometry& g) {
-        return g.cfg == cfg && g.xp.pilot_boost == xp.pilot_boost && g.xp.ls_window == xp.ls_window && g.xp.pilot_seed == xp.pilot_seed &&
-               g.xp.scrambler_seed == xp.scrambler_seed && g.xp.preamble_seed == xp.preamble_seed && g.xp.Nsymb == xp.Nsymb && g.xp.Dy == xp.Dy;
-    };
-    if (demap_last && same(*demap_last)) return demap_last;
-    const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
-    auto g = std::make_shared<DemapGeometry>();
-    g->cfg = cfg; g->xp = xp;
-    g->ofdm = t.mfsk_M == 0;
-    g->G = t.Nsymb * t.Nc; g->nData = t.nData; g->nPilots = t.nPilots; g->M = t.M; g->bps = t.bps;
-    g->pilot_boost = t.pilot_boost;
-    g->Nsymb = t.Nsymb; g->Nc = t.Nc; g->ls = t.estimator == MGPU_EST_LS;
-    if (g->ofdm) g->nmap = nmap_lists(t.cell_type, t.Nsymb, t.Nc);
-    for (int i = 0; i < g->G && g->ofdm; ++i) if (t.cell_type[i]) g->pilot_cell.push_back(uint16_t(i));
-    g->sym_src = t.sym_src; g->pilot_val = t.pilot_val; g->constellation = t.constellation;
-    demap_last = g;
-    return g;
+    return cached_geometry<DemapGeometry>(cfg, xp, [](const mgpu::ModeTables& t) {
+        DemapGeometry g;
+        g.ofdm = t.mfsk_M == 0;
+        g.G = t.Nsymb * t.Nc; g.nData = t.nData; g.nPilots = t.nPilots; g.M = t.M; g.bps = t.bps;
+        g.pilot_boost = t.pilot_boost;
+        g.Nsymb = t.Nsymb; g.Nc = t.Nc; g.ls = t.estimator == MGPU_EST_LS;
+        if (g.ofdm) g.nmap = nmap_lists(t.cell_type, t.Nsymb, t.Nc);
+        for (int i = 0; i < g.G && g.ofdm; ++i) if (t.cell_type[i]) g.pilot_cell.push_back(uint16_t(i));
+        g.sym_src = t.sym_src; g.pilot_val = t.pilot_val; g.constellation = t.constellation;
+        return g;
+    });
 }
 }  // namespace
 
@@ -194,11 +159,7 @@ extern "C" {
 
 int mgpu_host_demap_csi(int cfg, const mgpu_explicit_params* p, const double* grid, const double* H, float* llr, double* sigma2_out) {
     if (!grid || !H || !llr) return MGPU_ERR_ARG;
-    mgpu::ExplicitParams xp;
-    std::string err;
-    int rc = MGPU_OK;
-    if (!explicit_params_from(p, xp, err, &rc)) return rc;
-    try {
+    return host_twin(p, [&](const mgpu::ExplicitParams& xp) -> int {
         const std::shared_ptr<const DemapGeometry> geometry = demap_geometry(cfg, xp);
         const DemapGeometry& t = *geometry;
         if (!t.ofdm) return MGPU_ERR_UNSUPPORTED;
@@ -234,7 +195,7 @@ int mgpu_host_demap_csi(int cfg, const mgpu_explicit_params* p, const double* gr
             for (int b = 0; b < bps; ++b) llr[k * bps + (bps - 1 - b)] = scale * (d1[b] - d0[b]);
         }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
 
 int mgpu_host_demap_nmap(int cfg, const mgpu_explicit_params* p, const double* grid, const double* H, const mgpu_demapper_params* params, size_t params_size,
@@ -242,11 +203,7 @@ int mgpu_host_demap_nmap(int cfg, const mgpu_explicit_params* p, const double* g
     if (!grid || !H || !llr || params_size != sizeof(mgpu_demapper_params)) return MGPU_ERR_ARG;
     const mgpu_demapper_params prm = params ? *params : kNmapDefaults;
     if (!nmap_params_ok(prm)) return MGPU_ERR_ARG;
-    mgpu::ExplicitParams xp;
-    std::string err;
-    int rc = MGPU_OK;
-    if (!explicit_params_from(p, xp, err, &rc)) return rc;
-    try {
+    return host_twin(p, [&](const mgpu::ExplicitParams& xp) -> int {
         const std::shared_ptr<const DemapGeometry> geometry = demap_geometry(cfg, xp);
         const DemapGeometry& t = *geometry;
         if (!t.ofdm || !t.ls) return MGPU_ERR_UNSUPPORTED;
@@ -317,7 +274,7 @@ int mgpu_host_demap_nmap(int cfg, const mgpu_explicit_params* p, const double* g
             for (int bb = 0; bb < bps; ++bb) llr[k * bps + (bps - 1 - bb)] = scale * (d1[bb] - d0[bb]);
         }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
 
 }  // extern "C"

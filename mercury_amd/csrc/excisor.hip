@@ -10,7 +10,7 @@
 namespace {
 constexpr int kN = 1024, kH = 512, kBand = 64;
 constexpr int kSpecRow = 3 * kBand;     // doubles of one block's record in the spectrum workspace: re[64], im[64], P[64]
-constexpr unsigned long long kKeyMask = 0x7fffffffffffffffull, kKeyInf = 0x7ff0000000000000ull;
+constexpr unsigned long long kKeyInf = 0x7ff0000000000000ull;      // the smallest key (ctx.hpp kKeyMask) that is no finite power
 
 // The rule's tables, made once per process by the host's libm; the device reads copies of these very values.
 struct ExciseTables {
@@ -279,14 +279,8 @@ extern "C" {
 
 int mgpu_set_excisor(mgpu_ctx* c, int mode, const mgpu_excisor_params* params, size_t params_size) {
     if (!c) return MGPU_ERR_ARG;
-    if (params_size != sizeof(mgpu_excisor_params)) {
-        c->err = "excisor: params_size is not this library's sizeof(mgpu_excisor_params)";
-        return MGPU_ERR_ARG;
-    }
-    if (mode != MGPU_EXCISE_OFF && mode != MGPU_EXCISE_WELCH) {
-        c->err = "excisor mode must be MGPU_EXCISE_OFF or MGPU_EXCISE_WELCH";
-        return MGPU_ERR_ARG;
-    }
+    if (params_size != sizeof(mgpu_excisor_params)) return refuse(c, MGPU_ERR_ARG, "excisor: params_size is not this library's sizeof(mgpu_excisor_params)");
+    if (mode != MGPU_EXCISE_OFF && mode != MGPU_EXCISE_WELCH) return refuse(c, MGPU_ERR_ARG, "excisor mode must be MGPU_EXCISE_OFF or MGPU_EXCISE_WELCH");
     Excisor& E = c->exc;
     return guard(c, [&] {
         const mgpu_excisor_params q = params ? *params : mgpu_excisor_params MGPU_EXCISOR_PARAMS_DEFAULT;
@@ -314,10 +308,7 @@ int mgpu_get_excisor(mgpu_ctx* c, int* mode, mgpu_excisor_params* params, size_t
 int mgpu_get_excisor_report(mgpu_ctx* c, int first, int count, mgpu_excisor_report* report) {
     if (!c || first < 0 || count < 0 || (count && !report)) return MGPU_ERR_ARG;
     return guard(c, [&] {
-        need(size_t(first) + size_t(count) <= size_t(c->max_batch), "bad argument (first + count must be <= max_batch)");
-        need(bool(c->exc.d_report.p), "MGPU_EXCISE_WELCH was never set on this context");
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (count) HIPCK(hipMemcpy(report, c->exc.d_report + size_t(first), size_t(count) * sizeof(mgpu_excisor_report), hipMemcpyDeviceToHost));
+        read_rows(c, c->exc.d_report, 1, first, count, report, "MGPU_EXCISE_WELCH was never set on this context");
     });
 }
 
@@ -357,7 +348,7 @@ int host_brev10(int i) {
 
 extern "C" int mgpu_host_excise(const mgpu_excisor_params* params, double carrier_hz, const double* in, int n, double* out, mgpu_excisor_report* report) {
     if (!in || !out || n < 1 || n > (1 << 30) || !std::isfinite(carrier_hz) || std::fabs(carrier_hz) > 1e9) return MGPU_ERR_ARG;
-    try {
+    return host_try([&]() -> int {
         const mgpu_excisor_params q = params ? *params : mgpu_excisor_params MGPU_EXCISOR_PARAMS_DEFAULT;
         excisor_check(q);
         const ExciseTables& T = excise_tables();
@@ -423,5 +414,5 @@ extern "C" int mgpu_host_excise(const mgpu_excisor_params* params, double carrie
             out[i] = in[i] - (e[size_t(b0) * kN + kH + r0] + e[size_t(b0 + 1) * kN + r0]);
         }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }

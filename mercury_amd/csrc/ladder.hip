@@ -116,20 +116,71 @@ static int window_side(int v) {
 
 }  // namespace mgpu_detail
 
+// The front-end's general path (frontend.hip: the reference's own walk over the window's cells, ofdm.cc:1315-1451) on the host. What it needs
+// of the mode's tables is kept for the last geometry asked for (geometry_cache.hpp): a sweep over windows and frames builds the tables once.
+namespace {
+struct TwinGeometry {
+    bool ls = false;                    // an OFDM mode with the LS estimator
+    int Nc = 0, Nsymb = 0;
+    double pilot_boost = 0;
+    std::vector<uint8_t> cell_type;
+    std::vector<double> pilot_val;
+};
+
+// fn(the mode's geometry) as a host twin (ctx.hpp host_twin); MGPU_ERR_UNSUPPORTED where the mode has no LS window. The twins of this file
+// do not read ls_window: it is put back to its default, so that a sweep over it keeps the geometry.
+template <typename Fn> int ls_twin(int cfg, const mgpu_explicit_params* p, Fn&& fn) {
+    return host_twin(p, [&](mgpu::ExplicitParams xp) -> int {
+        xp.ls_window = mgpu::ExplicitParams().ls_window;
+        const auto geometry = cached_geometry<TwinGeometry>(cfg, xp, [](const mgpu::ModeTables& t) {
+            return TwinGeometry{t.mfsk_M == 0 && t.estimator == MGPU_EST_LS, t.Nc, t.Nsymb, t.pilot_boost, t.cell_type, t.pilot_val};
+        });
+        if (!geometry->ls) return MGPU_ERR_UNSUPPORTED;
+        return fn(geometry);
+    });
+}
+}  // namespace
+
+namespace {
+// the tables of the last (geometry, design) asked for: a sweep over frames builds them once
+struct TwinWiener {
+    std::shared_ptr<const TwinGeometry> geometry;
+    mgpu_wiener_design design{};
+    mgpu::WienerTables tables;
+};
+std::mutex wiener_mutex;
+std::shared_ptr<const TwinWiener> wiener_last;
+
+// fn(the mode's geometry, the design's tables) as ls_twin; MGPU_ERR_ARG where the design is refused
+template <typename Fn> int wiener_twin(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d_or_null, Fn&& fn) {
+    const mgpu_wiener_design d = d_or_null ? *d_or_null : mgpu_wiener_design MGPU_WIENER_DESIGN_DEFAULT;
+    const mgpu::WienerDesign design{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db};
+    if (!mgpu::wiener_design_ok(design)) return MGPU_ERR_ARG;
+    return ls_twin(cfg, p, [&](const std::shared_ptr<const TwinGeometry>& geometry) -> int {
+        std::shared_ptr<const TwinWiener> twin;
+        {
+            std::lock_guard<std::mutex> lock(wiener_mutex);
+            if (!wiener_last || wiener_last->geometry != geometry || std::memcmp(&wiener_last->design, &d, sizeof(d)) != 0) {
+                auto w = std::make_shared<TwinWiener>();
+                w->geometry = geometry; w->design = d;
+                w->tables = mgpu::build_wiener_tables(geometry->cell_type, geometry->Nsymb, geometry->Nc, geometry->pilot_boost, design);
+                wiener_last = w;
+            }
+            twin = wiener_last;
+        }
+        return fn(*geometry, twin->tables);
+    });
+}
+}  // namespace
+
 extern "C" {
 
 int mgpu_set_estimator_ladder_ex(mgpu_ctx* c, const mgpu_estimator_rung* rungs, int n_rungs, size_t rung_size) {
     if (!c) return MGPU_ERR_ARG;
-    if (rung_size != sizeof(mgpu_estimator_rung)) {
-        c->err = "estimator ladder: rung_size is not this library's sizeof(mgpu_estimator_rung)";
-        return MGPU_ERR_ARG;
-    }
+    if (rung_size != sizeof(mgpu_estimator_rung)) return refuse(c, MGPU_ERR_ARG, "estimator ladder: rung_size is not this library's sizeof(mgpu_estimator_rung)");
     const auto& t = c->tab;
     if (n_rungs == 0 && c->lad.n == 0) return MGPU_OK;      // nothing set, nothing to clear: fine on every mode
-    if (t.mfsk_M > 0 || t.estimator != MGPU_EST_LS) {
-        c->err = "an estimator ladder needs an OFDM mode with the LS estimator (the zero-forcing and MFSK modes have no window)";
-        return MGPU_ERR_UNSUPPORTED;
-    }
+    if (t.mfsk_M > 0 || t.estimator != MGPU_EST_LS) return refuse(c, MGPU_ERR_UNSUPPORTED, "an estimator ladder needs an OFDM mode with the LS estimator (the zero-forcing and MFSK modes have no window)");
     return guard(c, [&] {
         need(n_rungs >= 0 && n_rungs <= MGPU_LADDER_MAX && (rungs || n_rungs == 0), "estimator ladder: 0..MGPU_LADDER_MAX rungs");
         mgpu_ls_window win[MGPU_LADDER_MAX]{};
@@ -263,10 +314,7 @@ mgpu::WienerBankRule bank_rule(const std::vector<uint8_t>& cell_type, int Nsymb,
 
 int mgpu_set_wiener_bank(mgpu_ctx* c, int rung, const mgpu_wiener_bank_entry* e, int n, size_t entry_size) {
     if (!c) return MGPU_ERR_ARG;
-    if (entry_size != sizeof(mgpu_wiener_bank_entry)) {
-        c->err = "Wiener bank: entry_size is not this library's sizeof(mgpu_wiener_bank_entry)";
-        return MGPU_ERR_ARG;
-    }
+    if (entry_size != sizeof(mgpu_wiener_bank_entry)) return refuse(c, MGPU_ERR_ARG, "Wiener bank: entry_size is not this library's sizeof(mgpu_wiener_bank_entry)");
     return guard(c, [&] {
         const auto& t = c->tab;
         Ladder& L = c->lad;
@@ -331,10 +379,9 @@ int mgpu_get_wiener_choice(mgpu_ctx* c, int first, int count, int* design, doubl
     return guard(c, [&] {
         const Ladder& L = c->lad;
         need(L.n > 0 && L.kind[0] == MGPU_RUNG_WIENER && L.bank[0].n > 0, "rung 0 has no Wiener bank");
-        need(first >= 0 && count >= 0 && size_t(first) + size_t(count) <= size_t(c->max_batch), "bad argument (first + count must be <= max_batch)");
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (design && count) HIPCK(hipMemcpy(design, L.d_choice + first, size_t(count) * sizeof(int), hipMemcpyDeviceToHost));
-        if (corr && count) HIPCK(hipMemcpy(corr, L.d_corr + size_t(first) * 4, size_t(count) * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        need(first >= 0 && count >= 0, "bad argument (first + count must be <= max_batch)");
+        read_rows(c, L.d_choice, 1, first, count, design, "rung 0 has no Wiener bank");
+        read_rows(c, L.d_corr, 4, first, count, corr, "rung 0 has no Wiener bank");
         if (n1) *n1 = L.bank[0].n1;
         if (n2) *n2 = L.bank[0].n2;
     });
@@ -364,52 +411,12 @@ int mgpu_estimator_ladder_counters(mgpu_ctx* c, long long decoded_by_rung[MGPU_L
     });
 }
 
-// The front-end's general path (frontend.hip: the reference's own walk over the window's cells, ofdm.cc:1315-1451) on the host. What it needs
-// of the mode's tables is kept for the last geometry asked for: a sweep over windows and frames builds the tables once.
-namespace {
-struct TwinGeometry {
-    int cfg = -1;
-    mgpu::ExplicitParams xp;
-    bool ls = false;                    // an OFDM mode with the LS estimator
-    int Nc = 0, Nsymb = 0;
-    double pilot_boost = 0;
-    std::vector<uint8_t> cell_type;
-    std::vector<double> pilot_val;
-};
-std::mutex twin_mutex;
-std::shared_ptr<const TwinGeometry> twin_last;
-
-std::shared_ptr<const TwinGeometry> twin_geometry(int cfg, const mgpu::ExplicitParams& xp) {
-    std::lock_guard<std::mutex> lock(twin_mutex);
-    const auto same = [&](const TwinGeometry& g) {
-        return g.cfg == cfg && g.xp.pilot_boost == xp.pilot_boost && g.xp.ls_window == xp.ls_window && g.xp.pilot_seed == xp.pilot_seed &&
-               g.xp.scrambler_seed == xp.scrambler_seed && g.xp.preamble_seed == xp.preamble_seed && g.xp.Nsymb == xp.Nsymb && g.xp.Dy == xp.Dy;
-    };
-    if (twin_last && same(*twin_last)) return twin_last;
-    const mgpu::ModeTables t = mgpu::build_mode_tables(cfg, 0, mgpu_ldpc_blob, mgpu_ldpc_blob_size, xp);
-    auto g = std::make_shared<TwinGeometry>();
-    g->cfg = cfg; g->xp = xp;
-    g->ls = t.mfsk_M == 0 && t.estimator == MGPU_EST_LS;
-    g->Nc = t.Nc; g->Nsymb = t.Nsymb; g->pilot_boost = t.pilot_boost;
-    g->cell_type = t.cell_type; g->pilot_val = t.pilot_val;
-    twin_last = g;
-    return g;
-}
-}  // namespace
-
 int mgpu_host_ls_estimate(int cfg, const mgpu_explicit_params* p, int width, int height, const double* grid, double* H) {
     if (!grid || !H) return MGPU_ERR_ARG;
     const int wf = window_side(width), wt = window_side(height);
     if (!wf || !wt) return MGPU_ERR_ARG;
-    mgpu::ExplicitParams xp;
-    std::string err;
-    int rc = MGPU_OK;
-    if (!explicit_params_from(p, xp, err, &rc)) return rc;
-    xp.ls_window = mgpu::ExplicitParams().ls_window;
-    try {
-        const std::shared_ptr<const TwinGeometry> geometry = twin_geometry(cfg, xp);
+    return ls_twin(cfg, p, [&](const std::shared_ptr<const TwinGeometry>& geometry) -> int {
         const TwinGeometry& t = *geometry;
-        if (!t.ls) return MGPU_ERR_UNSUPPORTED;
         const std::vector<double> weight = mgpu::ls_weight_table(t.pilot_boost, wf * wt);
         const int Nc = t.Nc, Ns = t.Nsymb, hf = wf / 2, ht = wt / 2;
         int pilot = 0;
@@ -434,50 +441,12 @@ int mgpu_host_ls_estimate(int cfg, const mgpu_explicit_params* p, int width, int
             ++pilot;
         }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
-
-namespace {
-// the tables of the last (geometry, design) asked for: a sweep over frames builds them once
-struct TwinWiener {
-    std::shared_ptr<const TwinGeometry> geometry;
-    mgpu_wiener_design design{};
-    mgpu::WienerTables tables;
-};
-std::mutex wiener_mutex;
-std::shared_ptr<const TwinWiener> wiener_last;
-
-// null with *rc set where the mode or the design is refused
-std::shared_ptr<const TwinWiener> twin_wiener(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d_or_null, int* rc) {
-    const mgpu_wiener_design d = d_or_null ? *d_or_null : mgpu_wiener_design MGPU_WIENER_DESIGN_DEFAULT;
-    *rc = MGPU_ERR_ARG;
-    if (!mgpu::wiener_design_ok(mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db})) return nullptr;
-    mgpu::ExplicitParams xp;
-    std::string err;
-    if (!explicit_params_from(p, xp, err, rc)) return nullptr;
-    xp.ls_window = mgpu::ExplicitParams().ls_window;
-    const std::shared_ptr<const TwinGeometry> geometry = twin_geometry(cfg, xp);
-    if (!geometry->ls) { *rc = MGPU_ERR_UNSUPPORTED; return nullptr; }
-    *rc = MGPU_OK;
-    std::lock_guard<std::mutex> lock(wiener_mutex);
-    if (wiener_last && wiener_last->geometry == geometry && std::memcmp(&wiener_last->design, &d, sizeof(d)) == 0) return wiener_last;
-    auto w = std::make_shared<TwinWiener>();
-    w->geometry = geometry; w->design = d;
-    w->tables = mgpu::build_wiener_tables(geometry->cell_type, geometry->Nsymb, geometry->Nc, geometry->pilot_boost,
-                                          mgpu::WienerDesign{d.tau_min_us, d.tau_max_us, d.doppler_hz, d.snr_db});
-    wiener_last = w;
-    return w;
-}
-}  // namespace
 
 int mgpu_host_wiener_estimate(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d, const double* grid, double* H) {
     if (!grid || !H) return MGPU_ERR_ARG;
-    try {
-        int rc = MGPU_OK;
-        const std::shared_ptr<const TwinWiener> twin = twin_wiener(cfg, p, d, &rc);
-        if (!twin) return rc;
-        const TwinGeometry& t = *twin->geometry;
-        const mgpu::WienerTables& w = twin->tables;
+    return wiener_twin(cfg, p, d, [&](const TwinGeometry& t, const mgpu::WienerTables& w) -> int {
         const size_t nP = w.time_class.size();
         std::vector<double> yp(2 * nP), tp(2 * nP);
         size_t pilot = 0;
@@ -513,31 +482,13 @@ int mgpu_host_wiener_estimate(int cfg, const mgpu_explicit_params* p, const mgpu
             }
         }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
-
-namespace {
-// the mode's geometry for the bank's twins; null with *rc set where the mode is refused
-std::shared_ptr<const TwinGeometry> bank_geometry(int cfg, const mgpu_explicit_params* p, int* rc) {
-    mgpu::ExplicitParams xp;
-    std::string err;
-    *rc = MGPU_ERR_ARG;
-    if (!explicit_params_from(p, xp, err, rc)) return nullptr;
-    xp.ls_window = mgpu::ExplicitParams().ls_window;
-    std::shared_ptr<const TwinGeometry> geometry = twin_geometry(cfg, xp);
-    if (!geometry->ls) { *rc = MGPU_ERR_UNSUPPORTED; return nullptr; }
-    *rc = MGPU_OK;
-    return geometry;
-}
-}  // namespace
 
 int mgpu_host_wiener_select(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_bank_entry* e, int n, size_t entry_size, const double* grid,
                             int* design, double corr[4], int* n1, int* n2) {
     if (!grid || !e || entry_size != sizeof(mgpu_wiener_bank_entry) || n < 1 || n > MGPU_WIENER_BANK_MAX) return MGPU_ERR_ARG;
-    try {
-        int rc = MGPU_OK;
-        const std::shared_ptr<const TwinGeometry> geometry = bank_geometry(cfg, p, &rc);
-        if (!geometry) return rc;
+    return ls_twin(cfg, p, [&](const std::shared_ptr<const TwinGeometry>& geometry) -> int {
         const TwinGeometry& t = *geometry;
         mgpu::WienerDesign designs[MGPU_WIENER_BANK_MAX];
         const mgpu::WienerBankRule rule = bank_rule(t.cell_type, t.Nsymb, t.Nc, e, n, designs);
@@ -578,32 +529,25 @@ int mgpu_host_wiener_select(int cfg, const mgpu_explicit_params* p, const mgpu_w
         if (n1) *n1 = rule.n1;
         if (n2) *n2 = rule.n2;
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
 
 int mgpu_host_wiener_bank_thresholds(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_bank_entry* e, int n, size_t entry_size, double* rho_min,
                                      int* pilot_spacing) {
     if (!e || entry_size != sizeof(mgpu_wiener_bank_entry) || n < 1 || n > MGPU_WIENER_BANK_MAX) return MGPU_ERR_ARG;
-    try {
-        int rc = MGPU_OK;
-        const std::shared_ptr<const TwinGeometry> geometry = bank_geometry(cfg, p, &rc);
-        if (!geometry) return rc;
+    return ls_twin(cfg, p, [&](const std::shared_ptr<const TwinGeometry>& geometry) -> int {
         mgpu::WienerDesign designs[MGPU_WIENER_BANK_MAX];
         const mgpu::WienerBankRule rule = bank_rule(geometry->cell_type, geometry->Nsymb, geometry->Nc, e, n, designs);
         if (rho_min) std::copy(rule.rho_min.begin(), rule.rho_min.end(), rho_min);
         if (pilot_spacing) *pilot_spacing = rule.s;
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
 
 int mgpu_host_wiener_tables(int cfg, const mgpu_explicit_params* p, const mgpu_wiener_design* d, int which, int cls, int* n_classes, int* n,
                             int* members, double* matrix) {
     if (which != 0 && which != 1) return MGPU_ERR_ARG;
-    try {
-        int rc = MGPU_OK;
-        const std::shared_ptr<const TwinWiener> twin = twin_wiener(cfg, p, d, &rc);
-        if (!twin) return rc;
-        const mgpu::WienerTables& w = twin->tables;
+    return wiener_twin(cfg, p, d, [&](const TwinGeometry&, const mgpu::WienerTables& w) -> int {
         const auto& sets = which == 0 ? w.time_members : w.freq_members;
         if (n_classes) *n_classes = int(sets.size());
         if (!n && !members && !matrix) return MGPU_OK;
@@ -615,7 +559,7 @@ int mgpu_host_wiener_tables(int cfg, const mgpu_explicit_params* p, const mgpu_w
         if (matrix && which == 1)
             for (size_t i = 0; i < m * m; ++i) { matrix[2 * i] = w.B[size_t(cls)][i].re; matrix[2 * i + 1] = w.B[size_t(cls)][i].im; }
         return MGPU_OK;
-    } catch (const std::exception&) { return MGPU_ERR_ARG; }
+    });
 }
 
 }  // extern "C"

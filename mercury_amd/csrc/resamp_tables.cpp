@@ -8,6 +8,7 @@
 
 #include "chan_tables.hpp"
 #include "resamp_tables.hpp"
+#include "sample_formats.h"
 #include "../../include/mercury_gpu.h"
 
 namespace mgpu_resamp_detail {
@@ -18,24 +19,6 @@ bool ratio(int fin, int fout, Ratio* r) {
     r->L = fout / g;
     r->M = fin / g;
     return r->L <= MGPU_RESAMP_MAX_L && r->M <= MGPU_RESAMP_MAX_M && r->M <= MGPU_RESAMP_MAX_RATIO * r->L;
-}
-
-size_t format_bytes(int components, int format) {
-    if (components == 1) {
-        switch (format) {
-            case MGPU_SAMPLES_F64: return 8;
-            case MGPU_SAMPLES_INT32: return 4;
-            case MGPU_SAMPLES_INT16: return 2;
-            case MGPU_SAMPLES_F32: return 4;
-        }
-    } else if (components == 2) {
-        switch (format) {
-            case MGPU_IQ_CS16: return 2;
-            case MGPU_IQ_CF32: return 4;
-            case MGPU_IQ_CF64: return 8;
-        }
-    }
-    return 0;
 }
 
 const char* config_error(const mgpu_resamp_config* k) {
@@ -65,25 +48,6 @@ namespace {
 void design(int fin, const Ratio& r, int tp, double cutoff_hz, double atten_db, double* h) {
     const double R = double(fin) * r.L;
     mgpu_chan_detail::windowed_sinc(tp * r.L + 1, 2 * cutoff_hz / R, atten_db, r.L, h);
-}
-
-template <typename T> double widen(const T* p, size_t i, double divisor) { return divisor == 1.0 ? double(p[i]) : double(p[i]) / divisor; }
-
-// element i of the samples, widened: real formats as the capture thread's, IQ formats as the channeliser's
-double widen_at(int components, int format, const void* in, size_t i) {
-    if (components == 1) {
-        switch (format) {
-            case MGPU_SAMPLES_INT32: return widen(static_cast<const int32_t*>(in), i, 2147483647.0);
-            case MGPU_SAMPLES_INT16: return widen(static_cast<const int16_t*>(in), i, 32768.0);
-            case MGPU_SAMPLES_F32: return widen(static_cast<const float*>(in), i, 1.0);
-            default: return static_cast<const double*>(in)[i];
-        }
-    }
-    switch (format) {
-        case MGPU_IQ_CS16: return widen(static_cast<const int16_t*>(in), i, 32768.0);
-        case MGPU_IQ_CF32: return widen(static_cast<const float*>(in), i, 1.0);
-        default: return static_cast<const double*>(in)[i];
-    }
 }
 
 }  // namespace
@@ -131,7 +95,8 @@ int mgpu_host_resamp_count(int fin, int fout, uint64_t m0, int n_in, int* n_out)
 
 int mgpu_host_resamp_process(const mgpu_resamp_config* k, const void* in, int format, int n_in, uint64_t position, double* out,
                              size_t out_stride, int* n_out) {
-    if (config_error(k) || !in || !n_out || n_in < 1 || !format_bytes(k->components, format)) return MGPU_ERR_ARG;
+    const int e = k ? mgpu_fmt::element(k->components, format) : mgpu_fmt::kNone;
+    if (config_error(k) || !in || !n_out || n_in < 1 || e == mgpu_fmt::kNone) return MGPU_ERR_ARG;
     int N = 0;
     if (mgpu_host_resamp_count(k->fin, k->fout, position, n_in, &N) != MGPU_OK || size_t(N) > out_stride || (N && !out)) return MGPU_ERR_ARG;
     Ratio r;
@@ -142,7 +107,7 @@ int mgpu_host_resamp_process(const mgpu_resamp_config* k, const void* in, int fo
     const long long n0 = (long long)out_position(position, r);
     std::vector<double> x(size_t(n_in) * C);
     for (int s = 0; s < k->S; ++s) {
-        for (size_t i = 0; i < x.size(); ++i) x[i] = widen_at(C, format, in, size_t(s) * x.size() + i);
+        for (size_t i = 0; i < x.size(); ++i) x[i] = mgpu_fmt::widen_at(e, in, size_t(s) * x.size() + i);
         for (int i = 0; i < N; ++i) {
             const long long q = (n0 + i) * M, b = q / L - m0, rho = q % L;      // b relative to the seek: zeros before it
             for (int comp = 0; comp < C; ++comp) {

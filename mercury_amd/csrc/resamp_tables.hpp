@@ -28,8 +28,6 @@ inline int default_max_in(const Ratio& r) { return int((17408LL * r.M + r.L - 1)
 inline uint64_t out_position(uint64_t m, const Ratio& r) { return (m * uint64_t(r.L) + uint64_t(r.M) - 1) / uint64_t(r.M); }
 // why the configuration is refused, or null
 const char* config_error(const mgpu_resamp_config* k);
-// the element size of `format` for C components, 0 where the format does not fit C
-size_t format_bytes(int components, int format);
 // the prototype of a checked configuration: its own taps, or the default design at its tp
 std::vector<double> prototype(const mgpu_resamp_config* k, const Ratio& r);
 inline int config_tp(const mgpu_resamp_config* k, const Ratio& r) { return k->tp ? k->tp : default_tp(r); }

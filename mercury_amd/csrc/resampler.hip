@@ -27,7 +27,6 @@ using namespace mgpu_resamp_detail;
 namespace {
 
 constexpr int kTile = 128;                   // outputs of one stream per workgroup = threads per workgroup
-enum { kF64 = 0, kI32 = 1, kI16 = 2, kF32 = 3 };   // the element types of MGPU_SAMPLES_* and MGPU_IQ_*
 
 struct ResampArgs {
     const void* in;           // [S][n_in * C] elements of `kind`
@@ -38,14 +37,9 @@ struct ResampArgs {
     double* out0;             // outputs i < split:  out0[(s * stride0 + i) * C + comp]
     double* out1;             // the others:         out1[(s * stride1 + i - split) * C + comp]
     size_t stride0, stride1;
-    int split, kind, n_in, n_out, tp, L, M, d0, s0, lds_elems;
+    int split, kind, n_in, n_out, tp, L, M, d0, s0, lds_elems;      // kind: the samples' mgpu_fmt::Element
     unsigned r0;
 };
-
-int element_kind(int components, int format) {
-    if (components == 1) return format == MGPU_SAMPLES_INT32 ? kI32 : format == MGPU_SAMPLES_INT16 ? kI16 : format == MGPU_SAMPLES_F32 ? kF32 : kF64;
-    return format == MGPU_IQ_CS16 ? kI16 : format == MGPU_IQ_CF32 ? kF32 : kF64;
-}
 
 }  // namespace
 
@@ -54,13 +48,7 @@ __device__ inline double resamp_x(const ResampArgs& a, int s, int C, int e) {
     const int hist = a.tp * C, n = a.n_in * C;
     if (e < 0) return (a.hist_old && e >= -hist) ? a.hist_old[size_t(s) * hist + size_t(hist + e)] : 0.0;
     if (e >= n) return 0.0;
-    const size_t i = size_t(s) * size_t(n) + size_t(e);
-    switch (a.kind) {
-        case kI32: return double(static_cast<const int32_t*>(a.in)[i]) / 2147483647.0;
-        case kI16: return double(static_cast<const int16_t*>(a.in)[i]) / 32768.0;
-        case kF32: return double(static_cast<const float*>(a.in)[i]);
-        default: return static_cast<const double*>(a.in)[i];
-    }
+    return mgpu_fmt::widen_at(a.kind, a.in, size_t(s) * size_t(n) + size_t(e));
 }
 
 template <int C>
@@ -132,7 +120,7 @@ struct mgpu_resamp {
     int cur = 0;                                  // the history buffer the next call reads
     DevArray<double> d_hist[2];                   // [S][tp * C]
     DevArray<double> d_hp;                        // [L][tp]
-    DevArray<char> d_stage;                       // host input's landing area (grown)
+    DevArray<char> d_stage;                       // host input's landing area (ctx.hpp staged_on_device)
     DevArray<double> d_out;                       // [S][max_out * C]: process()'s output (made on first use)
     // the FIFO of mgpu_capture_run_resampled (made on its first call): what is left after the last whole hop, fewer than P per stream
     int P = 0, fill = 0, rem_cur = 0;
@@ -143,7 +131,7 @@ struct mgpu_resamp {
 
     void check_in(const void* in, int format, int n_in, const int* n_out) const {
         need(in && n_out, "null pointer");
-        need(format_bytes(C, format) != 0, "the format does not fit the components");
+        need(mgpu_fmt::element(C, format) != mgpu_fmt::kNone, "the format does not fit the components");
         need(n_in >= 1 && n_in <= max_in, "n_in must be 1..max_in");
         need(m0 + uint64_t(n_in) <= MGPU_RESAMP_MAX_POSITION, "position beyond 2^52");
     }
@@ -155,7 +143,7 @@ struct mgpu_resamp {
         a.in = d_in; a.hist_old = fresh ? nullptr : static_cast<const double*>(d_hist[cur]); a.hist_new = d_hist[cur ^ 1];
         a.hp = d_hp; a.h_last = h.back();
         a.out0 = out0; a.out1 = out1; a.stride0 = stride0; a.stride1 = stride1; a.split = split;
-        a.kind = element_kind(C, format); a.n_in = n_in; a.n_out = count(n_in); a.tp = tp; a.L = r.L; a.M = r.M;
+        a.kind = mgpu_fmt::element(C, format); a.n_in = n_in; a.n_out = count(n_in); a.tp = tp; a.L = r.L; a.M = r.M;
         a.d0 = int(q0 / uint64_t(r.L) - m0); a.r0 = unsigned(q0 % uint64_t(r.L)); a.lds_elems = lds_elems;
         const unsigned gx = unsigned(std::max(1, (a.n_out + kTile - 1) / kTile));
         for (int s0 = 0; s0 < S; s0 += 65535) {                    // grid y is 16 bits wide
@@ -168,14 +156,8 @@ struct mgpu_resamp {
         m0 += uint64_t(n_in);
     }
 
-    // the input where the kernel can read it: device memory as it is, host memory through the staging buffer
     const void* on_device(const void* in, int format, int n_in, hipStream_t st) {
-        if (is_device_memory(in)) return in;
-        const size_t bytes = size_t(S) * n_in * C * format_bytes(C, format);
-        HIPCK(hipStreamSynchronize(st));          // the last call's reads of the staging buffer
-        d_stage.grow(bytes);
-        HIPCK(hipMemcpyAsync(d_stage.p, in, bytes, hipMemcpyHostToDevice, st));
-        return d_stage.p;
+        return staged_on_device(d_stage, in, size_t(S) * n_in * C * mgpu_fmt::element_bytes(mgpu_fmt::element(C, format)), st);
     }
 };
 
@@ -272,13 +254,8 @@ int mgpu_capture_run_resampled(mgpu_capture* cap, mgpu_resamp* k, const void* sa
                                uint8_t* payloads, int max_events, int* n_events, int* hops_run) {
     if (!cap || !k) return MGPU_ERR_ARG;
     mgpu_capture_geometry g{};
-    mgpu_capture_state probe;
-    // the capture has exactly S captures: S - 1 is one of them, S is not
-    if (mgpu_capture_geometry_get(cap, &g) != MGPU_OK || mgpu_capture_get_state(cap, k->S - 1, &probe) != MGPU_OK ||
-        mgpu_capture_get_state(cap, k->S, &probe) == MGPU_OK || capture_context(cap) != k->c || k->C != 1 || k->cfg.fout != 48000) {
-        k->c->err = "mgpu_capture_run_resampled: one context, the same S, components = 1 and fout = 48000";
-        return MGPU_ERR_ARG;
-    }
+    if (mgpu_capture_geometry_get(cap, &g) != MGPU_OK || capture_streams(cap) != k->S || capture_context(cap) != k->c || k->C != 1 || k->cfg.fout != 48000)
+        return refuse(k->c, MGPU_ERR_ARG, "mgpu_capture_run_resampled: one context, the same S, components = 1 and fout = 48000");
     int H = 0;
     const int rc = guard(k->c, [&] {
         k->check_in(samples, format, n_in, hops_run);

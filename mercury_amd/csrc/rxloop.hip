@@ -830,14 +830,13 @@ void mgpu_detail::receive_byte_impl(mgpu_ctx* c, const double* passband, int W, 
 template <typename T>
 __global__ __launch_bounds__(256) void mgpu_widen_capture_kernel(const T* __restrict__ in, size_t n, double divisor, double* __restrict__ out) {
     for (size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x) * blockDim.x) {
-        const double x = double(in[i]);
-        out[i] = divisor == 1.0 ? x : x / divisor;
+        out[i] = mgpu_fmt::widen(in[i], divisor);
     }
 }
 namespace {
 void launch_widen(const void* d_in, int fmt, size_t n, double* d_out, hipStream_t s) {      // compact formats only: doubles are read where they lie
     const dim3 grid(unsigned(std::min<size_t>((n + 255) / 256, 65535u * 4))), block(256);
-    with_samples(fmt, d_in, [&](auto* in, double divisor) {
+    mgpu_fmt::with_elements(mgpu_fmt::element(1, fmt), d_in, [&](auto* in, double divisor) {
         using T = std::remove_cv_t<std::remove_pointer_t<decltype(in)>>;
         if constexpr (!std::is_same_v<T, double>) hipLaunchKernelGGL(mgpu_widen_capture_kernel<T>, grid, block, 0, s, in, n, divisor, d_out);
     });
@@ -870,7 +869,7 @@ std::vector<std::pair<int, int>> pieces(int W, int fmt) {
 
 // windows [off, off + n) of the host capture into the staging buffer as doubles (compact samples: copied, then widened), waited for
 hipError_t upload_piece(mgpu_ctx* c, const char* src, int fmt, size_t buf, int off, int n) {
-    const size_t sb = sample_bytes(fmt);
+    const size_t sb = mgpu_fmt::element_bytes(mgpu_fmt::element(1, fmt));
     double* stage = c->rb_stage + size_t(off) * buf;
     void* dst = fmt == MGPU_SAMPLES_F64 ? static_cast<void*>(stage) : c->rb_compact + size_t(off) * buf * sb;
     hipError_t e = hipMemcpyAsync(dst, src + size_t(off) * buf * sb, size_t(n) * buf * sb, hipMemcpyHostToDevice, c->rb_stream);
@@ -886,7 +885,7 @@ hipError_t upload_piece(mgpu_ctx* c, const char* src, int fmt, size_t buf, int o
 void receive_byte_any(mgpu_ctx* c, const void* capture, int fmt, int W, const mgpu_receive_config* rcp, mgpu_link_state* state, uint8_t* payload,
                       mgpu_receive_stats* stats) {
     need(capture && rcp && payload && stats && W > 0 && W <= c->max_batch, "bad argument (W must be 1..max_batch)");
-    need(known_format(fmt), "unknown sample format");
+    need(mgpu_fmt::element(1, fmt) != mgpu_fmt::kNone, "unknown sample format");
     need(rcp->time_sync_trials_max >= 1 && rcp->time_sync_trials_max < 64,
          "time_sync_trials_max must be 1..63 (0 makes the reference index its peak table at -1)");
     // every argument is judged before the first copy or kernel is queued: an error return leaves nothing in flight and no state[] entry touched
@@ -902,7 +901,7 @@ void receive_byte_any(mgpu_ctx* c, const void* capture, int fmt, int W, const mg
     const bool on_device = is_device_memory(capture);
     const auto& t = c->tab;
     const size_t buf = size_t(t.Nofdm) * mgpu_receive_buffer_nsymb(c) * kInterp;
-    const size_t sb = sample_bytes(fmt);
+    const size_t sb = mgpu_fmt::element_bytes(mgpu_fmt::element(1, fmt));
     const char* src = static_cast<const char*>(capture);
     if (!c->rb_stream) HIPCK(hipStreamCreateWithFlags(&c->rb_stream.h, hipStreamNonBlocking));
     const int kMinSub = 256;

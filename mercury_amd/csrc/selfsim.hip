@@ -70,7 +70,7 @@ int mgpu_baseband_test_esn0(mgpu_ctx* c, const double* esn0_db, int npoints, lon
 int mgpu_baseband_test_esn0_hf(mgpu_ctx* c, const double* esn0_db, int npoints, long long frames_per_point, uint64_t seed, uint64_t frame0,
                                const mgpu_hf_channel* ch, mgpu_error_rate* out) {
     if (!c) return MGPU_ERR_ARG;
-    if (!ch) { c->err = "no channel"; return MGPU_ERR_ARG; }
+    if (!ch) return refuse(c, MGPU_ERR_ARG, "no channel");
     return baseband_test_esn0_impl(c, esn0_db, npoints, frames_per_point, seed, frame0, 0, ch, out);
 }
 

@@ -80,6 +80,12 @@ struct ExplicitParams {
     int Nsymb = 0;                 // ofdm_Nsymb; 0 = what init() selects from the modulation for HIGH_DENSITY pilots (telecom_system.cc:1810-1826)
     int Dy = 3;                    // ofdm_pilot_configurator_Dy: 3 = HIGH_DENSITY (every mode's default), 5 = the reference's LOW_DENSITY option (telecom_system.cc:1848-1869)
 };
+// every field: what is cached per parameter set (geometry_cache.hpp) is looked up by this
+inline bool operator==(const ExplicitParams& a, const ExplicitParams& b) {
+    return a.pilot_boost == b.pilot_boost && a.ls_window == b.ls_window && a.pilot_seed == b.pilot_seed && a.scrambler_seed == b.scrambler_seed &&
+           a.preamble_seed == b.preamble_seed && a.Nsymb == b.Nsymb && a.Dy == b.Dy;
+}
+static_assert(sizeof(ExplicitParams) == 7 * 4, "ExplicitParams has changed: compare the new field in operator== above, then update this size");
 
 struct ModeTables {
     ExplicitParams xp;

@@ -21,6 +21,80 @@ DEC_GBF, DEC_SPA, DEC_MINSUM, DEC_SPA_FAST = 0, 1, 2, 3
 EST_ZF, EST_LS = 0, 1
 
 
+def _checked(fn, *args, what="failed"):
+    """fn(*args) of the library; a status other than 0 raises MgpuError("<the function's name> <what> (<status>)") with the status as its code"""
+    rc = fn(*args)
+    if rc != 0:
+        raise MgpuError("%s %s (%d)" % (fn.__name__, what, rc), rc)
+
+
+def _explicit_struct(explicit):
+    if not explicit:
+        return None
+    seeds = any(k in explicit for k in ("pilot_seed", "scrambler_seed", "preamble_seed"))
+    return ExplicitParams(float(explicit.get("pilot_boost", 0.0)), int(explicit.get("ls_window", 0)), 1 if seeds else 0,
+                          int(explicit.get("pilot_seed", 0)), int(explicit.get("scrambler_seed", 0)), int(explicit.get("preamble_seed", 1)),
+                          int(explicit.get("Nc", 0)), int(explicit.get("Nfft", 0)), int(explicit.get("Dx", 0)), int(explicit.get("Dy", 0)),
+                          int(explicit.get("Nsymb", 0)))
+
+
+def _explicit_ref(explicit):
+    """`explicit` (a dict as RxPhy takes it, or None) as the mgpu_explicit_params pointer the library takes"""
+    xp = _explicit_struct(explicit)
+    return C.byref(xp) if xp is not None else None
+
+
+def _written(call, *probes):
+    """how many entries of each output a twin writes for the geometry at hand: call(NaN-filled arrays of the given (size, dtype)) once,
+    count what is no NaN any more"""
+    arrays = [np.full(n, np.nan, dtype) for n, dtype in probes]
+    call(*arrays)
+    return [int(np.count_nonzero(~np.isnan(a.real))) for a in arrays]
+
+
+def _parse_spec(text, what, modes, mode, defaults, keys, usage, takes):
+    """"NAME" or "MODE:key=value,..." (the tools' --demapper, --blanker, --excisor) -> (name, None), or (mode, the defaults with what is
+    given) for the one mode that takes parameters. keys: {key: (field of defaults, its type)}"""
+    name, _, rest = str(text).partition(":")
+    if name not in modes or (rest and name != mode):
+        raise ValueError("%s: %s" % (what, usage))
+    if name != mode:
+        return name, None
+    prm = dict(defaults)
+    for item in filter(None, rest.split(",")):
+        key, _, value = item.partition("=")
+        if key not in keys:
+            raise ValueError("%s %s: %s what it takes, not %r" % (what, mode, takes, item))
+        field, kind = keys[key]
+        prm[field] = kind(value)
+    return name, prm
+
+
+def _params(struct, defaults, given):
+    """a parameter struct of the library from the values given, in the order of its fields; None: the field's default"""
+    return struct(*[kind(defaults[field] if value is None else value) for (field, kind), value in zip(struct._fields_, given)])
+
+
+class _Handle:
+    """what owns one handle of the library, self.h, made by self.lib: close() releases it once with the function named by _destroy, and so
+    does the collection of the object"""
+    _destroy = None
+
+    def _release(self):
+        getattr(self.lib, self._destroy)(self.h)
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self._release()
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Config(C.Structure):
     _fields_ = [("cfg", C.c_int), ("max_iters", C.c_int), ("decoder", C.c_int), ("agc", C.c_int),
                 ("variance_source", C.c_int), ("device", C.c_int), ("max_batch", C.c_int),
@@ -191,25 +265,19 @@ def host_wiener_select(cfg, grid, entries, explicit=None):
     -> dict(design, corr: float64 [4] R1r R1i R2r R2i, n1, n2)"""
     lib = load_library()
     g = np.ascontiguousarray(grid, np.complex128).ravel()
-    xp = _explicit_struct(explicit)
     arr, n = _bank_array(entries)
     design, n1, n2, corr = C.c_int(), C.c_int(), C.c_int(), np.zeros(4, np.float64)
-    rc = lib.mgpu_host_wiener_select(int(cfg), C.byref(xp) if xp is not None else None, arr, n, C.sizeof(WienerBankEntry), _ptr(g), C.byref(design),
-                                     _ptr(corr), C.byref(n1), C.byref(n2))
-    if rc != 0:
-        raise MgpuError("mgpu_host_wiener_select failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_wiener_select, int(cfg), _explicit_ref(explicit), arr, n, C.sizeof(WienerBankEntry), _ptr(g), C.byref(design),
+             _ptr(corr), C.byref(n1), C.byref(n2))
     return dict(design=design.value, corr=corr, n1=n1.value, n2=n2.value)
 
 
 def host_wiener_bank_thresholds(cfg, entries, explicit=None):
     """mgpu_host_wiener_bank_thresholds: (rho_min as applied: float64 [n - 1], the pilot spacing s) of a bank on the mode's geometry; no GPU"""
     lib = load_library()
-    xp = _explicit_struct(explicit)
     arr, n = _bank_array(entries)
     rho, s = np.zeros(max(n - 1, 1), np.float64), C.c_int()
-    rc = lib.mgpu_host_wiener_bank_thresholds(int(cfg), C.byref(xp) if xp is not None else None, arr, n, C.sizeof(WienerBankEntry), _ptr(rho), C.byref(s))
-    if rc != 0:
-        raise MgpuError("mgpu_host_wiener_bank_thresholds failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_wiener_bank_thresholds, int(cfg), _explicit_ref(explicit), arr, n, C.sizeof(WienerBankEntry), _ptr(rho), C.byref(s))
     return rho[: max(n - 1, 0)], s.value
 
 
@@ -229,18 +297,13 @@ def host_wiener_estimate(cfg, grid, design=None, explicit=None):
     defaults). explicit: as RxPhy's."""
     lib = load_library()
     g = np.ascontiguousarray(grid, np.complex128).ravel()
-    xp = _explicit_struct(explicit)
-    ref = C.byref(xp) if xp is not None else None
+    ref = _explicit_ref(explicit)
     d = _wiener_design(design)
     # nPilots of the (possibly explicit) geometry: the entries a call on an all-zero grid writes
-    count = np.full(g.size, np.nan + 0j, np.complex128)
-    rc = lib.mgpu_host_wiener_estimate(int(cfg), ref, C.byref(d), _ptr(np.zeros_like(g)), _ptr(count))
-    if rc != 0:
-        raise MgpuError("mgpu_host_wiener_estimate failed (%d)" % rc, rc)
-    out = np.zeros(int(np.count_nonzero(~np.isnan(count.real))), np.complex128)
-    rc = lib.mgpu_host_wiener_estimate(int(cfg), ref, C.byref(d), _ptr(g), _ptr(out))
-    if rc != 0:
-        raise MgpuError("mgpu_host_wiener_estimate failed (%d)" % rc, rc)
+    nP, = _written(lambda count: _checked(lib.mgpu_host_wiener_estimate, int(cfg), ref, C.byref(d), _ptr(np.zeros_like(g)), _ptr(count)),
+                   (g.size, np.complex128))
+    out = np.zeros(nP, np.complex128)
+    _checked(lib.mgpu_host_wiener_estimate, int(cfg), ref, C.byref(d), _ptr(g), _ptr(out))
     return out
 
 
@@ -248,24 +311,19 @@ def host_wiener_tables(cfg, design=None, explicit=None):
     """mgpu_host_wiener_tables: (time classes, frequency classes) of a design, each a list of (members: int32 [n] - the pilot rows a carrier
     has / the pilot carriers a symbol has -, matrix [n, n]: float64 / complex128, as the kernel reads it); no GPU."""
     lib = load_library()
-    xp = _explicit_struct(explicit)
-    ref = C.byref(xp) if xp is not None else None
+    ref = _explicit_ref(explicit)
     d = _wiener_design(design)
     out = []
     for which in (0, 1):
         count = C.c_int()
-        rc = lib.mgpu_host_wiener_tables(int(cfg), ref, C.byref(d), which, 0, C.byref(count), None, None, None)
-        if rc != 0:
-            raise MgpuError("mgpu_host_wiener_tables failed (%d)" % rc, rc)
+        _checked(lib.mgpu_host_wiener_tables, int(cfg), ref, C.byref(d), which, 0, C.byref(count), None, None, None)
         classes = []
         for cls in range(count.value):
             n = C.c_int()
             lib.mgpu_host_wiener_tables(int(cfg), ref, C.byref(d), which, cls, None, C.byref(n), None, None)
             members = np.zeros(n.value, np.int32)
             matrix = np.zeros((n.value, n.value), np.complex128 if which else np.float64)
-            rc = lib.mgpu_host_wiener_tables(int(cfg), ref, C.byref(d), which, cls, None, None, _ptr(members), _ptr(matrix))
-            if rc != 0:
-                raise MgpuError("mgpu_host_wiener_tables failed (%d)" % rc, rc)
+            _checked(lib.mgpu_host_wiener_tables, int(cfg), ref, C.byref(d), which, cls, None, None, _ptr(members), _ptr(matrix))
             classes.append((members, matrix))
         out.append(classes)
     return tuple(out)
@@ -276,20 +334,14 @@ def host_ls_estimate(cfg, grid, width, height, explicit=None):
     (complex128 [Nsymb * Nc], after the AGC) for a width x height window; no GPU. explicit: as RxPhy's."""
     lib = load_library()
     g = np.ascontiguousarray(grid, np.complex128).ravel()
-    xp = None
-    if explicit:
-        seeds = any(k in explicit for k in ("pilot_seed", "scrambler_seed", "preamble_seed"))
-        xp = ExplicitParams(float(explicit.get("pilot_boost", 0.0)), int(explicit.get("ls_window", 0)), 1 if seeds else 0,
-                            int(explicit.get("pilot_seed", 0)), int(explicit.get("scrambler_seed", 0)), int(explicit.get("preamble_seed", 1)),
-                            int(explicit.get("Nc", 0)), int(explicit.get("Nfft", 0)), int(explicit.get("Dx", 0)), int(explicit.get("Dy", 0)),
-                            int(explicit.get("Nsymb", 0)))
-    ref = C.byref(xp) if xp is not None else None
+    ref = _explicit_ref(explicit)
+
+    def probe(count):
+        rc = lib.mgpu_host_ls_estimate(cfg, ref, int(width), int(height), _ptr(np.zeros_like(g)), _ptr(count))
+        if rc != 0:
+            raise MgpuError("mgpu_host_ls_estimate failed (%d)" % rc)
     # nPilots of the (possibly explicit) geometry: the entries a call on an all-zero grid writes
-    count = np.full(g.size, np.nan + 0j, np.complex128)
-    rc = lib.mgpu_host_ls_estimate(cfg, ref, int(width), int(height), _ptr(np.zeros_like(g)), _ptr(count))
-    if rc != 0:
-        raise MgpuError("mgpu_host_ls_estimate failed (%d)" % rc)
-    out = np.zeros(int(np.count_nonzero(~np.isnan(count.real))), np.complex128)
+    out = np.zeros(_written(probe, (g.size, np.complex128))[0], np.complex128)
     if lib.mgpu_host_ls_estimate(cfg, ref, int(width), int(height), _ptr(g), _ptr(out)) != 0:
         raise MgpuError("mgpu_host_ls_estimate failed")
     return out
@@ -308,31 +360,8 @@ class DemapperParams(C.Structure):
 
 def parse_demapper(text):
     """"maxlog", "csi", "nmap" or "nmap:band=2,smooth=1" (the tools' --demapper) -> (name, {dead_band, smooth} or None)"""
-    name, _, rest = str(text).partition(":")
-    if name not in DEMAPPERS or (rest and name != "nmap"):
-        raise ValueError("demapper: one of %s, nmap with :band=B,smooth=W" % ", ".join(DEMAPPERS))
-    if name != "nmap":
-        return name, None
-    prm = dict(NMAP_DEFAULT)
-    for item in filter(None, rest.split(",")):
-        key, _, value = item.partition("=")
-        if key == "band":
-            prm["dead_band"] = float(value)
-        elif key == "smooth":
-            prm["smooth"] = int(value)
-        else:
-            raise ValueError("demapper nmap: band=B and smooth=W are what it takes, not %r" % item)
-    return name, prm
-
-
-def _explicit_struct(explicit):
-    if not explicit:
-        return None
-    seeds = any(k in explicit for k in ("pilot_seed", "scrambler_seed", "preamble_seed"))
-    return ExplicitParams(float(explicit.get("pilot_boost", 0.0)), int(explicit.get("ls_window", 0)), 1 if seeds else 0,
-                          int(explicit.get("pilot_seed", 0)), int(explicit.get("scrambler_seed", 0)), int(explicit.get("preamble_seed", 1)),
-                          int(explicit.get("Nc", 0)), int(explicit.get("Nfft", 0)), int(explicit.get("Dx", 0)), int(explicit.get("Dy", 0)),
-                          int(explicit.get("Nsymb", 0)))
+    return _parse_spec(text, "demapper", DEMAPPERS, "nmap", NMAP_DEFAULT, {"band": ("dead_band", float), "smooth": ("smooth", int)},
+                       "one of %s, nmap with :band=B,smooth=W" % ", ".join(DEMAPPERS), "band=B and smooth=W are")
 
 
 def host_demap_csi(cfg, grid, H, explicit=None):
@@ -343,18 +372,13 @@ def host_demap_csi(cfg, grid, H, explicit=None):
     h = np.ascontiguousarray(H, np.complex128).ravel()
     if g.size != h.size:
         raise MgpuError("host_demap_csi: grid and H must have one entry per cell")
-    xp = _explicit_struct(explicit)
-    ref = C.byref(xp) if xp is not None else None
+    ref = _explicit_ref(explicit)
     # nBits of the (possibly explicit) geometry: the entries a call on an all-zero grid with H = 1 writes
-    count = np.full(g.size * 5, np.nan, np.float32)
-    rc = lib.mgpu_host_demap_csi(int(cfg), ref, _ptr(np.zeros_like(g)), _ptr(np.ones_like(g)), _ptr(count), None)
-    if rc != 0:
-        raise MgpuError("mgpu_host_demap_csi failed (%d)" % rc, rc)
-    llr = np.zeros(int(np.count_nonzero(~np.isnan(count))), np.float32)
+    nbits, = _written(lambda count: _checked(lib.mgpu_host_demap_csi, int(cfg), ref, _ptr(np.zeros_like(g)), _ptr(np.ones_like(g)), _ptr(count), None),
+                      (g.size * 5, np.float32))
+    llr = np.zeros(nbits, np.float32)
     sigma2 = C.c_double()
-    rc = lib.mgpu_host_demap_csi(int(cfg), ref, _ptr(g), _ptr(h), _ptr(llr), C.byref(sigma2))
-    if rc != 0:
-        raise MgpuError("mgpu_host_demap_csi failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_demap_csi, int(cfg), ref, _ptr(g), _ptr(h), _ptr(llr), C.byref(sigma2))
     return llr, float(sigma2.value)
 
 
@@ -366,21 +390,16 @@ def host_demap_nmap(cfg, grid, H, dead_band=2.0, smooth=1, explicit=None):
     h = np.ascontiguousarray(H, np.complex128).ravel()
     if g.size != h.size:
         raise MgpuError("host_demap_nmap: grid and H must have one entry per cell")
-    xp = _explicit_struct(explicit)
-    ref = C.byref(xp) if xp is not None else None
+    ref = _explicit_ref(explicit)
     prm = DemapperParams(float(dead_band), int(smooth))
     # nBits and Nsymb of the (possibly explicit) geometry: the entries a call on an all-zero grid with H = 1 writes
-    count, rows = np.full(g.size * 5, np.nan, np.float32), np.full(g.size, np.nan, np.float64)
-    rc = lib.mgpu_host_demap_nmap(int(cfg), ref, _ptr(np.zeros_like(g)), _ptr(np.ones_like(g)), C.byref(prm), C.sizeof(prm), _ptr(count), None, None, _ptr(rows))
-    if rc != 0:
-        raise MgpuError("mgpu_host_demap_nmap failed (%d)" % rc, rc)
-    llr = np.zeros(int(np.count_nonzero(~np.isnan(count))), np.float32)
-    fs = np.zeros(int(np.count_nonzero(~np.isnan(rows))), np.float64)
+    nbits, nsymb = _written(lambda count, rows: _checked(lib.mgpu_host_demap_nmap, int(cfg), ref, _ptr(np.zeros_like(g)), _ptr(np.ones_like(g)),
+                                                         C.byref(prm), C.sizeof(prm), _ptr(count), None, None, _ptr(rows)),
+                            (g.size * 5, np.float32), (g.size, np.float64))
+    llr, fs = np.zeros(nbits, np.float32), np.zeros(nsymb, np.float64)
     fc = np.zeros(g.size // fs.size, np.float64)
     sigma2 = C.c_double()
-    rc = lib.mgpu_host_demap_nmap(int(cfg), ref, _ptr(g), _ptr(h), C.byref(prm), C.sizeof(prm), _ptr(llr), C.byref(sigma2), _ptr(fc), _ptr(fs))
-    if rc != 0:
-        raise MgpuError("mgpu_host_demap_nmap failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_demap_nmap, int(cfg), ref, _ptr(g), _ptr(h), C.byref(prm), C.sizeof(prm), _ptr(llr), C.byref(sigma2), _ptr(fc), _ptr(fs))
     return llr, float(sigma2.value), fc, fs
 
 
@@ -395,25 +414,19 @@ def host_cfo_pilots(cfg, grid, explicit=None):
     by s steps: complex128 [Nsymb * Nc], the step in radians per symbol). explicit: as RxPhy's."""
     lib = load_library()
     g = np.ascontiguousarray(grid, np.complex128).ravel()
-    xp = _explicit_struct(explicit)
-    ref = C.byref(xp) if xp is not None else None
+    ref = _explicit_ref(explicit)
     # the cells of the (possibly explicit) geometry: the entries a call on an all-zero grid writes (at most 255 symbols of 50 carriers);
     # asked once per geometry
     key = (int(cfg), tuple(sorted((explicit or {}).items())))
     if key not in _CFO_CELLS:
-        count = np.full(255 * 50, np.nan + 0j, np.complex128)
-        rc = lib.mgpu_host_cfo_pilots(int(cfg), ref, _ptr(np.zeros_like(count)), _ptr(count), None)
-        if rc != 0:
-            raise MgpuError("mgpu_host_cfo_pilots failed (%d)" % rc, rc)
-        _CFO_CELLS[key] = int(np.count_nonzero(~np.isnan(count.real)))
+        _CFO_CELLS[key], = _written(lambda count: _checked(lib.mgpu_host_cfo_pilots, int(cfg), ref, _ptr(np.zeros_like(count)), _ptr(count), None),
+                                    (255 * 50, np.complex128))
     cells = _CFO_CELLS[key]
     if g.size != cells:
         raise MgpuError("host_cfo_pilots: the grid must have one entry per cell (%d)" % cells)
     out = np.zeros_like(g)
     step = C.c_double()
-    rc = lib.mgpu_host_cfo_pilots(int(cfg), ref, _ptr(g), _ptr(out), C.byref(step))
-    if rc != 0:
-        raise MgpuError("mgpu_host_cfo_pilots failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_cfo_pilots, int(cfg), ref, _ptr(g), _ptr(out), C.byref(step))
     return out, float(step.value)
 
 
@@ -430,30 +443,14 @@ class BlankerParams(C.Structure):
 
 
 def _blanker_params(threshold=None, guard=None, max_share=None):
-    d = BLANKER_DEFAULT
-    return BlankerParams(float(d["threshold"] if threshold is None else threshold), int(d["guard"] if guard is None else guard),
-                         float(d["max_share"] if max_share is None else max_share))
+    return _params(BlankerParams, BLANKER_DEFAULT, (threshold, guard, max_share))
 
 
 def parse_blanker(text):
     """"off", "median" or "median:thr=24,guard=4,share=0.125" (the tools' --blanker) -> (name, {threshold, guard, max_share} or None)"""
-    name, _, rest = str(text).partition(":")
-    if name not in BLANKER_MODES or (rest and name != "median"):
-        raise ValueError("blanker: off, or median with :thr=T,guard=G,share=S")
-    if name != "median":
-        return name, None
-    prm = dict(BLANKER_DEFAULT)
-    for item in filter(None, rest.split(",")):
-        key, _, value = item.partition("=")
-        if key == "thr":
-            prm["threshold"] = float(value)
-        elif key == "guard":
-            prm["guard"] = int(value)
-        elif key == "share":
-            prm["max_share"] = float(value)
-        else:
-            raise ValueError("blanker median: thr=T, guard=G and share=S are what it takes, not %r" % item)
-    return name, prm
+    return _parse_spec(text, "blanker", BLANKER_MODES, "median", BLANKER_DEFAULT,
+                       {"thr": ("threshold", float), "guard": ("guard", int), "share": ("max_share", float)},
+                       "off, or median with :thr=T,guard=G,share=S", "thr=T, guard=G and share=S are")
 
 
 def host_blank(cfg, frame, explicit=None, **params):
@@ -461,7 +458,6 @@ def host_blank(cfg, frame, explicit=None, **params):
     params: threshold, guard, max_share (the defaults where left out). explicit: as RxPhy's."""
     lib = load_library()
     x = np.ascontiguousarray(frame, np.complex128).ravel()
-    xp = _explicit_struct(explicit)
     # frame_samples of the (possibly explicit) geometry: an explicit Nsymb symbols of the mode's length, else the mode's own
     info = Info()
     if lib.mgpu_host_mode_info(int(cfg), 0, C.byref(info)) != 0:
@@ -471,9 +467,7 @@ def host_blank(cfg, frame, explicit=None, **params):
         raise MgpuError("host_blank: the frame must have frame_samples (%d) samples" % n, 1)
     prm = _blanker_params(**params)
     out, rep = np.zeros_like(x), np.zeros(1, BLANKER_REPORT_DTYPE)
-    rc = lib.mgpu_host_blank(int(cfg), C.byref(xp) if xp is not None else None, C.byref(prm), _ptr(x), _ptr(out), _ptr(rep))
-    if rc != 0:
-        raise MgpuError("mgpu_host_blank failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_blank, int(cfg), _explicit_ref(explicit), C.byref(prm), _ptr(x), _ptr(out), _ptr(rep))
     return out, {"marked": int(rep["marked"][0]), "blanked": int(rep["blanked"][0])}
 
 
@@ -491,30 +485,14 @@ class ExcisorParams(C.Structure):
 
 
 def _excisor_params(threshold=None, guard=None, max_bins=None):
-    d = EXCISOR_DEFAULT
-    return ExcisorParams(float(d["threshold"] if threshold is None else threshold), int(d["guard"] if guard is None else guard),
-                         int(d["max_bins"] if max_bins is None else max_bins))
+    return _params(ExcisorParams, EXCISOR_DEFAULT, (threshold, guard, max_bins))
 
 
 def parse_excisor(text):
     """"off", "welch" or "welch:thr=12,guard=1,bins=16" (the tools' --excisor) -> (name, {threshold, guard, max_bins} or None)"""
-    name, _, rest = str(text).partition(":")
-    if name not in EXCISOR_MODES or (rest and name != "welch"):
-        raise ValueError("excisor: off, or welch with :thr=T,guard=G,bins=B")
-    if name != "welch":
-        return name, None
-    prm = dict(EXCISOR_DEFAULT)
-    for item in filter(None, rest.split(",")):
-        key, _, value = item.partition("=")
-        if key == "thr":
-            prm["threshold"] = float(value)
-        elif key == "guard":
-            prm["guard"] = int(value)
-        elif key == "bins":
-            prm["max_bins"] = int(value)
-        else:
-            raise ValueError("excisor welch: thr=T, guard=G and bins=B are what it takes, not %r" % item)
-    return name, prm
+    return _parse_spec(text, "excisor", EXCISOR_MODES, "welch", EXCISOR_DEFAULT,
+                       {"thr": ("threshold", float), "guard": ("guard", int), "bins": ("max_bins", int)},
+                       "off, or welch with :thr=T,guard=G,bins=B", "thr=T, guard=G and bins=B are")
 
 
 def host_excise(window, carrier_hz, **params):
@@ -524,9 +502,7 @@ def host_excise(window, carrier_hz, **params):
     x = np.ascontiguousarray(window, np.float64).ravel()
     prm = _excisor_params(**params)
     out, rep = np.zeros_like(x), np.zeros(1, EXCISOR_REPORT_DTYPE)
-    rc = lib.mgpu_host_excise(C.byref(prm), float(carrier_hz), _ptr(x), int(x.size), _ptr(out), _ptr(rep))
-    if rc != 0:
-        raise MgpuError("mgpu_host_excise failed (%d)" % rc, rc)
+    _checked(lib.mgpu_host_excise, C.byref(prm), float(carrier_hz), _ptr(x), int(x.size), _ptr(out), _ptr(rep))
     return out, {name: rep[name][0].item() for name in EXCISOR_REPORT_DTYPE.names}
 
 
@@ -561,9 +537,7 @@ def host_llr_combine(llr, D=None, groups=None):
     l = np.ascontiguousarray(llr, np.float32).reshape(-1, 1600)
     D, first, member, G, rows = _group_args(l.shape[0], D, groups)
     out = np.zeros((rows, 1600), np.float32)
-    rc = lib.mgpu_host_llr_combine(_ptr(l), l.shape[0], D, _ptr(first), _ptr(member), G, _ptr(out))
-    if rc != 0:
-        raise MgpuError("mgpu_host_llr_combine refused the groups (%d)" % rc, rc)
+    _checked(lib.mgpu_host_llr_combine, _ptr(l), l.shape[0], D, _ptr(first), _ptr(member), G, _ptr(out), what="refused the groups")
     return out
 
 
@@ -684,8 +658,9 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class RxPhy:
+class RxPhy(_Handle):
     """One GPU receive context for one Mercury mode (``load_configuration(cfg)`` equivalent)."""
+    _destroy = "mgpu_destroy"
 
     def __init__(self, cfg, max_iters=50, decoder=DEC_SPA, agc=1, variance_source=1, device=0,
                  max_batch=4096, minsum_alpha=0.0, mfsk_ctrl_mode=False, test_puncture_nbits=0, explicit=None):
@@ -695,12 +670,7 @@ class RxPhy:
         self.h = C.c_void_p()
         c = Config(cfg, max_iters, decoder, agc, variance_source, device, max_batch, minsum_alpha, 1 if mfsk_ctrl_mode else 0, test_puncture_nbits)
         if explicit:
-            seeds = any(k in explicit for k in ("pilot_seed", "scrambler_seed", "preamble_seed"))
-            xp = ExplicitParams(float(explicit.get("pilot_boost", 0.0)), int(explicit.get("ls_window", 0)), 1 if seeds else 0,
-                                int(explicit.get("pilot_seed", 0)), int(explicit.get("scrambler_seed", 0)), int(explicit.get("preamble_seed", 1)),
-                                int(explicit.get("Nc", 0)), int(explicit.get("Nfft", 0)), int(explicit.get("Dx", 0)), int(explicit.get("Dy", 0)),
-                                int(explicit.get("Nsymb", 0)))
-            rc = self.lib.mgpu_create_explicit(C.byref(c), C.byref(xp), C.byref(self.h))
+            rc = self.lib.mgpu_create_explicit(C.byref(c), _explicit_ref(explicit), C.byref(self.h))
         else:
             rc = self.lib.mgpu_create(C.byref(c), C.byref(self.h))
         if rc != 0:
@@ -718,17 +688,6 @@ class RxPhy:
     def _ck(self, rc):
         if rc != 0:
             raise MgpuError("mgpu error %d: %s" % (rc, self.lib.mgpu_last_error(self.h).decode()), rc)
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.mgpu_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- estimator ladder (include/mercury_estimator.h) ----------------------------------------
     def set_estimator_ladder(self, rungs):
@@ -1418,8 +1377,9 @@ def pool_shard(F, G, g):
     return a.value, n.value
 
 
-class RxPool:
+class RxPool(_Handle):
     """One context + one host worker thread per device; a call is split into contiguous frame ranges (mgpu_pool_*)."""
+    _destroy = "mgpu_pool_destroy"
 
     def __init__(self, cfg, devices, max_iters=50, decoder=DEC_SPA, agc=1, variance_source=1, max_batch=4096, minsum_alpha=0.0,
                  mfsk_ctrl_mode=False):
@@ -1448,17 +1408,6 @@ class RxPool:
     def _ck(self, rc):
         if rc != 0:
             raise MgpuError("mgpu pool error %d: %s" % (rc, self.lib.mgpu_pool_last_error(self.h).decode()))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.mgpu_pool_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def counters(self):
         c = PoolCounters()
@@ -1631,10 +1580,11 @@ def host_capture_process(geometry, state, stats=None, link=None):
     return bool(rc)
 
 
-class RxCapture:
+class RxCapture(_Handle):
     """S continuous captures on one RxPhy context: the reference's capture-prep thread and RX_SHM_process_main, batched on the GPU
     (include/mercury_capture.h). Samples go in as [S, H * P] arrays of float64 / int32 / int16 / float32 (numpy, or torch tensors on the
     context's device, read in place)."""
+    _destroy = "mgpu_capture_destroy"
 
     def __init__(self, rx, S, carrier_hz, trials_max=2, use_last_good_time_sync=1, use_last_good_freq_offset=1, coarse_freq_sync=0,
                  initial_windows=None, max_hops=0, ladder=None):
@@ -1653,17 +1603,6 @@ class RxCapture:
         self.P = self.geometry.symbol_period
         self.window_samples = self.geometry.buffer_nsymb * self.P
         self.payload_stride = rx.payload_stride
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.mgpu_capture_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _samples(self, samples):
         """-> (pointer, format, H, keep-alive)"""
@@ -1756,10 +1695,11 @@ def host_hf_stream_noise(seed, signal, position, n):
     return out
 
 
-class HfStream:
+class HfStream(_Handle):
     """The Watterson channel on S real signals that are fed in chunks (mgpu_hf_stream_*): apply() takes float64 [S, n] (numpy, or a torch
     tensor on the context's device, then `out` must be one too), n a multiple of 64, and returns the next n output samples of every
     signal, delayed by `latency` samples."""
+    _destroy = "mgpu_hf_stream_destroy"
 
     def __init__(self, rx, S, ch, seed, realisation0=0, fs=48000.0):
         self.rx, self.lib, self.S = rx, rx.lib, S
@@ -1767,17 +1707,6 @@ class HfStream:
         lib = self.lib
         rx._ck(lib.mgpu_hf_stream_create(rx.h, C.byref(_hf(ch)), fs, S, seed, realisation0, C.byref(self.h)))
         self.latency = int(lib.mgpu_hf_stream_latency(self.h))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.mgpu_hf_stream_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def seek(self, position):
         self.rx._ck(self.lib.mgpu_hf_stream_seek(self.h, position))
@@ -1852,7 +1781,7 @@ class _BorrowedCapture(RxCapture):
         self.h = C.c_void_p()
 
 
-class LinkSim:
+class LinkSim(_Handle):
     """S simplex links (transmitter -> streaming HF channel -> noise -> the capture receive loop) on one RxPhy context
     (include/mercury_linksim.h). config: linksim_config(...); esn0_db: None (no noise), a number or [S]."""
 
@@ -1874,17 +1803,9 @@ class LinkSim:
         self.slot = self.frame_samples + config.gap_hops * self.P
         self.payload_stride = rx.payload_stride
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.capture.close()
-            self.lib.mgpu_linksim_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        self.capture.close()
+        self.lib.mgpu_linksim_destroy(self.h)
 
     def run(self, H, want_samples=False, max_events=None):
         """H more hops for every link -> list of (link, hop since the start, stats, payload bytes) for the decoded frames; with
@@ -2008,10 +1929,11 @@ def host_chan_process(D, channels, iq, position=0, taps=None, audio_centre_hz=14
     return out
 
 
-class Channelizer:
+class Channelizer(_Handle):
     """One wideband IQ stream at 48000 * D into S 48 kHz sideband audio streams on an RxPhy context (include/mercury_channelizer.h).
     channels: [(offset_hz, sideband, gain), ...] as chan_channels takes them. process() takes complex64 / complex128 / int16 [..., 2]
     samples (numpy, or a torch tensor on the context's device), a multiple of D of them, and returns float64 [S, n_in // D]."""
+    _destroy = "mgpu_chan_destroy"
 
     def __init__(self, rx, D, channels, taps=None, audio_centre_hz=1472, max_out=0):
         self.rx, self.lib, self.D = rx, rx.lib, int(D)
@@ -2021,17 +1943,6 @@ class Channelizer:
         self.h = C.c_void_p()
         rx._ck(self.lib.mgpu_chan_create(rx.h, C.byref(self.config), self._chs, C.byref(self.h)))
         self.latency = int(self.lib.mgpu_chan_latency(self.h))
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.mgpu_chan_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def seek(self, position):
         self.rx._ck(self.lib.mgpu_chan_seek(self.h, int(position)))
@@ -2156,10 +2067,11 @@ def host_resamp_process(fin, fout, x, position=0, components=1, tp=None, taps=No
     return _resamp_result(out, n.value, components)
 
 
-class Resampler:
+class Resampler(_Handle):
     """S streams at fin into S streams at fout on an RxPhy context (include/ext/mercury_resampler.h). process() takes [S, n_in] samples,
     real in a capture format (components 1) or IQ as Channelizer.process takes it (components 2), numpy or a torch tensor on the
     context's device, cut anywhere, and returns float64 / complex128 [S, n_out]."""
+    _destroy = "mgpu_resamp_destroy"
 
     def __init__(self, rx, fin, fout=48000, S=1, components=1, tp=None, taps=None, max_in=None):
         self.rx, self.lib, self.fin, self.fout, self.S, self.components = rx, rx.lib, int(fin), int(fout), int(S), int(components)
@@ -2168,17 +2080,6 @@ class Resampler:
         rx._ck(self.lib.mgpu_resamp_create(rx.h, C.byref(self.config), C.byref(self.h)))
         st = self.info()
         self.L, self.M, self.tp, self.max_in, self.max_out, self.tile, self.delay = st.L, st.M, st.tp, st.max_in, st.max_out, st.tile, st.delay
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.mgpu_resamp_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def info(self):
         st = ResampStatus()
