@@ -37,6 +37,7 @@
 #define HF_NOISE_STREAM 5u                      // Philox stream id of the streaming channel's noise
 #define HF_LATENCY 256                          // streaming form: output delay in samples (>= HF_HILBERT_HALF, a multiple of HF_BLK)
 #define HF_MAX_FS 192000.0
+#define HF_MAX_DELAY int(MGPU_HF_MAX_DELAY_MS * HF_MAX_FS / 1000.0)     // 1920 samples
 
 namespace {
 
@@ -354,6 +355,18 @@ void launch(int mode, const HfPlan& pl, HfIo io, int W, hipStream_t s) {
     const unsigned tiles = unsigned((io.n + HF_TILE - 1) / HF_TILE);
     auto* k = mode == HF_REAL ? mgpu_hf_channel_real_kernel : mode == HF_COMPLEX ? mgpu_hf_channel_complex_kernel
             : mode == HF_PASSBAND ? mgpu_hf_passband_kernel : mode == HF_BASEBAND ? mgpu_hf_baseband_kernel : mgpu_hf_stream_kernel;
+    // Above 48 kHz a 10 ms path's halo takes the real forms' carve past the default dynamic-LDS limit (69,488 B at 96 kHz, 92,528 B at
+    // HF_MAX_FS; the complex forms stop at 65,536 B): raise the kernel's limit as create.hip does for the front-end, to the largest carve
+    // make_plan admits, so that launches from two host threads cannot lower it under each other. Nothing at or below 48 kHz (57,968 B
+    // at the most) comes here.
+    constexpr size_t kDefaultLds = 64 * 1024;
+    constexpr size_t kMaxLds = size_t(HF_NBLK) * 32 * 16 + 2 * 32 * 8 * 16 + 2 * MGPU_HF_MAX_PATHS * 32 * 8 + size_t(HF_TILE + HF_MAX_DELAY) * 16 +
+                               size_t(HF_TILE + HF_MAX_DELAY + 2 * HF_HILBERT_HALF) * 8;       // lds_bytes() of a real form at dmax = HF_MAX_DELAY
+    static_assert(kMaxLds == 92528, "the carve DESIGN.md §6.2 and include/mercury_channel.h's 192 kHz stand on");
+    if (lds > kDefaultLds) {
+        need(lds <= kMaxLds, "the channel's LDS carve exceeds the kernel's limit");
+        HIPCK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(kMaxLds)));
+    }
     for (int w0 = 0; w0 < W; w0 += 65535) {
         io.w0 = w0;
         hipLaunchKernelGGL(k, dim3(tiles, unsigned(std::min(W - w0, 65535))), dim3(HF_THREADS), lds, s, pl, io);

@@ -4,29 +4,8 @@ entry points), and the channel end to end through the real receiver."""
 import numpy as np
 import pytest
 
+from hf_channel_ref import _numpy_channel
 from oraclelib import CARRIER
-
-
-def _numpy_channel(x, ch, seed, r0, fs, t0=0):
-    """y = Re / (.)(e^{j 2 pi df t} sum_k g_k(t) a[i - d_k]), a = x + j Hx (real x) or x, from the host taps and the host Hilbert FIR."""
-    from mercury_amd import host_hf_channel_taps, host_hilbert_taps
-    W, n = x.shape
-    real = not np.iscomplexobj(x)
-    h = host_hilbert_taps()
-    M = (h.size - 1) // 2
-    t = (t0 + np.arange(n)) / fs
-    rot = np.exp(2j * np.pi * ch.freq_offset_hz * t)
-    out = np.zeros_like(x)
-    for w in range(W):
-        a = x[w] + 1j * np.convolve(x[w], h)[M: M + n] if real else x[w]
-        g = host_hf_channel_taps(ch, fs, seed, r0 + w, n, t0=t0)
-        y = np.zeros(n, np.complex128)
-        for k in range(ch.n_paths):
-            d = int(round(ch.delay_ms[k] * fs / 1000.0))
-            y[d:] += g[k, d:] * a[: n - d]
-        y *= rot
-        out[w] = y.real if real else y
-    return out
 
 
 @pytest.mark.gpu
