@@ -16,7 +16,8 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              CHANNELIZER_SYMBOLS, Channelizer, ChanChannel, ChanConfig, chan_channels, chan_config, host_chan_design, host_chan_tables, host_chan_process,
                              EXCISOR_SYMBOLS, EXCISOR_MODES, EXCISOR_DEFAULT, EXCISOR_REPORT_DTYPE, ExcisorParams, host_excise, parse_excisor,
                              RESAMPLER_SYMBOLS, Resampler, ResampConfig, ResampStatus, resamp_config, resamp_ratio, host_resamp_design, host_resamp_process,
-                             host_resamp_count)
+                             host_resamp_count,
+                             SYNTH_SYMBOLS, Synthesizer, SynthConfig, SynthState, synth_config, host_synth_process, host_synth_tables)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -30,4 +31,5 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "CHANNELIZER_SYMBOLS", "Channelizer", "ChanChannel", "ChanConfig", "chan_channels", "chan_config", "host_chan_design", "host_chan_tables", "host_chan_process",
            "EXCISOR_SYMBOLS", "EXCISOR_MODES", "EXCISOR_DEFAULT", "EXCISOR_REPORT_DTYPE", "ExcisorParams", "host_excise", "parse_excisor",
            "RESAMPLER_SYMBOLS", "Resampler", "ResampConfig", "ResampStatus", "resamp_config", "resamp_ratio", "host_resamp_design", "host_resamp_process",
-           "host_resamp_count"]
+           "host_resamp_count",
+           "SYNTH_SYMBOLS", "Synthesizer", "SynthConfig", "SynthState", "synth_config", "host_synth_process", "host_synth_tables"]

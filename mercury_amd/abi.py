@@ -126,6 +126,11 @@ EXTENSIONS = {
         "mgpu_host_resamp_design": "i:iiiddpp", "mgpu_host_resamp_default_taps": "i:iipp", "mgpu_host_resamp_process": "i:ppiiupzp",
         "mgpu_host_resamp_count": "i:iiuip",
     },
+    "ext/mercury_synth.h": {
+        "mgpu_synth_create": "i:pppp", "mgpu_synth_destroy": "i:p", "mgpu_synth_latency": "i:p", "mgpu_synth_seek": "i:pu",
+        "mgpu_synth_retune": "i:pip", "mgpu_synth_process": "i:ppziip", "mgpu_synth_process_dev": "i:ppziipp", "mgpu_synth_status": "i:pp",
+        "mgpu_host_synth_tables": "i:pppppp", "mgpu_host_synth_process": "i:pppziuipp",
+    },
 }
 
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of

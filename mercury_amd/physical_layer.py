@@ -2106,3 +2106,133 @@ class Resampler(_Handle):
         host = np.zeros((self.S, stride * self.components))
         self.rx._ck(self.lib.mgpu_resamp_process(self.h, ptr, f, n_in, _ptr(host), stride, C.byref(n)))
         return _resamp_result(host, n.value, self.components)
+
+
+# ---- wideband synthesiser (include/ext/mercury_synth.h) -----------------------------------------------------------------
+SYNTH_SYMBOLS = names("ext/mercury_synth.h")
+_IQ_FORMATS = {"cs16": IQ_CS16, "cf32": IQ_CF32, "cf64": IQ_CF64}
+
+
+class SynthConfig(C.Structure):         # mgpu_synth_config
+    _fields_ = [("struct_size", C.c_int), ("D", C.c_int), ("S", C.c_int), ("audio_centre_hz", C.c_int), ("ntaps", C.c_int),
+                ("taps", C.c_void_p), ("max_in", C.c_int)]
+
+
+class SynthState(C.Structure):          # mgpu_synth_state
+    _fields_ = [("position", C.c_uint64), ("clamped", C.c_uint64), ("D", C.c_int), ("S", C.c_int), ("tp", C.c_int), ("max_in", C.c_int),
+                ("tile", C.c_int), ("phases", C.c_int)]
+
+
+def synth_config(D, S, taps=None, audio_centre_hz=1472, max_in=0):
+    """-> (mgpu_synth_config, keep-alive of its taps)"""
+    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
+    k = SynthConfig(C.sizeof(SynthConfig), int(D), int(S), int(audio_centre_hz), 0 if h is None else h.size,
+                    None if h is None else h.ctypes.data, int(max_in))
+    return k, h
+
+
+def _iq_format(fmt):
+    f = _IQ_FORMATS.get(fmt.lower()) if isinstance(fmt, str) else fmt
+    if f not in (IQ_CS16, IQ_CF32, IQ_CF64):
+        raise MgpuError("IQ format: 'cs16', 'cf32' or 'cf64', not %r" % (fmt,))
+    return f
+
+
+def _iq_empty(fmt, n):
+    """a numpy array for n IQ samples of MGPU_IQ_* fmt: int16 [n, 2], complex64 [n] or complex128 [n]"""
+    return np.zeros((n, 2), np.int16) if fmt == IQ_CS16 else np.zeros(n, np.complex64 if fmt == IQ_CF32 else np.complex128)
+
+
+def _synth_audio(audio, S):
+    """-> (pointer, row stride in samples, samples per channel, keep-alive): float64 audio [S, n_in] (or [n_in] for one channel), a numpy
+    array or a torch tensor (read in place; its rows may be further apart than n_in)"""
+    if hasattr(audio, "data_ptr"):
+        import torch
+        a = audio.reshape(1, -1) if audio.dim() == 1 else audio
+        if a.dtype != torch.float64 or a.dim() != 2 or a.shape[0] != S or a.stride(1) != 1 or (S > 1 and a.stride(0) < a.shape[1]):
+            raise MgpuError("device audio: a float64 tensor [S, n_in] with contiguous rows, S = %d" % S)
+        return a.data_ptr(), (a.stride(0) if S > 1 else a.shape[1]), a.shape[1], a
+    a = np.ascontiguousarray(audio, np.float64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    if a.ndim != 2 or a.shape[0] != S:
+        raise MgpuError("audio must be [S, n_in] with S = %d" % S)
+    return _ptr(a), a.shape[1], a.shape[1], a
+
+
+def host_synth_tables(D, channel, taps=None, audio_centre_hz=1472, want_phasor=False):
+    """one channel's tables as the device reads them: (q complex128 [T], the tap table of its sideband; P complex128 [D]; G) and, with
+    want_phasor, W complex128 [48000]"""
+    k, keep = synth_config(D, 1, taps, audio_centre_hz)
+    T = keep.size if keep is not None else CHAN_DEFAULT_TP * max(int(D), 0) + 1
+    q, P, G = np.zeros(T, np.complex128), np.zeros(max(int(D), 1), np.complex128), C.c_double()
+    W = np.zeros(CHAN_PHASOR_LEN, np.complex128) if want_phasor else None
+    if load_library().mgpu_host_synth_tables(C.byref(k), chan_channels([channel]), _ptr(q), _ptr(P), C.byref(G), _ptr(W)) != 0:
+        raise MgpuError("mgpu_host_synth_tables: bad argument", 1)
+    return (q, P, G.value, W) if want_phasor else (q, P, G.value)
+
+
+def host_synth_process(D, channels, audio, position=0, fmt="cf64", taps=None, audio_centre_hz=1472, struct_size=None, want_clamped=False):
+    """the twin (mgpu_host_synth_process): a fresh synthesiser seeked to `position` and fed audio [S, n_in] whole -> n_in * D IQ samples
+    (complex128, complex64 or int16 [.., 2]); with want_clamped also the CS16 components clamped"""
+    chs = chan_channels(channels)
+    k, _keep = synth_config(D, len(chs), taps, audio_centre_hz)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    f = _iq_format(fmt)
+    ptr, stride, n_in, _a = _synth_audio(audio, len(chs))
+    out = _iq_empty(f, max(n_in * max(int(D), 1), 1))
+    clamped = C.c_uint64()
+    if load_library().mgpu_host_synth_process(C.byref(k), chs, ptr, stride, n_in, int(position), f, _ptr(out), C.byref(clamped)) != 0:
+        raise MgpuError("mgpu_host_synth_process: bad argument", 1)
+    return (out, clamped.value) if want_clamped else out
+
+
+class Synthesizer(_Handle):
+    """S 48 kHz transmit audio streams into one wideband IQ stream at 48000 * D on an RxPhy context (include/ext/mercury_synth.h), the
+    mirror of Channelizer. channels: [(offset_hz, sideband, gain), ...] as chan_channels takes them. process() takes float64 audio
+    [S, n_in] (numpy, or a torch tensor on the context's device such as the one transmit_byte_dev leaves there) and returns n_in * D IQ
+    samples."""
+    _destroy = "mgpu_synth_destroy"
+
+    def __init__(self, rx, D, channels, taps=None, audio_centre_hz=1472, max_in=0):
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
+        self._chs = chan_channels(channels)
+        self.S = len(self._chs)
+        self.config, self._taps = synth_config(D, self.S, taps, audio_centre_hz, max_in)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_synth_create(rx.h, C.byref(self.config), self._chs, C.byref(self.h)))
+        self.latency = int(self.lib.mgpu_synth_latency(self.h))
+        st = self.status()
+        self.tp, self.max_in, self.tile, self.phases = st.tp, st.max_in, st.tile, st.phases
+
+    def status(self):
+        """mgpu_synth_state: position, clamped (CS16 components since the last seek), D, S, tp, max_in, tile, phases. Waits for the device."""
+        st = SynthState()
+        self.rx._ck(self.lib.mgpu_synth_status(self.h, C.byref(st)))
+        return st
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_synth_seek(self.h, int(position)))
+
+    def retune(self, s, channel):
+        self.rx._ck(self.lib.mgpu_synth_retune(self.h, int(s), chan_channels([channel])))
+
+    def process(self, audio, fmt="cf64", out=None, stream=None):
+        """out None: a new numpy array of n_in * D IQ samples in fmt ('cf64' complex128, 'cf32' complex64, 'cs16' int16 [.., 2]); a
+        blocking call. out a torch tensor on the device (complex128 / complex64 [n_in * D] or int16 [n_in * D, 2], matching fmt), with
+        `audio` one too: mgpu_synth_process_dev, asynchronous on `stream` (None: the context's stream)."""
+        f = _iq_format(fmt)
+        ptr, stride, n_in, _keep = _synth_audio(audio, self.S)
+        if out is not None and hasattr(out, "data_ptr"):
+            optr, ofmt, n_out, _o = _iq(out)
+            if not hasattr(audio, "data_ptr") or ofmt != f or n_out != n_in * self.D:
+                raise MgpuError("device output: device input and a contiguous tensor of n_in * D IQ samples in the format asked for")
+            self.rx._ck(self.lib.mgpu_synth_process_dev(self.h, ptr, stride, n_in, f, optr, stream))
+            return out
+        if out is None:
+            out = _iq_empty(f, max(n_in * self.D, 1))
+        optr, ofmt, n_out, _o = _iq(out)
+        if ofmt != f or n_out < n_in * self.D or not out.flags.c_contiguous:
+            raise MgpuError("out: a contiguous array of n_in * D IQ samples in the format asked for")
+        self.rx._ck(self.lib.mgpu_synth_process(self.h, ptr, stride, n_in, f, optr))
+        return out
