@@ -223,8 +223,10 @@ struct mgpu_capture {
     }
 };
 
-mgpu_ctx* capture_context(mgpu_capture* cap) { return cap->c; }
 int capture_streams(mgpu_capture* cap) { return cap->S; }
+bool capture_pairs(mgpu_capture* cap, mgpu_ctx* c, int S, mgpu_capture_geometry* g) {
+    return mgpu_capture_geometry_get(cap, g) == MGPU_OK && cap->S == S && cap->c == c;
+}
 
 namespace {
 void check_feed_args(mgpu_capture* k, const void* samples, int fmt, int H) {
@@ -316,7 +318,7 @@ int mgpu_capture_run(mgpu_capture* k, const void* samples, int fmt, int H, mgpu_
     if (!k) return MGPU_ERR_ARG;
     return guard(k->c, [&] {
         check_feed_args(k, samples, fmt, H);
-        need(n_events != nullptr && max_events >= 0 && (max_events == 0 || events), "bad argument (n_events, events)");
+        check_event_args(events, max_events, n_events);
         const bool dev = is_device_memory(samples);
         const int stride = k->c->tab.payload_stride;
         int n = 0;

@@ -39,6 +39,12 @@ const char* channel_error(int D, int a_c, const mgpu_chan_channel* ch) {
     return nullptr;
 }
 
+const char* plan_error(int D, int a_c, int S, const mgpu_chan_channel* channels) {
+    const char* bad = channels ? nullptr : "no channels";
+    for (int s = 0; !bad && s < S; ++s) bad = channel_error(D, a_c, channels + s);
+    return bad;
+}
+
 namespace {
 
 // modified Bessel function I0 by its power series (terms fall below 1e-17 of the sum within 40 for x <= 20)
@@ -133,9 +139,7 @@ int mgpu_host_chan_tables(const mgpu_chan_config* k, const mgpu_chan_channel* ch
 
 int mgpu_host_chan_process(const mgpu_chan_config* k, const mgpu_chan_channel* channels, const void* iq, int format, int n_in,
                            uint64_t position, double* out) {
-    if (config_error(k, true) || !channels || !iq || !out) return MGPU_ERR_ARG;
-    for (int s = 0; s < k->S; ++s)
-        if (channel_error(k->D, k->audio_centre_hz, channels + s)) return MGPU_ERR_ARG;
+    if (config_error(k, true) || plan_error(k->D, k->audio_centre_hz, k->S, channels) || !iq || !out) return MGPU_ERR_ARG;
     const int D = k->D;
     const int e = mgpu_fmt::element(2, format);
     if (n_in < D || n_in % D || position > (1ULL << 62) || e == mgpu_fmt::kNone) return MGPU_ERR_ARG;

@@ -18,6 +18,8 @@ inline long long floor_mod(long long a, long long m) {
 const char* config_error(const mgpu_chan_config* k, bool need_s);
 // why the channel is refused at decimation D around audio centre a_c, or null
 const char* channel_error(int D, int a_c, const mgpu_chan_channel* ch);
+// why a plan of S channels is refused, or null: "no channels", or the first refused channel's reason
+const char* plan_error(int D, int a_c, int S, const mgpu_chan_channel* channels);
 // the prototype of a checked configuration: its own taps, or the default design
 std::vector<double> prototype(const mgpu_chan_config* k);
 // A windowed-sinc low-pass of T (odd) taps: cutoff fc as a fraction of the Nyquist frequency, Kaiser window with

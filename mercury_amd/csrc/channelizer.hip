@@ -19,11 +19,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <vector>
 
-#include "ctx.hpp"
-#include "chan_tables.hpp"
+#include "stream_stage.hpp"
 
 using namespace mgpu_chan_detail;
 
@@ -170,10 +168,8 @@ struct mgpu_chan {
     int S = 0, D = 0, T = 0, L = 0, max_out = 0, R = 1, NB = 0, ncols = 0, nblocks = 0;
     size_t lds = 0;
     uint64_t pos = 0;
-    bool fresh = true;                            // no history: the next line starts with zeros
-    int cur = 0;                                  // the line buffer the next call writes
-    size_t kept = 0;                              // where the history starts in the other one
-    DevArray<double2> d_line[2];                  // [T - 1 + max_out * D]
+    History<double2> line;                        // [T - 1 + max_out * D] the input line; the history is the last T - 1 samples of the old one,
+    size_t kept = 0;                              // which start here
     DevArray<double2> d_g, d_W;                   // [S][T], [48000]
     DevArray<ChanRow> d_rows;                     // [S]
     DevArray<char> d_stage;                       // host input's landing area (ctx.hpp staged_on_device)
@@ -199,13 +195,13 @@ struct mgpu_chan {
     // one call on device memory: the next n_in / D outputs of every channel into d_o [S][n_in / D]
     void run(const void* d_iq, int format, int n_in, double* d_o, hipStream_t st) {
         const int N = n_in / D, hist = T - 1;
-        double2* line = d_line[cur];
+        double2* cur = line.next();
         const size_t total = size_t(hist) + size_t(n_in);
         hipLaunchKernelGGL(mgpu_chan_assemble_kernel, dim3(unsigned(std::min<size_t>((total + 255) / 256, 2048))), dim3(256), 0, st,
-                           fresh ? nullptr : static_cast<const double2*>(d_line[cur ^ 1]), kept, hist, d_iq, format, n_in, line);
+                           line.old(), kept, hist, d_iq, format, n_in, cur);
         HIPCK(hipGetLastError());
         FirArgs a{};
-        a.cur = line; a.g = d_g; a.W = d_W; a.rows = d_rows; a.out = d_o; a.out_stride = size_t(N);
+        a.cur = cur; a.g = d_g; a.W = d_W; a.rows = d_rows; a.out = d_o; a.out_stride = size_t(N);
         a.total = int(total); a.S = S; a.N = N; a.D = D; a.T = T; a.NB = NB; a.ncols = ncols; a.nblocks = nblocks;
         a.nm = unsigned(floor_mod((long long)(pos % MGPU_CHAN_PHASOR_LEN) - L, MGPU_CHAN_PHASOR_LEN));
         const unsigned gx = unsigned((N + 64 * R - 1) / (64 * R));
@@ -219,8 +215,7 @@ struct mgpu_chan {
             HIPCK(hipGetLastError());
         }
         kept = size_t(n_in);                      // the line's last T - 1 samples are the next call's history
-        cur ^= 1;
-        fresh = false;
+        line.advance();
         pos += uint64_t(N);
     }
 
@@ -235,24 +230,10 @@ struct mgpu_chan {
 extern "C" {
 
 int mgpu_chan_create(mgpu_ctx* c, const mgpu_chan_config* kc, const mgpu_chan_channel* channels, mgpu_chan** out) {
-    if (!out) return MGPU_ERR_ARG;
-    *out = nullptr;
-    // refused before any device work, with or without a context
     const char* bad = config_error(kc, true);
-    if (!bad && !channels) bad = "no channels";
-    for (int s = 0; !bad && s < kc->S; ++s) bad = channel_error(kc->D, kc->audio_centre_hz, channels + s);
-    if (bad) {
-        if (c) c->err = std::string("mgpu_chan_create: ") + bad;
-        return MGPU_ERR_ARG;
-    }
-    if (!c) return MGPU_ERR_DEVICE;               // no context: no device was opened
-    return guard(c, [&] {
-        std::unique_ptr<mgpu_chan> k(new mgpu_chan);
-        k->c = c;
-        k->h = prototype(kc);
-        k->cfg = *kc;
-        k->cfg.taps = k->h.data();
-        k->cfg.ntaps = int(k->h.size());
+    if (!bad) bad = plan_error(kc->D, kc->audio_centre_hz, kc->S, channels);
+    return create_stage(c, out, "mgpu_chan_create", bad, [&](mgpu_chan* k) {
+        keep_config(k, kc, prototype(kc));
         k->chans.assign(channels, channels + kc->S);
         const int S = k->S = kc->S, D = k->D = kc->D, T = k->T = int(k->h.size());
         k->L = (T - 1) / D / 2;
@@ -266,54 +247,32 @@ int mgpu_chan_create(mgpu_ctx* c, const mgpu_chan_config* kc, const mgpu_chan_ch
         const void* fn = R == 2 ? reinterpret_cast<const void*>(mgpu_chan_fir_r2_kernel) : reinterpret_cast<const void*>(mgpu_chan_fir_r1_kernel);
         need(k->lds <= size_t(kMaxLds), "LDS image larger than the kernel's limit");
         HIPCK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));   // the same for every channeliser
-        const size_t line = size_t(T - 1) + size_t(k->max_out) * D;
-        for (auto& b : k->d_line) b = DevArray<double2>(line * sizeof(double2));
+        k->line.make((size_t(T - 1) + size_t(k->max_out) * D) * sizeof(double2));
         k->d_g = DevArray<double2>(size_t(S) * T * sizeof(double2));
         k->d_rows = DevArray<ChanRow>(size_t(S) * sizeof(ChanRow));
-        std::vector<double> W(size_t(MGPU_CHAN_PHASOR_LEN) * 2);
-        phasor_table(W.data());
-        k->d_W = DevArray<double2>(W.size() * 8);
-        HIPCK(hipMemcpyAsync(k->d_W, W.data(), W.size() * 8, hipMemcpyHostToDevice, c->stream));
+        k->d_W = phasor_table_on_device();
         for (int s = 0; s < S; ++s) k->upload_row(s, c->stream);
-        HIPCK(hipStreamSynchronize(c->stream));
-        *out = k.release();
     });
 }
 
-int mgpu_chan_destroy(mgpu_chan* k) {
-    if (!k) return MGPU_ERR_ARG;
-    mgpu_ctx* c = k->c;
-    return guard(c, [&] {
-        HIPCK(hipDeviceSynchronize());            // process_dev may have run on a caller's stream
-        delete k;
-    });
-}
+int mgpu_chan_destroy(mgpu_chan* k) { return destroy_stage(k); }
 
 int mgpu_chan_latency(mgpu_chan* k) { return k ? k->L : -1; }
 
 int mgpu_chan_seek(mgpu_chan* k, uint64_t position) {
     if (!k || position > (1ULL << 62)) return MGPU_ERR_ARG;
     k->pos = position;
-    k->fresh = true;
+    k->line.restart();
     return MGPU_OK;
 }
 
-int mgpu_chan_retune(mgpu_chan* k, int s, const mgpu_chan_channel* channel) {
-    if (!k) return MGPU_ERR_ARG;
-    return guard(k->c, [&] {
-        need(s >= 0 && s < k->S, "no such channel");
-        if (const char* e = channel_error(k->D, k->cfg.audio_centre_hz, channel)) throw std::invalid_argument(e);
-        HIPCK(hipDeviceSynchronize());            // calls that still read the row, on whatever stream
-        k->chans[s] = *channel;
-        k->upload_row(s, k->c->stream);
-    });
-}
+int mgpu_chan_retune(mgpu_chan* k, int s, const mgpu_chan_channel* channel) { return retune_channel(k, s, channel); }
 
 int mgpu_chan_process_dev(mgpu_chan* k, const void* d_iq, int format, int n_in, double* d_out, void* stream) {
     if (!k) return MGPU_ERR_ARG;
     return guard(k->c, [&] {
         k->check_n_in(d_iq, format, n_in, d_out);
-        k->run(d_iq, format, n_in, d_out, stream ? static_cast<hipStream_t>(stream) : k->c->stream.h);
+        k->run(d_iq, format, n_in, d_out, stream_or_own(k->c, stream));
     });
 }
 
@@ -334,11 +293,13 @@ int mgpu_capture_run_wideband(mgpu_capture* cap, mgpu_chan* k, const void* iq, i
                               uint8_t* payloads, int max_events, int* n_events) {
     if (!cap || !k) return MGPU_ERR_ARG;
     mgpu_capture_geometry g{};
-    if (mgpu_capture_geometry_get(cap, &g) != MGPU_OK || capture_streams(cap) != k->S)
-        return refuse(k->c, MGPU_ERR_ARG, "mgpu_capture_run_wideband: the capture and the channeliser must have the same S");
+    if (!capture_pairs(cap, k->c, k->S, &g))
+        return refuse(k->c, MGPU_ERR_ARG, capture_streams(cap) != k->S
+                                              ? "mgpu_capture_run_wideband: the capture and the channeliser must have the same S"
+                                              : "mgpu_capture_run_wideband: the capture and the channeliser must belong to one context");
     const int rc = guard(k->c, [&] {
         need(H > 0 && (long long)H * g.symbol_period <= k->max_out, "H * P must be 1..max_out");
-        need(n_events != nullptr && max_events >= 0 && (max_events == 0 || events), "bad argument (n_events, events)");
+        check_event_args(events, max_events, n_events);
         const int n_in = H * g.symbol_period * k->D;
         k->need_out();
         k->check_n_in(iq, format, n_in, k->d_out.p);

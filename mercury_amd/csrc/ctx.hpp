@@ -490,6 +490,12 @@ inline int guard(mgpu_ctx* c, const std::function<void()>& fn) {
 inline void need(bool ok, const char* what) { if (!ok) throw std::invalid_argument(what); }
 // a refusal before any device work: the message where mgpu_last_error finds it, and the code to return
 inline int refuse(mgpu_ctx* c, int code, const char* message) { c->err = message; return code; }
+// the stream a *_dev entry point works on: the caller's, or the context's own where it names none
+inline hipStream_t stream_or_own(mgpu_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream.h; }
+// the event arguments of mgpu_capture_run and of the entry points that end in it
+inline void check_event_args(const void* events, int max_events, const int* n_events) {
+    need(n_events != nullptr && max_events >= 0 && (max_events == 0 || events), "bad argument (n_events, events)");
+}
 // Rows [first, first + count) of an array the last call left on the device, one row of `per_row` elements per frame (or window) of
 // max_batch, into dst (null: not wanted). never_set: the message where the array was never made.
 template <typename T>
@@ -558,7 +564,10 @@ double audio_noise_amplitude(const mgpu::ModeTables& t, double esn0_db, double m
 
 }  // namespace mgpu_detail
 
-// the context a capture was made on and the number of its captures (capture.hip): what the feeders in front of one hold against their own
+// what the feeders in front of a capture (capture.hip) hold against their own: the number of its captures,
 struct mgpu_capture;
-mgpu_ctx* capture_context(mgpu_capture* cap);
+struct mgpu_capture_geometry;
 int capture_streams(mgpu_capture* cap);
+// and whether a stage of context c with S streams can feed the capture: its geometry (into *g) is readable, it has S captures and it was made
+// on c, so that its kernels run on the stream of the stage's, behind them
+bool capture_pairs(mgpu_capture* cap, mgpu_ctx* c, int S, mgpu_capture_geometry* g);

@@ -551,7 +551,7 @@ int mgpu_hf_stream_apply_dev(mgpu_hf_stream* k, const void* d_in, int n, const d
     return guard(k->c, [&] {
         need(d_in && d_out && d_in != d_out, "bad argument (in and out must be given and may not alias)");
         need(n > 0 && n % HF_BLK == 0, "n must be a positive multiple of 64");
-        k->apply(static_cast<const double*>(d_in), n, noise_amp, static_cast<double*>(d_out), stream ? static_cast<hipStream_t>(stream) : k->c->stream);
+        k->apply(static_cast<const double*>(d_in), n, noise_amp, static_cast<double*>(d_out), stream_or_own(k->c, stream));
     });
 }
 
@@ -579,7 +579,7 @@ int mgpu_hf_channel_apply_dev(mgpu_ctx* c, const mgpu_hf_channel* ch, const void
         need(d_in && d_out && d_in != d_out && W >= 0 && n >= 0 && (complex_input == 0 || complex_input == 1), "bad argument");
         if (W == 0 || n == 0) return;
         launch(complex_input ? HF_COMPLEX : HF_REAL, pl, HfIo{static_cast<const double*>(d_in), static_cast<double*>(d_out), n, 0, 0, 0, 0.0}, W,
-               stream ? static_cast<hipStream_t>(stream) : c->stream);
+               stream_or_own(c, stream));
     });
 }
 

@@ -16,11 +16,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <vector>
 
-#include "ctx.hpp"
 #include "resamp_tables.hpp"
+#include "stream_stage.hpp"
 
 using namespace mgpu_resamp_detail;
 
@@ -116,9 +115,7 @@ struct mgpu_resamp {
     Ratio r;
     int S = 0, C = 0, tp = 0, max_in = 0, max_out = 0, lds_elems = 0;
     uint64_t m0 = 0;
-    bool fresh = true;                            // no history: the next call reads zeros
-    int cur = 0;                                  // the history buffer the next call reads
-    DevArray<double> d_hist[2];                   // [S][tp * C]
+    History<double> hist;                         // [S][tp * C]
     DevArray<double> d_hp;                        // [L][tp]
     DevArray<char> d_stage;                       // host input's landing area (ctx.hpp staged_on_device)
     DevArray<double> d_out;                       // [S][max_out * C]: process()'s output (made on first use)
@@ -140,7 +137,7 @@ struct mgpu_resamp {
     void run(const void* d_in, int format, int n_in, double* out0, size_t stride0, int split, double* out1, size_t stride1, hipStream_t st) {
         const uint64_t n0 = out_position(m0, r), q0 = n0 * uint64_t(r.M);
         ResampArgs a{};
-        a.in = d_in; a.hist_old = fresh ? nullptr : static_cast<const double*>(d_hist[cur]); a.hist_new = d_hist[cur ^ 1];
+        a.in = d_in; a.hist_old = hist.old(); a.hist_new = hist.next();
         a.hp = d_hp; a.h_last = h.back();
         a.out0 = out0; a.out1 = out1; a.stride0 = stride0; a.stride1 = stride1; a.split = split;
         a.kind = mgpu_fmt::element(C, format); a.n_in = n_in; a.n_out = count(n_in); a.tp = tp; a.L = r.L; a.M = r.M;
@@ -151,8 +148,7 @@ struct mgpu_resamp {
             hipLaunchKernelGGL(mgpu_resamp_kernel, dim3(gx, unsigned(std::min(S - s0, 65535))), dim3(kTile), size_t(lds_elems) * 8, st, a, C);
             HIPCK(hipGetLastError());
         }
-        cur ^= 1;
-        fresh = false;
+        hist.advance();
         m0 += uint64_t(n_in);
     }
 
@@ -164,46 +160,25 @@ struct mgpu_resamp {
 extern "C" {
 
 int mgpu_resamp_create(mgpu_ctx* c, const mgpu_resamp_config* kc, mgpu_resamp** out) {
-    if (!out) return MGPU_ERR_ARG;
-    *out = nullptr;
-    // refused before any device work, with or without a context
-    if (const char* bad = config_error(kc)) {
-        if (c) c->err = std::string("mgpu_resamp_create: ") + bad;
-        return MGPU_ERR_ARG;
-    }
-    if (!c) return MGPU_ERR_DEVICE;               // no context: no device was opened
-    return guard(c, [&] {
-        std::unique_ptr<mgpu_resamp> k(new mgpu_resamp);
-        k->c = c;
+    return create_stage(c, out, "mgpu_resamp_create", config_error(kc), [&](mgpu_resamp* k) {
         ratio(kc->fin, kc->fout, &k->r);
-        k->h = prototype(kc, k->r);
+        keep_config(k, kc, prototype(kc, k->r));
         const int L = k->r.L, M = k->r.M, tp = k->tp = int((k->h.size() - 1) / size_t(L)), S = k->S = kc->S, C = k->C = kc->components;
-        k->cfg = *kc;
         k->cfg.tp = tp;
-        k->cfg.taps = k->h.data();
-        k->cfg.ntaps = int(k->h.size());
         k->max_in = k->cfg.max_in = kc->max_in ? kc->max_in : default_max_in(k->r);
         k->max_out = int(((long long)k->max_in * L + M - 1) / M) + 1;
         k->lds_elems = (((kTile - 1) * M) / L + tp + 3) * C;      // <= (127 * 16 + 515) * 2 doubles = 40752 bytes
-        for (auto& b : k->d_hist) b = DevArray<double>(size_t(S) * tp * C * 8);
+        k->hist.make(size_t(S) * tp * C * 8);
         std::vector<double> hp(size_t(L) * tp);
         for (int rho = 0; rho < L; ++rho)
             for (int j = 0; j < tp; ++j) hp[size_t(rho) * tp + j] = k->h[size_t(rho) + size_t(j) * L];
         k->d_hp = DevArray<double>(hp.size() * 8);
         HIPCK(hipMemcpyAsync(k->d_hp, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));   // hp is this call's
-        *out = k.release();
     });
 }
 
-int mgpu_resamp_destroy(mgpu_resamp* k) {
-    if (!k) return MGPU_ERR_ARG;
-    mgpu_ctx* c = k->c;
-    return guard(c, [&] {
-        HIPCK(hipDeviceSynchronize());            // process_dev may have run on a caller's stream
-        delete k;
-    });
-}
+int mgpu_resamp_destroy(mgpu_resamp* k) { return destroy_stage(k); }
 
 int mgpu_resamp_info(mgpu_resamp* k, mgpu_resamp_status* st) {
     if (!k || !st) return MGPU_ERR_ARG;
@@ -218,7 +193,7 @@ int mgpu_resamp_info(mgpu_resamp* k, mgpu_resamp_status* st) {
 int mgpu_resamp_seek(mgpu_resamp* k, uint64_t position) {
     if (!k || position > MGPU_RESAMP_MAX_POSITION) return MGPU_ERR_ARG;
     k->m0 = position;
-    k->fresh = true;
+    k->hist.restart();
     k->fill = 0;
     return MGPU_OK;
 }
@@ -230,7 +205,7 @@ int mgpu_resamp_process_dev(mgpu_resamp* k, const void* d_in, int format, int n_
         const int N = k->count(n_in);
         need(size_t(N) <= out_stride && (d_out || !N), "out_stride is smaller than the call's outputs");
         *n_out = N;
-        k->run(d_in, format, n_in, d_out, out_stride, N, nullptr, 0, stream ? static_cast<hipStream_t>(stream) : k->c->stream.h);
+        k->run(d_in, format, n_in, d_out, out_stride, N, nullptr, 0, stream_or_own(k->c, stream));
     });
 }
 
@@ -254,12 +229,12 @@ int mgpu_capture_run_resampled(mgpu_capture* cap, mgpu_resamp* k, const void* sa
                                uint8_t* payloads, int max_events, int* n_events, int* hops_run) {
     if (!cap || !k) return MGPU_ERR_ARG;
     mgpu_capture_geometry g{};
-    if (mgpu_capture_geometry_get(cap, &g) != MGPU_OK || capture_streams(cap) != k->S || capture_context(cap) != k->c || k->C != 1 || k->cfg.fout != 48000)
+    if (!capture_pairs(cap, k->c, k->S, &g) || k->C != 1 || k->cfg.fout != 48000)
         return refuse(k->c, MGPU_ERR_ARG, "mgpu_capture_run_resampled: one context, the same S, components = 1 and fout = 48000");
     int H = 0;
     const int rc = guard(k->c, [&] {
         k->check_in(samples, format, n_in, hops_run);
-        need(n_events != nullptr && max_events >= 0 && (max_events == 0 || events), "bad argument (n_events, events)");
+        check_event_args(events, max_events, n_events);
         const int P = g.symbol_period, S = k->S;
         if (k->P != P) {                                              // first call, or another capture's hop: an empty FIFO of rows of P
             need(k->fill == 0, "the FIFO holds outputs for a capture with another symbol period: seek first");

@@ -105,13 +105,13 @@ void mgpu_device_free(mgpu_ctx* c, void* d_ptr) {
 void* mgpu_context_stream(mgpu_ctx* c) { return c ? static_cast<void*>(c->stream) : nullptr; }
 int mgpu_synchronize(mgpu_ctx* c, void* stream) {
     if (!c) return MGPU_ERR_ARG;
-    return guard(c, [&] { HIPCK(hipStreamSynchronize(stream ? static_cast<hipStream_t>(stream) : c->stream)); });
+    return guard(c, [&] { HIPCK(hipStreamSynchronize(stream_or_own(c, stream))); });
 }
 static int copy_and_wait(mgpu_ctx* c, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, void* stream) {
     if (!c) return MGPU_ERR_ARG;
     return guard(c, [&] {
         need((dst && src) || bytes == 0, "bad argument");
-        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+        hipStream_t s = stream_or_own(c, stream);
         if (bytes) HIPCK(hipMemcpyAsync(dst, src, bytes, kind, s));
         HIPCK(hipStreamSynchronize(s));
     });

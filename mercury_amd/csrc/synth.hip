@@ -19,14 +19,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <vector>
 
-#include "ctx.hpp"
+#include "stream_stage.hpp"
 #include "synth_tables.hpp"
 
 using namespace mgpu_synth_detail;
-using mgpu_chan_detail::channel_error;
 using mgpu_chan_detail::floor_mod;
 
 namespace {
@@ -175,10 +173,8 @@ struct mgpu_synth {
     std::vector<mgpu_chan_channel> chans;
     int S = 0, D = 0, tp = 0, max_in = 0, PH = 1, groups = 1;
     uint64_t pos = 0;
-    bool fresh = true;                            // no history: the next call reads zeros
     bool recount = true;                          // the clamp count restarts at the next call
-    int cur = 0;                                  // the history buffer the next call reads
-    DevArray<double> d_hist[2];                   // [S][tp]
+    History<double> hist;                         // [S][tp]
     DevArray<double2> d_q, d_P, d_W;              // [2][groups][tp + 1][PH], [S][groups PH], [48000]
     DevArray<SynthRow> d_rows;                    // [S]
     DevArray<unsigned long long> d_clamped;       // [1]
@@ -207,7 +203,7 @@ struct mgpu_synth {
         if (recount) HIPCK(hipMemsetAsync(d_clamped.p, 0, sizeof(unsigned long long), st));
         recount = false;
         SynthArgs a{};
-        a.in = d_in; a.in_stride = in_stride; a.hist_old = fresh ? nullptr : static_cast<const double*>(d_hist[cur]); a.hist_new = d_hist[cur ^ 1];
+        a.in = d_in; a.in_stride = in_stride; a.hist_old = hist.old(); a.hist_new = hist.next();
         a.out = d_o; a.clamped = d_clamped; a.format = format; a.S = S; a.D = D; a.tp = tp; a.n_in = n_in; a.groups = groups;
         a.nm = unsigned(pos % MGPU_CHAN_PHASOR_LEN);
         const dim3 grid(unsigned((n_in + kTile - 1) / kTile), unsigned(groups));
@@ -215,8 +211,7 @@ struct mgpu_synth {
         hipLaunchKernelGGL(fn, grid, dim3(kThreads), 0, st, a, static_cast<const double2*>(d_q), static_cast<const double2*>(d_P),
                            static_cast<const double2*>(d_W), static_cast<const SynthRow*>(d_rows));
         HIPCK(hipGetLastError());
-        cur ^= 1;
-        fresh = false;
+        hist.advance();
         pos += uint64_t(n_in);
     }
 };
@@ -224,30 +219,16 @@ struct mgpu_synth {
 extern "C" {
 
 int mgpu_synth_create(mgpu_ctx* c, const mgpu_synth_config* kc, const mgpu_chan_channel* channels, mgpu_synth** out) {
-    if (!out) return MGPU_ERR_ARG;
-    *out = nullptr;
-    // refused before any device work, with or without a context
     const char* bad = config_error(kc, true);
-    if (!bad && !channels) bad = "no channels";
-    for (int s = 0; !bad && s < kc->S; ++s) bad = channel_error(kc->D, kc->audio_centre_hz, channels + s);
-    if (bad) {
-        if (c) c->err = std::string("mgpu_synth_create: ") + bad;
-        return MGPU_ERR_ARG;
-    }
-    if (!c) return MGPU_ERR_DEVICE;               // no context: no device was opened
-    return guard(c, [&] {
-        std::unique_ptr<mgpu_synth> k(new mgpu_synth);
-        k->c = c;
-        k->h = prototype(kc);
-        k->cfg = *kc;
-        k->cfg.taps = k->h.data();
-        k->cfg.ntaps = int(k->h.size());
+    if (!bad) bad = mgpu_chan_detail::plan_error(kc->D, kc->audio_centre_hz, kc->S, channels);
+    return create_stage(c, out, "mgpu_synth_create", bad, [&](mgpu_synth* k) {
+        keep_config(k, kc, prototype(kc));
         k->chans.assign(channels, channels + kc->S);
         const int S = k->S = kc->S, D = k->D = kc->D, T = int(k->h.size()), tp = k->tp = (T - 1) / D;
         k->max_in = k->cfg.max_in = kc->max_in ? kc->max_in : kDefaultMaxIn;
         need((long long)k->max_in * D <= (1LL << 30), "max_in * D must be at most 2^30");
         const int PH = k->PH = phases_per_lane(D), groups = k->groups = (D + PH - 1) / PH;
-        for (auto& b : k->d_hist) b = DevArray<double>(size_t(S) * tp * 8);
+        k->hist.make(size_t(S) * tp * 8);
         // the taps as the kernel walks them: [sideband][group][j = 0 .. tp][PH]; a phase beyond D - 1, and step tp of a phase above 0, are zeros
         // that no output reads
         std::vector<double> qp(size_t(T) * 2), q(size_t(2) * groups * (tp + 1) * PH * 2, 0.0);
@@ -266,53 +247,33 @@ int mgpu_synth_create(mgpu_ctx* c, const mgpu_synth_config* kc, const mgpu_chan_
         k->d_P = DevArray<double2>(size_t(S) * groups * PH * sizeof(double2));
         k->d_rows = DevArray<SynthRow>(size_t(S) * sizeof(SynthRow));
         k->d_clamped = DevArray<unsigned long long>(sizeof(unsigned long long));
-        std::vector<double> W(size_t(MGPU_CHAN_PHASOR_LEN) * 2);
-        mgpu_chan_detail::phasor_table(W.data());
-        k->d_W = DevArray<double2>(W.size() * 8);
+        k->d_W = phasor_table_on_device();
         HIPCK(hipMemcpyAsync(k->d_q, q.data(), q.size() * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCK(hipMemcpyAsync(k->d_W, W.data(), W.size() * 8, hipMemcpyHostToDevice, c->stream));
         HIPCK(hipMemsetAsync(k->d_clamped.p, 0, sizeof(unsigned long long), c->stream));
         for (int s = 0; s < S; ++s) k->upload_row(s, c->stream);
-        HIPCK(hipStreamSynchronize(c->stream));   // q and W are this call's
-        *out = k.release();
+        HIPCK(hipStreamSynchronize(c->stream));   // q is this call's
     });
 }
 
-int mgpu_synth_destroy(mgpu_synth* k) {
-    if (!k) return MGPU_ERR_ARG;
-    mgpu_ctx* c = k->c;
-    return guard(c, [&] {
-        HIPCK(hipDeviceSynchronize());            // process_dev may have run on a caller's stream
-        delete k;
-    });
-}
+int mgpu_synth_destroy(mgpu_synth* k) { return destroy_stage(k); }
 
 int mgpu_synth_latency(mgpu_synth* k) { return k ? k->tp / 2 : -1; }
 
 int mgpu_synth_seek(mgpu_synth* k, uint64_t position) {
     if (!k || position > kMaxPosition) return MGPU_ERR_ARG;
     k->pos = position;
-    k->fresh = true;
+    k->hist.restart();
     k->recount = true;
     return MGPU_OK;
 }
 
-int mgpu_synth_retune(mgpu_synth* k, int s, const mgpu_chan_channel* channel) {
-    if (!k) return MGPU_ERR_ARG;
-    return guard(k->c, [&] {
-        need(s >= 0 && s < k->S, "no such channel");
-        if (const char* e = channel_error(k->D, k->cfg.audio_centre_hz, channel)) throw std::invalid_argument(e);
-        HIPCK(hipDeviceSynchronize());            // calls that still read the row, on whatever stream
-        k->chans[s] = *channel;
-        k->upload_row(s, k->c->stream);
-    });
-}
+int mgpu_synth_retune(mgpu_synth* k, int s, const mgpu_chan_channel* channel) { return retune_channel(k, s, channel); }
 
 int mgpu_synth_process_dev(mgpu_synth* k, const double* d_audio, size_t in_stride, int n_in, int format, void* d_out, void* stream) {
     if (!k) return MGPU_ERR_ARG;
     return guard(k->c, [&] {
         k->check_in(d_audio, in_stride, n_in, format, d_out);
-        k->run(d_audio, in_stride, n_in, format, d_out, stream ? static_cast<hipStream_t>(stream) : k->c->stream.h);
+        k->run(d_audio, in_stride, n_in, format, d_out, stream_or_own(k->c, stream));
     });
 }
 

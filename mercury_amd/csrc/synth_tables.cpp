@@ -82,9 +82,7 @@ int mgpu_host_synth_tables(const mgpu_synth_config* k, const mgpu_chan_channel* 
 
 int mgpu_host_synth_process(const mgpu_synth_config* k, const mgpu_chan_channel* channels, const double* audio, size_t in_stride, int n_in,
                             uint64_t position, int format, void* out, uint64_t* clamped) {
-    if (config_error(k, true) || !channels || !audio || !out) return MGPU_ERR_ARG;
-    for (int s = 0; s < k->S; ++s)
-        if (mgpu_chan_detail::channel_error(k->D, k->audio_centre_hz, channels + s)) return MGPU_ERR_ARG;
+    if (config_error(k, true) || mgpu_chan_detail::plan_error(k->D, k->audio_centre_hz, k->S, channels) || !audio || !out) return MGPU_ERR_ARG;
     if (n_in < 1 || (long long)n_in * k->D > (1LL << 30) || in_stride < size_t(n_in) || !iq_sample_bytes(format)) return MGPU_ERR_ARG;
     if (position > kMaxPosition || position + uint64_t(n_in) > kMaxPosition) return MGPU_ERR_ARG;
     const int D = k->D, S = k->S;

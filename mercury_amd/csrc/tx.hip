@@ -414,7 +414,7 @@ int mgpu_transmit_byte_batch_dev(mgpu_ctx* c, const void* d_payload, int payload
         need(!stream || !stream_mode, "FIRST / MIDDLE / FLUSH messages carry state between calls: pass stream = NULL (the context's stream)");
         if (F == 0) return;
         transmit_dev(c, static_cast<const uint8_t*>(d_payload), payload_stride, static_cast<const int*>(d_nbytes), F, *cfg,
-                     static_cast<double*>(d_passband), stream ? static_cast<hipStream_t>(stream) : c->stream);
+                     static_cast<double*>(d_passband), stream_or_own(c, stream));
         if (!stream) HIPCK(hipStreamSynchronize(c->stream));
     });
 }

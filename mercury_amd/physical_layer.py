@@ -28,6 +28,13 @@ def _checked(fn, *args, what="failed"):
         raise MgpuError("%s %s (%d)" % (fn.__name__, what, rc), rc)
 
 
+def _twin(fn, *args, code=None):
+    """fn(*args) of a host twin, which has no context to leave a reason in: a status other than 0 raises
+    MgpuError("<the function's name>: bad argument") with `code` as its code"""
+    if fn(*args) != 0:
+        raise MgpuError("%s: bad argument" % fn.__name__, code)
+
+
 def _explicit_struct(explicit):
     if not explicit:
         return None
@@ -1565,8 +1572,7 @@ def host_capture_prep(geometry, window, samples, state):
     x = np.ascontiguousarray(samples)
     assert window.dtype == np.float64 and window.flags.c_contiguous and window.size == geometry.buffer_nsymb * geometry.symbol_period
     assert x.size == geometry.symbol_period and state.dtype == CAPTURE_STATE_DTYPE
-    if load_library().mgpu_host_capture_prep(C.byref(geometry), _ptr(window), _ptr(x), _sample_format(x.dtype), _ptr(state)) != 0:
-        raise MgpuError("mgpu_host_capture_prep: bad argument")
+    _twin(load_library().mgpu_host_capture_prep, C.byref(geometry), _ptr(window), _ptr(x), _sample_format(x.dtype), _ptr(state))
 
 
 def host_capture_process(geometry, state, stats=None, link=None):
@@ -1578,6 +1584,29 @@ def host_capture_process(geometry, state, stats=None, link=None):
     if rc < 0:
         raise MgpuError("mgpu_host_capture_process: bad argument (%d)" % rc)
     return bool(rc)
+
+
+def _event_buffers(rows, payload_stride):
+    """the arrays a run writes its events and their payloads into, `rows` of each"""
+    return np.zeros(rows, CAPTURE_EVENT_DTYPE), np.zeros((rows, payload_stride), np.uint8)
+
+
+def _event_list(ev, pl, n, m, payload_bytes):
+    """the first min(n, m) events as (capture, hop, stats, payload bytes)"""
+    return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :payload_bytes].copy()) for i in range(min(n, m))]
+
+
+def _real_samples(samples):
+    """-> (pointer, MGPU_SAMPLES_* format, count, keep-alive): real samples in a capture format, a numpy array or a contiguous torch
+    tensor (read in place)"""
+    if hasattr(samples, "data_ptr"):                       # a device tensor
+        import torch
+        fmt = {torch.float64: 0, torch.int32: 1, torch.int16: 2, torch.float32: 3}.get(samples.dtype)
+        if fmt is None or not samples.is_contiguous():
+            raise MgpuError("device samples: a contiguous float64 / int32 / int16 / float32 tensor")
+        return samples.data_ptr(), fmt, samples.numel(), samples
+    x = np.ascontiguousarray(samples)
+    return _ptr(x), _sample_format(x.dtype), x.size, x
 
 
 class RxCapture(_Handle):
@@ -1598,24 +1627,18 @@ class RxCapture(_Handle):
         if initial_windows is not None:
             init = np.ascontiguousarray(initial_windows, np.float64).reshape(S, -1)
         rx._ck(self.lib.mgpu_capture_create(rx.h, S, C.byref(cfg), _ptr(init), max_hops, C.byref(self.h)))
+        self._read_geometry()
+
+    def _read_geometry(self):
         self.geometry = CaptureGeometry()
-        rx._ck(self.lib.mgpu_capture_geometry_get(self.h, C.byref(self.geometry)))
+        self.rx._ck(self.lib.mgpu_capture_geometry_get(self.h, C.byref(self.geometry)))
         self.P = self.geometry.symbol_period
         self.window_samples = self.geometry.buffer_nsymb * self.P
-        self.payload_stride = rx.payload_stride
+        self.payload_stride = self.rx.payload_stride
 
     def _samples(self, samples):
         """-> (pointer, format, H, keep-alive)"""
-        if hasattr(samples, "data_ptr"):                   # a device tensor
-            import torch
-            fmt = {torch.float64: 0, torch.int32: 1, torch.int16: 2, torch.float32: 3}.get(samples.dtype)
-            if fmt is None or not samples.is_contiguous():
-                raise MgpuError("device samples: a contiguous float64 / int32 / int16 / float32 tensor")
-            n = samples.numel()
-            ptr, keep = samples.data_ptr(), samples
-        else:
-            x = np.ascontiguousarray(samples)
-            fmt, n, ptr, keep = _sample_format(x.dtype), x.size, _ptr(x), x
+        ptr, fmt, n, keep = _real_samples(samples)
         if n % (self.S * self.P):
             raise MgpuError("samples must be [S, H * P] with P = %d" % self.P)
         return ptr, fmt, n // (self.S * self.P), keep
@@ -1636,12 +1659,10 @@ class RxCapture(_Handle):
         """H rounds of feed(1) + process() -> list of (capture, hop, stats, payload bytes) for the decoded frames, in order of hop, then capture"""
         ptr, fmt, H, _keep = self._samples(samples)
         m = self.S * H if max_events is None else max_events
-        ev = np.zeros(m, CAPTURE_EVENT_DTYPE)
-        pl = np.zeros((m, self.payload_stride), np.uint8)
+        ev, pl = _event_buffers(m, self.payload_stride)
         n = C.c_int()
         self.rx._ck(self.lib.mgpu_capture_run(self.h, ptr, fmt, H, _ptr(ev), _ptr(pl), m, C.byref(n)))
-        nb = self.rx.payload_bytes
-        return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
+        return _event_list(ev, pl, n.value, m, self.rx.payload_bytes)
 
     def run_wideband(self, chan, iq, max_events=None):
         """run() on wideband IQ through the Channelizer `chan` (mgpu_capture_run_wideband): H * P * D complex samples -> the decoded
@@ -1651,24 +1672,20 @@ class RxCapture(_Handle):
             raise MgpuError("IQ samples must be H * P * D with P = %d, D = %d" % (self.P, chan.D))
         H = n_in // (self.P * chan.D)
         m = self.S * H if max_events is None else max_events
-        ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
-        pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
+        ev, pl = _event_buffers(max(m, 1), self.payload_stride)
         n = C.c_int()
         self.rx._ck(self.lib.mgpu_capture_run_wideband(self.h, chan.h, ptr, fmt, H, _ptr(ev), _ptr(pl), m, C.byref(n)))
-        nb = self.rx.payload_bytes
-        return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
+        return _event_list(ev, pl, n.value, m, self.rx.payload_bytes)
 
     def run_resampled(self, rs, samples, max_events=None):
         """run() on audio at the Resampler `rs`'s input rate (mgpu_capture_run_resampled): [S, n_in] samples, any n_in up to rs.max_in ->
         (the decoded frames as run() lists them, hops numbered from the call's first, and how many hops the call ran)"""
         ptr, fmt, n_in, _keep = _resamp_input(samples, self.S, 1)
         m = self.S * (rs.max_out // self.P + 1) if max_events is None else max_events
-        ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
-        pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
+        ev, pl = _event_buffers(max(m, 1), self.payload_stride)
         n, hops = C.c_int(), C.c_int()
         self.rx._ck(self.lib.mgpu_capture_run_resampled(self.h, rs.h, ptr, fmt, n_in, _ptr(ev), _ptr(pl), m, C.byref(n), C.byref(hops)))
-        nb = self.rx.payload_bytes
-        return [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))], hops.value
+        return _event_list(ev, pl, n.value, m, self.rx.payload_bytes), hops.value
 
     def state(self, s):
         st = np.zeros((), CAPTURE_STATE_DTYPE)
@@ -1690,8 +1707,7 @@ def host_hf_stream_noise(seed, signal, position, n):
     """g(seed, signal, position + i), i < n: the streaming channel's unit noise (host-only twin, no GPU)."""
     out = np.zeros(n)
     lib = load_library()
-    if lib.mgpu_host_hf_stream_noise(seed, signal, position, n, _ptr(out)) != 0:
-        raise MgpuError("mgpu_host_hf_stream_noise: bad argument")
+    _twin(lib.mgpu_host_hf_stream_noise, seed, signal, position, n, _ptr(out))
     return out
 
 
@@ -1752,8 +1768,7 @@ def host_linksim_frame_start(config, frame_samples, symbol_period, link, frame):
     """transmit position of frame `frame` of link `link` (host only)"""
     out = C.c_longlong()
     lib = load_library()
-    if lib.mgpu_host_linksim_frame_start(C.byref(config), frame_samples, symbol_period, link, frame, C.byref(out)) != 0:
-        raise MgpuError("mgpu_host_linksim_frame_start: bad argument")
+    _twin(lib.mgpu_host_linksim_frame_start, C.byref(config), frame_samples, symbol_period, link, frame, C.byref(out))
     return out.value
 
 
@@ -1761,8 +1776,7 @@ def host_linksim_payload(seed, link, frame, nbytes):
     """the payload link `link` sends in its frame `frame`: uint8 [nbytes] (host only)"""
     out = np.zeros(nbytes, np.uint8)
     lib = load_library()
-    if lib.mgpu_host_linksim_payload(seed, link, frame, nbytes, _ptr(out)) != 0:
-        raise MgpuError("mgpu_host_linksim_payload: bad argument")
+    _twin(lib.mgpu_host_linksim_payload, seed, link, frame, nbytes, _ptr(out))
     return out
 
 
@@ -1771,11 +1785,7 @@ class _BorrowedCapture(RxCapture):
 
     def __init__(self, rx, handle, S):
         self.rx, self.lib, self.S, self.h = rx, rx.lib, S, handle
-        self.geometry = CaptureGeometry()
-        rx._ck(self.lib.mgpu_capture_geometry_get(self.h, C.byref(self.geometry)))
-        self.P = self.geometry.symbol_period
-        self.window_samples = self.geometry.buffer_nsymb * self.P
-        self.payload_stride = rx.payload_stride
+        self._read_geometry()
 
     def close(self):
         self.h = C.c_void_p()
@@ -1811,13 +1821,11 @@ class LinkSim(_Handle):
         """H more hops for every link -> list of (link, hop since the start, stats, payload bytes) for the decoded frames; with
         want_samples also the audio the captures were fed, float64 [S, H * P]"""
         m = self.S * H if max_events is None else max_events
-        ev = np.zeros(max(m, 1), CAPTURE_EVENT_DTYPE)
-        pl = np.zeros((max(m, 1), self.payload_stride), np.uint8)
+        ev, pl = _event_buffers(max(m, 1), self.payload_stride)
         n = C.c_int()
         audio = np.zeros((self.S, H * self.P)) if want_samples else None
         self.rx._ck(self.lib.mgpu_linksim_run(self.h, H, _ptr(ev), _ptr(pl), m, C.byref(n), _ptr(audio)))
-        nb = self.rx.payload_bytes
-        events = [(int(ev[i]["capture"]), int(ev[i]["hop"]), ev[i]["stats"].copy(), pl[i, :nb].copy()) for i in range(min(n.value, m))]
+        events = _event_list(ev, pl, n.value, m, self.rx.payload_bytes)
         return (events, audio) if want_samples else events
 
     def counters(self):
@@ -1853,11 +1861,6 @@ class ChanConfig(C.Structure):          # mgpu_chan_config
                 ("taps", C.c_void_p), ("max_out", C.c_int)]
 
 
-def _chan_argtypes(lib):
-    """what typed the channeliser's functions before abi.py did it at load; kept, as the identity, for tests written against that binding"""
-    return lib
-
-
 def chan_channels(channels):
     """[(offset_hz, sideband, gain), ...] (sideband 0 / "usb" or 1 / "lsb"; gain optional, 1.0) -> an array of mgpu_chan_channel"""
     rows = []
@@ -1870,12 +1873,23 @@ def chan_channels(channels):
     return (ChanChannel * len(rows))(*rows)
 
 
+def _taps_arg(taps):
+    """a prototype given as taps -> (float64 array or None: the keep-alive, its count, its address as a configuration's `taps` takes it)"""
+    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
+    return h, 0 if h is None else h.size, None if h is None else h.ctypes.data
+
+
 def chan_config(D, S, taps=None, audio_centre_hz=1472, max_out=0):
     """-> (mgpu_chan_config, keep-alive of its taps)"""
-    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
-    k = ChanConfig(C.sizeof(ChanConfig), int(D), int(S), int(audio_centre_hz), 0 if h is None else h.size,
-                   None if h is None else h.ctypes.data, int(max_out))
-    return k, h
+    h, ntaps, address = _taps_arg(taps)
+    return ChanConfig(C.sizeof(ChanConfig), int(D), int(S), int(audio_centre_hz), ntaps, address, int(max_out)), h
+
+
+def _plan_tables(D, keep, want_phasor):
+    """what a channel plan's table twins write: T, the prototype's length (keep: a configuration's own taps, or None: the default
+    design), and the phasor table's array (None: not wanted)"""
+    T = keep.size if keep is not None else CHAN_DEFAULT_TP * max(int(D), 0) + 1
+    return T, np.zeros(CHAN_PHASOR_LEN, np.complex128) if want_phasor else None
 
 
 def _iq(iq):
@@ -1900,19 +1914,16 @@ def host_chan_design(D, tp=None, cutoff_hz=1500.0, atten_db=60.0):
     tp = CHAN_DEFAULT_TP if tp is None else int(tp)
     taps = np.zeros(max(tp, 0) * max(int(D), 0) + 1)
     n = C.c_int()
-    if load_library().mgpu_host_chan_design(int(D), tp, cutoff_hz, atten_db, _ptr(taps), C.byref(n)) != 0:
-        raise MgpuError("mgpu_host_chan_design: bad argument", 1)
+    _twin(load_library().mgpu_host_chan_design, int(D), tp, cutoff_hz, atten_db, _ptr(taps), C.byref(n), code=1)
     return taps[: n.value]
 
 
 def host_chan_tables(D, channel, taps=None, audio_centre_hz=1472, want_phasor=False):
     """one channel's tap row g, complex128 [T] (and the phasor table W, complex128 [48000]) as the device reads them"""
     k, keep = chan_config(D, 1, taps, audio_centre_hz)
-    T = keep.size if keep is not None else CHAN_DEFAULT_TP * max(int(D), 0) + 1
+    T, W = _plan_tables(D, keep, want_phasor)
     g = np.zeros(T, np.complex128)
-    W = np.zeros(CHAN_PHASOR_LEN, np.complex128) if want_phasor else None
-    if load_library().mgpu_host_chan_tables(C.byref(k), chan_channels([channel]), _ptr(g), _ptr(W)) != 0:
-        raise MgpuError("mgpu_host_chan_tables: bad argument", 1)
+    _twin(load_library().mgpu_host_chan_tables, C.byref(k), chan_channels([channel]), _ptr(g), _ptr(W), code=1)
     return (g, W) if want_phasor else g
 
 
@@ -1924,8 +1935,7 @@ def host_chan_process(D, channels, iq, position=0, taps=None, audio_centre_hz=14
         k.struct_size = struct_size
     ptr, fmt, n_in, _x = _iq(iq)
     out = np.zeros((len(chs), max(n_in // max(int(D), 1), 1)))
-    if load_library().mgpu_host_chan_process(C.byref(k), chs, ptr, fmt, n_in, int(position), _ptr(out)) != 0:
-        raise MgpuError("mgpu_host_chan_process: bad argument", 1)
+    _twin(load_library().mgpu_host_chan_process, C.byref(k), chs, ptr, fmt, n_in, int(position), _ptr(out), code=1)
     return out
 
 
@@ -1991,28 +2001,16 @@ def resamp_ratio(fin, fout):
 
 def resamp_config(fin, fout=48000, S=1, components=1, tp=None, taps=None, max_in=None):
     """-> (mgpu_resamp_config, keep-alive of its taps). With taps and no tp, tp is (len(taps) - 1) / L."""
-    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
+    h, ntaps, address = _taps_arg(taps)
     if h is not None and tp is None and fin > 0 and fout > 0:
         tp = (h.size - 1) // resamp_ratio(fin, fout)[0]
-    k = ResampConfig(C.sizeof(ResampConfig), int(fin), int(fout), int(S), int(components), int(tp or 0), 0 if h is None else h.size,
-                     None if h is None else h.ctypes.data, int(max_in or 0))
-    return k, h
+    return ResampConfig(C.sizeof(ResampConfig), int(fin), int(fout), int(S), int(components), int(tp or 0), ntaps, address, int(max_in or 0)), h
 
 
 def _resamp_input(x, S, components):
     """-> (pointer, format, samples per stream, keep-alive): [S, n_in] real samples in a capture format (components 1) or IQ as
     Channelizer.process takes it (components 2); a numpy array or a torch tensor (read in place)"""
-    if components == 2:
-        ptr, fmt, n, keep = _iq(x)
-    elif hasattr(x, "data_ptr"):
-        import torch
-        fmt = {torch.float64: 0, torch.int32: 1, torch.int16: 2, torch.float32: 3}.get(x.dtype)
-        if fmt is None or not x.is_contiguous():
-            raise MgpuError("device samples: a contiguous float64 / int32 / int16 / float32 tensor")
-        ptr, n, keep = x.data_ptr(), x.numel(), x
-    else:
-        keep = np.ascontiguousarray(x)
-        ptr, fmt, n = _ptr(keep), _sample_format(keep.dtype), keep.size
+    ptr, fmt, n, keep = _iq(x) if components == 2 else _real_samples(x)
     if n % S:
         raise MgpuError("samples must be [S, n_in] with S = %d" % S)
     return ptr, fmt, n // S, keep
@@ -2023,19 +2021,16 @@ def host_resamp_design(fin, fout=48000, tp=None, cutoff_hz=None, atten_db=None):
     lib = load_library()
     n = C.c_int()
     args = (int(fin), int(fout), int(tp or 0), float(cutoff_hz or 0.0), float(atten_db or 0.0))
-    if lib.mgpu_host_resamp_design(*args, None, C.byref(n)) != 0:
-        raise MgpuError("mgpu_host_resamp_design: bad argument", 1)
+    _twin(lib.mgpu_host_resamp_design, *args, None, C.byref(n), code=1)
     taps = np.zeros(n.value)
-    if lib.mgpu_host_resamp_design(*args, _ptr(taps), C.byref(n)) != 0:
-        raise MgpuError("mgpu_host_resamp_design: bad argument", 1)
+    _twin(lib.mgpu_host_resamp_design, *args, _ptr(taps), C.byref(n), code=1)
     return taps
 
 
 def host_resamp_count(fin, fout, m0, n_in):
     """outputs of a call of n_in inputs at input position m0 (mgpu_host_resamp_count)"""
     n = C.c_int()
-    if load_library().mgpu_host_resamp_count(int(fin), int(fout), int(m0), int(n_in), C.byref(n)) != 0:
-        raise MgpuError("mgpu_host_resamp_count: bad argument", 1)
+    _twin(load_library().mgpu_host_resamp_count, int(fin), int(fout), int(m0), int(n_in), C.byref(n), code=1)
     return n.value
 
 
@@ -2061,9 +2056,8 @@ def host_resamp_process(fin, fout, x, position=0, components=1, tp=None, taps=No
         cap = 0
     out = np.zeros((S, max(cap, 1) * max(int(components), 1)))
     n = C.c_int()
-    if load_library().mgpu_host_resamp_process(C.byref(k), ptr, f if fmt is None else fmt, n_in, int(position), _ptr(out), max(cap, 1),
-                                               C.byref(n)) != 0:
-        raise MgpuError("mgpu_host_resamp_process: bad argument", 1)
+    _twin(load_library().mgpu_host_resamp_process, C.byref(k), ptr, f if fmt is None else fmt, n_in, int(position), _ptr(out), max(cap, 1),
+          C.byref(n), code=1)
     return _resamp_result(out, n.value, components)
 
 
@@ -2125,10 +2119,8 @@ class SynthState(C.Structure):          # mgpu_synth_state
 
 def synth_config(D, S, taps=None, audio_centre_hz=1472, max_in=0):
     """-> (mgpu_synth_config, keep-alive of its taps)"""
-    h = None if taps is None else np.ascontiguousarray(taps, np.float64).ravel()
-    k = SynthConfig(C.sizeof(SynthConfig), int(D), int(S), int(audio_centre_hz), 0 if h is None else h.size,
-                    None if h is None else h.ctypes.data, int(max_in))
-    return k, h
+    h, ntaps, address = _taps_arg(taps)
+    return SynthConfig(C.sizeof(SynthConfig), int(D), int(S), int(audio_centre_hz), ntaps, address, int(max_in)), h
 
 
 def _iq_format(fmt):
@@ -2163,11 +2155,9 @@ def host_synth_tables(D, channel, taps=None, audio_centre_hz=1472, want_phasor=F
     """one channel's tables as the device reads them: (q complex128 [T], the tap table of its sideband; P complex128 [D]; G) and, with
     want_phasor, W complex128 [48000]"""
     k, keep = synth_config(D, 1, taps, audio_centre_hz)
-    T = keep.size if keep is not None else CHAN_DEFAULT_TP * max(int(D), 0) + 1
+    T, W = _plan_tables(D, keep, want_phasor)
     q, P, G = np.zeros(T, np.complex128), np.zeros(max(int(D), 1), np.complex128), C.c_double()
-    W = np.zeros(CHAN_PHASOR_LEN, np.complex128) if want_phasor else None
-    if load_library().mgpu_host_synth_tables(C.byref(k), chan_channels([channel]), _ptr(q), _ptr(P), C.byref(G), _ptr(W)) != 0:
-        raise MgpuError("mgpu_host_synth_tables: bad argument", 1)
+    _twin(load_library().mgpu_host_synth_tables, C.byref(k), chan_channels([channel]), _ptr(q), _ptr(P), C.byref(G), _ptr(W), code=1)
     return (q, P, G.value, W) if want_phasor else (q, P, G.value)
 
 
@@ -2182,8 +2172,7 @@ def host_synth_process(D, channels, audio, position=0, fmt="cf64", taps=None, au
     ptr, stride, n_in, _a = _synth_audio(audio, len(chs))
     out = _iq_empty(f, max(n_in * max(int(D), 1), 1))
     clamped = C.c_uint64()
-    if load_library().mgpu_host_synth_process(C.byref(k), chs, ptr, stride, n_in, int(position), f, _ptr(out), C.byref(clamped)) != 0:
-        raise MgpuError("mgpu_host_synth_process: bad argument", 1)
+    _twin(load_library().mgpu_host_synth_process, C.byref(k), chs, ptr, stride, n_in, int(position), f, _ptr(out), C.byref(clamped), code=1)
     return (out, clamped.value) if want_clamped else out
 
 

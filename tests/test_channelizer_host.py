@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import channelizer_ref as cz
-from mercury_amd import (CHANNELIZER_SYMBOLS, MgpuError, chan_channels, chan_config, host_chan_design, host_chan_process, host_chan_tables,
+from band_links import create_without_a_context, iq as _iq, refused as _refused
+from mercury_amd import (CHANNELIZER_SYMBOLS, chan_channels, chan_config, host_chan_design, host_chan_process, host_chan_tables,
                          load_library)
 from mercury_amd.physical_layer import ChanConfig
 
@@ -42,13 +43,6 @@ def test_default_design_meets_its_mask(D):
     n = C.c_int()
     assert load_library().mgpu_host_chan_default_taps(D, taps.ctypes.data_as(C.c_void_p), C.byref(n)) == 0
     assert n.value == h.size and np.array_equal(taps, h)
-
-
-def _iq(rng, n, fmt):
-    if fmt == "cs16":
-        return rng.integers(-2 ** 15, 2 ** 15, (n, 2)).astype(np.int16)
-    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
-    return x.astype(np.complex64 if fmt == "cf32" else np.complex128)
 
 
 CHANNELS = {1: [(-9000, 0, 1.0), (0, 0, 0.5), (7001, 1, 2.0), (-20000, 0, 1.0)],
@@ -138,12 +132,6 @@ def test_a_retuned_channel_has_a_fresh_channels_tables():
     assert np.array_equal(both[1], host_chan_process(D, [(-5000, 1, 2.0)], iq, taps=h)[0])
 
 
-def _refused(fn):
-    with pytest.raises(MgpuError) as e:
-        fn()
-    assert e.value.code == 1
-
-
 def test_refusals_need_no_device():
     D = 4
     iq = _iq(np.random.default_rng(1), 16 * D, "cf64")
@@ -168,20 +156,23 @@ def test_refusals_need_no_device():
 def test_create_without_a_device_refuses_bad_arguments_and_reports_the_device():
     """without a context (no device could be opened: tests/test_abi.py) a bad configuration is still MGPU_ERR_ARG, a good one MGPU_ERR_DEVICE"""
     lib = load_library()
-    out = C.c_void_p()
+
+    def create(k, chs):
+        return create_without_a_context(lib.mgpu_chan_create, C.byref(k), chs)     # and the handle is null
+
     chs = chan_channels([(0, 0, 1.0), (3000, 1, 1.0)])
     k, _ = chan_config(4, 2)
-    assert lib.mgpu_chan_create(None, C.byref(k), chs, C.byref(out)) == 2 and not out.value       # MGPU_ERR_DEVICE
+    assert create(k, chs) == 2                                                                     # MGPU_ERR_DEVICE
     for change in (dict(struct_size=44), dict(D=0), dict(D=65), dict(S=0), dict(audio_centre_hz=0), dict(max_out=-1)):
         k, _ = chan_config(4, 2)
         for name, v in change.items():
             setattr(k, name, v)
-        assert lib.mgpu_chan_create(None, C.byref(k), chs, C.byref(out)) == 1, change              # MGPU_ERR_ARG
+        assert create(k, chs) == 1, change                                                         # MGPU_ERR_ARG
     k, keep = chan_config(4, 2, taps=np.ones(14))
-    assert lib.mgpu_chan_create(None, C.byref(k), chs, C.byref(out)) == 1
+    assert create(k, chs) == 1
     k, _ = chan_config(4, 2)
-    assert lib.mgpu_chan_create(None, C.byref(k), chan_channels([(0, 0, 1.0), (96000, 0, 1.0)]), C.byref(out)) == 1
-    assert lib.mgpu_chan_create(None, C.byref(k), None, C.byref(out)) == 1
+    assert create(k, chan_channels([(0, 0, 1.0), (96000, 0, 1.0)])) == 1
+    assert create(k, None) == 1
     assert lib.mgpu_chan_latency(None) < 0 and lib.mgpu_chan_destroy(None) == 1 and lib.mgpu_chan_seek(None, 0) == 1
 
 

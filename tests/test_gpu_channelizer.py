@@ -5,55 +5,21 @@ every format from host and device memory; chunk invariance; positions; retuning;
 The FIR kernel's output tile is TILE = 128 outputs per workgroup (64 lanes of 2 consecutive outputs, D <= 32), four channels per
 workgroup; at D = 16 the default filter's 5137 steps go through the LDS image in blocks of 1024 (tests/test_channelizer_host.py pins
 the twin itself)."""
+import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
 import channelizer_ref as cz
-from mercury_amd import Channelizer, MgpuError, RxCapture, RxPhy, host_chan_design, host_chan_process
+from band_links import FIRST_STARTS, ThreeLinks, bits as _bits, channels as _channels, iq as _iq, last_error, other_rx, rx as _rx, \
+    taps as _taps, torch as _torch
+from mercury_amd import (Channelizer, MgpuError, Resampler, RxCapture, Synthesizer, chan_channels, chan_config, host_chan_process,
+                         host_resamp_process, host_synth_process, resamp_config, synth_config)
 from oraclelib import CARRIER
 
 pytestmark = pytest.mark.gpu
-MAX_ITERS = 10
 TILE = 128
-
-
-def _torch():
-    import torch
-    return torch
-
-
-@functools.lru_cache(maxsize=None)
-def _rx():
-    return RxPhy(8, max_iters=MAX_ITERS, max_batch=8)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def _iq(rng, n, fmt):
-    if fmt == "cs16":
-        return rng.integers(-2 ** 15, 2 ** 15, (n, 2)).astype(np.int16)
-    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
-    return x.astype(np.complex64 if fmt == "cf32" else np.complex128)
-
-
-def _channels(rng, D, S):
-    """S channels anywhere a band fits in (-R/2, R/2): both sidebands, both signs of the offset, gains that are no powers of two"""
-    half = 24000 * D
-    out = []
-    for s in range(S):
-        sb = int(rng.integers(0, 2))
-        lo, hi = (-half + 1, half - 2945) if sb == 0 else (-half + 2945, half - 1)
-        out.append((int(rng.integers(lo, hi + 1)), sb, float(rng.uniform(0.3, 3.0))))
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def _taps(D, tp):
-    return host_chan_design(D, tp)
 
 
 @pytest.mark.parametrize("tp", [2, 320])
@@ -197,82 +163,18 @@ def test_position_and_retune():
     ch.close(), fresh.close()
 
 
-def _canon(r):
-    """a structured scalar's field bytes, without its padding (bit patterns of the doubles kept)"""
-    r = np.asarray(r)
-    return b"".join(_canon(r[n]) if r.dtype[n].names else np.asarray(r[n]).tobytes() for n in r.dtype.names)
-
-
 L_DEFAULT = 160                 # the default design's latency: tp / 2
 
 
 OFFSETS, GAINS = (-30000, -27000, 12345), (1.0, 10 ** (30 / 20.0), 1.0)
-FIRST_STARTS = (5 * 1088 + 333, 7 * 1088 + 17, 11 * 1088 + 901)        # mode 8: P = 1088
 HOPS_PER_CALL = 16
+LINKS = ThreeLinks(seed=2024, tail=L_DEFAULT, hops_per_call=HOPS_PER_CALL)
 
 
-@functools.lru_cache(maxsize=None)
-def _frames():
-    """three payloads and their transmit_byte frames (mode 8)"""
-    rx = _rx()
-    payloads = np.random.default_rng(2024).integers(0, 256, (3, rx.payload_bytes)).astype(np.uint8)
-    return payloads, rx.transmit_byte(payloads, CARRIER)
-
-
-def _audio(starts, delay=0):
-    """the three links' 48 kHz audio [3, H P]: each frame at its start sample (+ delay) in silence; H a multiple of HOPS_PER_CALL by which
-    every frame has ended, with the channeliser's latency, and some hops more"""
-    P = _rx().Nofdm * 4
-    _, frames = _frames()
-    fsz = frames.shape[1]
-    H = -(-(max(starts) + fsz + L_DEFAULT + P) // P) + 4
-    H = -(-H // HOPS_PER_CALL) * HOPS_PER_CALL
-    assert P == 1088 and all(s % P for s in starts) and H * P > max(starts) + fsz + L_DEFAULT
-    audio = np.zeros((3, H * P))
-    for s in range(3):
-        audio[s, starts[s] + delay: starts[s] + delay + fsz] = frames[s]
-    return audio
-
-
-def _run(cap, x, run):
-    """run(chunk) over x, [3, H P] audio or [H P D] IQ, in calls of HOPS_PER_CALL hops -> events (capture, hop since the start, stats
-    bytes, payload bytes)"""
-    n = x.shape[-1] // ((4 if x.ndim == 1 else 1) * cap.P * HOPS_PER_CALL)          # D = 4
-    ev = []
-    for c, part in enumerate(np.split(x, n, axis=-1)):
-        ev += [(e[0], e[1] + c * HOPS_PER_CALL, _canon(e[2]), e[3].tobytes()) for e in run(np.ascontiguousarray(part))]
-    return ev
-
-
-def _delivered(ev, payloads):
-    return {e[0] for e in ev if e[3] == payloads[e[0]].tobytes()}
-
-
-@functools.lru_cache(maxsize=None)
 def _starts_the_loop_delivers():
-    """The receive loop's own synchroniser loses a noise-free frame at some positions on its hop grid, with no channeliser anywhere:
-    fed the transmitted audio itself it delivers the frames at FIRST_STARTS but not the one at 7 P + 17 + 160 (measured; the next test
-    pins it). The channeliser's latency moves a frame by L = 160 samples on that grid, so the end-to-end test places each link's frame
-    where the loop delivers the transmitted audio DELAYED BY L: per link the first of start + 156 k, k = 0 .. 5 (residues that are no
-    multiple of P), judged by RxCapture.run on that audio alone. What is chosen by is the existing loop on a pure delay, never the
-    channeliser's output."""
-    rx = _rx()
-    P = rx.Nofdm * 4
-    payloads, _ = _frames()
-    chosen = [None] * 3
-    for k in range(6):
-        cand = tuple(FIRST_STARTS[s] + 156 * k for s in range(3))
-        cap = RxCapture(rx, 3, CARRIER, max_hops=HOPS_PER_CALL)
-        ok = _delivered(_run(cap, _audio(cand, L_DEFAULT), cap.run), payloads)
-        cap.close()
-        for s in ok:
-            if chosen[s] is None and cand[s] % P:
-                chosen[s] = cand[s]
-        if all(c is not None for c in chosen):
-            break
-    assert all(c is not None for c in chosen), ("the loop delivers no candidate of a link", chosen)
-    print("starts the loop delivers on the audio delayed by L:", chosen, [c % P for c in chosen])
-    return tuple(chosen)
+    """The channeliser's latency moves a frame by L = 160 samples on the loop's hop grid (band_links.ThreeLinks.starts_the_loop_delivers):
+    the starts at which the loop delivers the transmitted audio delayed by L"""
+    return LINKS.starts_the_loop_delivers((L_DEFAULT,))
 
 
 @functools.lru_cache(maxsize=None)
@@ -282,8 +184,8 @@ def _three_links(starts):
     16 hops per call until every frame has passed. -> the payloads, the events of run_wideband, of RxCapture.run on the twin's output
     and of RxCapture.run on the transmitted audio itself delayed by the latency (no channeliser)"""
     rx, D, S = _rx(), 4, 3
-    payloads, _ = _frames()
-    audio = _audio(starts)
+    payloads, _ = LINKS.frames()
+    audio = LINKS.audio(starts)
     iq = cz.synthesise(audio, D, OFFSETS, None, GAINS).astype(np.complex64)
     chs = [(OFFSETS[s], 0, 1.0 / GAINS[s]) for s in range(S)]
     twin = host_chan_process(D, chs, iq)
@@ -291,13 +193,21 @@ def _three_links(starts):
         print("link %d: audio error against the direct feed %.1f dB" % (s, cz.error_db(twin[s], audio[s], L_DEFAULT, 2000)))
     chan = Channelizer(rx, D, chs)
     caps = [RxCapture(rx, S, CARRIER, max_hops=HOPS_PER_CALL) for _ in range(3)]
-    ev = [_run(caps[0], iq, lambda part: caps[0].run_wideband(chan, part)), _run(caps[1], twin, caps[1].run),
-          _run(caps[2], _audio(starts, L_DEFAULT), caps[2].run)]
+    ev = [LINKS.run_in_calls(iq, lambda part: caps[0].run_wideband(chan, part), D=D), LINKS.run_in_calls(twin, caps[1].run),
+          LINKS.run_in_calls(LINKS.audio(starts, L_DEFAULT), caps[2].run)]
     for k, name in enumerate(("run_wideband", "run on the twin's output", "run on the audio delayed by L")):
         print("%s: (capture, hop, own payload)" % name, [(e[0], e[1], e[3] == payloads[e[0]].tobytes()) for e in ev[k]])
+    part = iq[: HOPS_PER_CALL * caps[0].P * D]
     with pytest.raises(MgpuError) as e:
-        RxCapture(rx, 2, CARRIER).run_wideband(chan, iq[: HOPS_PER_CALL * caps[0].P * D])     # the S of both objects must agree
+        RxCapture(rx, 2, CARRIER).run_wideband(chan, part)                                     # the S of both objects must agree
     assert e.value.code == 1
+    assert last_error(rx) == "mgpu_capture_run_wideband: the capture and the channeliser must have the same S"
+    with pytest.raises(MgpuError) as e:
+        RxCapture(other_rx(), S, CARRIER).run_wideband(chan, part)                             # and so must their contexts
+    assert e.value.code == 1
+    assert last_error(rx) == "mgpu_capture_run_wideband: the capture and the channeliser must belong to one context"
+    chan.seek(0)                                                                               # a refused call ran nothing: the stream is whole
+    assert np.array_equal(_bits(chan.process(iq[: 8 * D])), _bits(host_chan_process(D, chs, iq[: 8 * D])))
     chan.close()
     for c in caps:
         c.close()
@@ -330,7 +240,43 @@ def test_wideband_delivers_what_the_loop_delivers_on_the_audio_delayed_by_the_la
     frame at 7 P + 177 on its hop grid, not the channeliser's latency or phase."""
     payloads, got, _, direct = _three_links(FIRST_STARTS)
     assert [(e[0], e[1], e[3]) for e in got] == [(e[0], e[1], e[3]) for e in direct]
-    assert len(_delivered(got, payloads)) >= 2
+    assert len(LINKS.delivered(got)) >= 2
+
+
+def test_create_refusals_keep_their_words_and_the_smallest_stages_equal_their_twins():
+    """The three stream stages share how a handle is made: a refused configuration gives MGPU_ERR_ARG, a null handle and
+    "<function>: <reason>" as the context's last error, before any device work; the literals are the library's. Then one create / process /
+    close of each stage at the smallest shape there is (channeliser and synthesiser D = 1, tp = 2, S = 1; resampler 44100 -> 48000,
+    S = 1) equals its twin bit for bit."""
+    rx, lib = _rx(), _rx().lib
+    one = chan_channels([(0, 0, 1.0)])
+
+    def refused(create, *args):
+        h = C.c_void_p(1)
+        assert create(rx.h, *args, C.byref(h)) == 1 and not h.value
+        return last_error(rx)
+
+    assert refused(lib.mgpu_chan_create, C.byref(chan_config(65, 1)[0]), one) == "mgpu_chan_create: D must be 1..64"
+    assert refused(lib.mgpu_chan_create, C.byref(chan_config(4, 1)[0]), None) == "mgpu_chan_create: no channels"
+    assert refused(lib.mgpu_chan_create, C.byref(chan_config(4, 1)[0]), chan_channels([(96000, 0, 1.0)])) \
+        == "mgpu_chan_create: the channel's band leaves (-R/2, R/2)"
+    assert refused(lib.mgpu_synth_create, C.byref(synth_config(4, 1, max_in=-1)[0]), one) == "mgpu_synth_create: max_in * D must be 0..2^30"
+    assert refused(lib.mgpu_resamp_create, C.byref(resamp_config(48000, 48001)[0])) \
+        == "mgpu_resamp_create: rates must be >= 1 with L <= 640, M <= 640 and M <= 16 L"
+    rng = np.random.default_rng(31)
+    h, plan = _taps(1, 2), [(-5000, 1, 1.7)]
+    iq = _iq(rng, 64, "cf64")
+    ch = Channelizer(rx, 1, plan, taps=h)
+    assert np.array_equal(_bits(ch.process(iq)), _bits(host_chan_process(1, plan, iq, taps=h)))
+    ch.close()
+    audio = rng.standard_normal((1, 64))
+    sy = Synthesizer(rx, 1, plan, taps=h)
+    assert sy.process(audio).tobytes() == host_synth_process(1, plan, audio, taps=h).tobytes()
+    sy.close()
+    x = rng.standard_normal((1, 100))
+    rs = Resampler(rx, 44100, 48000)
+    assert np.array_equal(_bits(rs.process(x)), _bits(host_resamp_process(44100, 48000, x)))
+    rs.close()
 
 
 def test_create_use_destroy_gives_the_memory_back():

@@ -9,6 +9,7 @@ import functools
 import numpy as np
 import pytest
 
+from band_links import canon as _canon
 from mercury_amd import LinkSim, RxCapture, RxPhy, host_hf_stream_noise, linksim_config
 from oraclelib import CARRIER
 
@@ -16,12 +17,6 @@ pytestmark = pytest.mark.gpu
 MAX_ITERS = 10
 SEED = 0x4C53494D
 L = 256
-
-
-def _canon(r):
-    """a structured scalar's field bytes, without its padding (bit patterns of the doubles kept)"""
-    r = np.asarray(r)
-    return b"".join(_canon(r[n]) if r.dtype[n].names else np.asarray(r[n]).tobytes() for n in r.dtype.names)
 
 
 def _events(ev):

@@ -5,32 +5,15 @@ invariance with calls that produce nothing; a far position; non-finite samples; 
 
 The kernel computes Resampler.tile consecutive outputs of one stream per workgroup (mgpu_resamp_status.tile, 128) from one LDS image of
 their input span; tests/test_resampler_host.py pins the twin itself."""
-import functools
-
 import numpy as np
 import pytest
 
 import resampler_ref as rr
-from mercury_amd import MgpuError, Resampler, RxCapture, RxPhy, host_resamp_count, host_resamp_design, host_resamp_process
+from band_links import ThreeLinks, bits as _bits, events as _events, last_error, other_rx, rx as _rx, torch as _torch
+from mercury_amd import MgpuError, Resampler, RxCapture, host_resamp_count, host_resamp_design, host_resamp_process
 from oraclelib import CARRIER
 
 pytestmark = pytest.mark.gpu
-MAX_ITERS = 10
-
-
-def _torch():
-    import torch
-    return torch
-
-
-@functools.lru_cache(maxsize=None)
-def _rx():
-    return RxPhy(8, max_iters=MAX_ITERS, max_batch=8)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64)
 
 
 def _signal(rng, S, n, C, fmt="f64"):
@@ -195,83 +178,16 @@ def test_non_finite_samples_go_through_the_same_chain():
     rs.close()
 
 
-def _canon(r):
-    """a structured scalar's field bytes, without its padding (bit patterns of the doubles kept)"""
-    r = np.asarray(r)
-    return b"".join(_canon(r[n]) if r.dtype[n].names else np.asarray(r[n]).tobytes() for n in r.dtype.names)
-
-
-FIRST_STARTS = (5 * 1088 + 333, 7 * 1088 + 17, 11 * 1088 + 901)        # mode 8: P = 1088
 DELAYS = {44100: 32 * 160 / (2.0 * 147), 8000: 32 * 6 / 2.0}          # 17.41 and 96 output samples
-HOPS_PER_CALL = 15
+HOPS_PER_CALL = 15              # H P samples are whole numbers of samples at 44 100 and 8 000 Hz
+LINKS = ThreeLinks(seed=2025, tail=96, hops_per_call=HOPS_PER_CALL)    # the tail: the longest delay
 
 
-@functools.lru_cache(maxsize=None)
-def _frames():
-    rx = _rx()
-    payloads = np.random.default_rng(2025).integers(0, 256, (3, rx.payload_bytes)).astype(np.uint8)
-    return payloads, rx.transmit_byte(payloads, CARRIER)
-
-
-def _audio(starts, delay=0):
-    """the three links' 48 kHz audio [3, H P]: each frame at its start sample (+ delay) in silence; H a multiple of 15 (H P samples are
-    whole numbers of samples at 44 100 and 8 000 Hz) by which every frame has ended, with the longest delay, and some hops more"""
-    P = _rx().Nofdm * 4
-    _, frames = _frames()
-    fsz = frames.shape[1]
-    H = -(-(max(starts) + fsz + 96 + P) // P) + 4
-    H = -(-H // HOPS_PER_CALL) * HOPS_PER_CALL
-    assert P == 1088 and all(s % P for s in starts)
-    audio = np.zeros((3, H * P))
-    for s in range(3):
-        audio[s, starts[s] + delay: starts[s] + delay + fsz] = frames[s]
-    return audio
-
-
-def _events(ev, hop0):
-    return [(e[0], e[1] + hop0, _canon(e[2]), e[3].tobytes()) for e in ev]
-
-
-def _run(cap, x, hops):
-    """cap.run over x [3, H P] in calls of the given hop counts -> events with hops counted from the start"""
-    P, at, out = cap.P, 0, []
-    for H in hops:
-        if H:
-            out += _events(cap.run(np.ascontiguousarray(x[:, at * P: (at + H) * P])), at)
-            at += H
-    return out
-
-
-def _delivered(ev, payloads):
-    return {e[0] for e in ev if e[3] == payloads[e[0]].tobytes()}
-
-
-@functools.lru_cache(maxsize=None)
 def _starts_the_loop_delivers():
-    """The receive loop's own synchroniser loses a noise-free frame at some positions on its hop grid (tests/test_gpu_channelizer.py pins
-    it), and the resampler moves a frame by its delay on that grid. Per link the first of start + 156 k, k = 0 .. 5, at which
-    RxCapture.run delivers the transmitted 48 kHz audio delayed by 17, by 18 (floor and ceil of 17.41, the delay at 44 100 Hz) and by 96
-    samples (the delay at 8 000 Hz): judged by the existing loop on pure delays, never by the resampler's output."""
-    rx = _rx()
-    payloads, _ = _frames()
-    delays = sorted({int(np.floor(d)) for d in DELAYS.values()} | {int(np.ceil(d)) for d in DELAYS.values()})
-    chosen = [None] * 3
-    for k in range(6):
-        cand = tuple(FIRST_STARTS[s] + 156 * k for s in range(3))
-        ok = {0, 1, 2}
-        for d in delays:
-            cap = RxCapture(rx, 3, CARRIER, max_hops=HOPS_PER_CALL)
-            a = _audio(cand, d)
-            ok &= _delivered(_run(cap, a, [HOPS_PER_CALL] * (a.shape[1] // (cap.P * HOPS_PER_CALL))), payloads)
-            cap.close()
-        for s in ok:
-            if chosen[s] is None and cand[s] % 1088:
-                chosen[s] = cand[s]
-        if all(c is not None for c in chosen):
-            break
-    assert all(c is not None for c in chosen), ("the loop delivers no candidate of a link", chosen)
-    print("starts the loop delivers on the audio delayed by", delays, ":", chosen)
-    return tuple(chosen)
+    """The resampler moves a frame by its delay on the loop's hop grid (band_links.ThreeLinks.starts_the_loop_delivers): the starts at
+    which the loop delivers the transmitted 48 kHz audio delayed by 17, by 18 (floor and ceil of 17.41, the delay at 44 100 Hz) and by 96
+    samples (the delay at 8 000 Hz)"""
+    return LINKS.starts_the_loop_delivers(tuple(sorted({int(np.floor(d)) for d in DELAYS.values()} | {int(np.ceil(d)) for d in DELAYS.values()})))
 
 
 @pytest.mark.parametrize("fin", [44100, 8000])
@@ -281,8 +197,8 @@ def test_three_links_end_to_end_through_the_receive_loop(fin):
     exactly those of RxCapture.run on the twin's whole output cut into the same hops; (b) no capture reports a CRC-good payload that is
     not its link's; (c) every link is delivered (the starts are those of _starts_the_loop_delivers)."""
     rx = _rx()
-    payloads, _ = _frames()
-    audio = _audio(_starts_the_loop_delivers())
+    payloads, _ = LINKS.frames()
+    audio = LINKS.audio(_starts_the_loop_delivers())
     x = rr.fft_resample(audio, 48000, fin).astype(np.float32)
     n = x.shape[1]
     twin = host_resamp_process(fin, 48000, x)
@@ -303,7 +219,7 @@ def test_three_links_end_to_end_through_the_receive_loop(fin):
         at, i = at + c, i + 1
     P = caps[0].P
     assert sum(hops) == twin.shape[1] // P and rs.info().fifo == twin.shape[1] % P
-    want = _run(caps[1], twin, hops)
+    want = LINKS.run_in_calls(twin, caps[1].run, hops)
     print("run_resampled: (capture, hop, own payload)", [(e[0], e[1], e[3] == payloads[e[0]].tobytes()) for e in got])
     rs.close()
     for c in caps:
@@ -317,21 +233,29 @@ def test_three_links_end_to_end_through_the_receive_loop(fin):
 
 
 def test_run_resampled_refuses_what_does_not_fit_the_loop():
-    """another S, C = 2 or fout != 48000 gives MGPU_ERR_ARG, and so does a format that is no capture format"""
+    """another S, C = 2, fout != 48000 or a capture of another context gives MGPU_ERR_ARG, and so does a format that is no capture format;
+    every refusal leaves its words as the resampler's context's last error, and the resampler where it was"""
     rx = _rx()
     cap = RxCapture(rx, 3, CARRIER)
     x = np.zeros((3, 500), np.float32)
+    does_not_pair = "mgpu_capture_run_resampled: one context, the same S, components = 1 and fout = 48000"
     for kw in (dict(S=2), dict(S=3, components=2), dict(S=3, fout=44100)):
         kw = dict(dict(fout=48000), **kw)
         rs = Resampler(rx, 48000 if kw["fout"] != 48000 else 44100, **kw)
         with pytest.raises(MgpuError) as e:
             cap.run_resampled(rs, x)
-        assert e.value.code == 1
+        assert e.value.code == 1 and last_error(rx) == does_not_pair
         rs.close()
     rs = Resampler(rx, 44100, S=3)
+    elsewhere = RxCapture(other_rx(), 3, CARRIER)                      # a capture on a second context of the same device
+    with pytest.raises(MgpuError) as e:
+        elsewhere.run_resampled(rs, x)
+    assert e.value.code == 1 and last_error(rx) == does_not_pair
+    elsewhere.close()
     n, hops = np.zeros(1, np.int32), np.zeros(1, np.int32)
     assert rx.lib.mgpu_capture_run_resampled(cap.h, rs.h, x.ctypes.data, 7, 500, None, None, 0, n.ctypes.data, hops.ctypes.data) == 1
-    assert rs.info().m0 == 0
+    assert last_error(rx) == "the format does not fit the components"
+    assert rs.info().m0 == 0 and rs.info().fifo == 0
     ev, H = cap.run_resampled(rs, x)                                   # 500 inputs: 545 outputs, no hop yet
     assert (ev, H) == ([], 0) and rs.info().fifo == 545
     rs.close(), cap.close()

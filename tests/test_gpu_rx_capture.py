@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import capture_ref as cr
+from band_links import canon as _canon
 from mercury_amd import RxCapture, RxPhy
 from mercury_amd.physical_layer import host_capture_init_state, host_capture_process
 from oraclelib import MODE_REFERENCE, RefTelecomSystemGpu
@@ -57,12 +58,6 @@ def test_device_windows_equal_the_host_twin(fmt, on_device):
         assert st["data_ready"] == 1 and st["frames_to_read"] == 0 and st["n_under"] == n_feeds * H - 1
         cap.close()
     rx.close()
-
-
-def _canon(r):
-    """a structured scalar's field bytes, without its padding (bit patterns of the doubles kept)"""
-    r = np.asarray(r)
-    return b"".join(_canon(r[n]) if r.dtype[n].names else np.asarray(r[n]).tobytes() for n in r.dtype.names)
 
 
 def _compare_held(cfg, where, st, held, attempted):

@@ -5,29 +5,17 @@ and device memory; chunk invariance; positions; retuning; three links end to end
 The kernel's tile is TILE = 64 audio positions per workgroup (one per lane) and a group of 4 phases (D = 1: 1, D = 2: 2), so D = 3 and
 D = 33 leave a group partly used and D = 64 has 16 groups; ROUND = 4 channels are in flight per workgroup, so S = 5 and 9 take two and
 three rounds, the last with one channel."""
-import functools
-
 import numpy as np
 import pytest
 
-from mercury_amd import Channelizer, MgpuError, RxCapture, Synthesizer, host_chan_design, host_synth_process
+from band_links import ThreeLinks, rx as _rx, taps as _taps, torch as _torch
+from mercury_amd import Channelizer, MgpuError, RxCapture, Synthesizer, host_synth_process
 from oraclelib import CARRIER
-from test_gpu_channelizer import FIRST_STARTS, HOPS_PER_CALL, _audio, _delivered, _frames, _run, _rx
 
 pytestmark = pytest.mark.gpu
 TILE = 64
 ROUND = 4
 POSITION = 2 ** 40 + 7
-
-
-def _torch():
-    import torch
-    return torch
-
-
-@functools.lru_cache(maxsize=None)
-def _taps(D, tp):
-    return host_chan_design(D, tp)
 
 
 def _channels(rng, D, S):
@@ -211,28 +199,8 @@ TP_DEFAULT = 320                # synthesiser -> channeliser with the default de
 OFFSETS, SIDEBANDS, GAINS = (-30000, -27000, 12345), (0, 0, 1), (1.0, 10 ** (30 / 20.0), 1.0)
 
 
-@functools.lru_cache(maxsize=None)
-def _starts_the_loop_delivers():
-    """As tests/test_gpu_channelizer.py chooses its frame starts: the receive loop's own synchroniser loses a noise-free frame at some
-    positions on its hop grid, so each link's frame goes where the loop delivers the transmitted audio DELAYED BY tp: per link the first
-    of start + 156 k, k = 0 .. 5, judged by RxCapture.run on that audio alone, never by the synthesiser's output."""
-    rx = _rx()
-    P = rx.Nofdm * 4
-    payloads, _ = _frames()
-    chosen = [None] * 3
-    for k in range(6):
-        cand = tuple(FIRST_STARTS[s] + 156 * k for s in range(3))
-        cap = RxCapture(rx, 3, CARRIER, max_hops=HOPS_PER_CALL)
-        ok = _delivered(_run(cap, _audio(cand, TP_DEFAULT), cap.run), payloads)
-        cap.close()
-        for s in ok:
-            if chosen[s] is None and cand[s] % P:
-                chosen[s] = cand[s]
-        if all(c is not None for c in chosen):
-            break
-    assert all(c is not None for c in chosen), ("the loop delivers no candidate of a link", chosen)
-    print("starts the loop delivers on the audio delayed by tp:", chosen)
-    return tuple(chosen)
+HOPS_PER_CALL = 16
+LINKS = ThreeLinks(seed=2024, tail=TP_DEFAULT // 2, hops_per_call=HOPS_PER_CALL)     # the frames and the hops of tests/test_gpu_channelizer.py
 
 
 def test_three_links_end_to_end_through_the_channeliser_and_the_receive_loop():
@@ -242,10 +210,10 @@ def test_three_links_end_to_end_through_the_channeliser_and_the_receive_loop():
     payload) are those of captures fed the transmitted audio itself delayed by tp samples."""
     torch = _torch()
     rx, D, S = _rx(), 4, 3
-    starts = _starts_the_loop_delivers()
-    payloads, frames = _frames()
+    starts = LINKS.starts_the_loop_delivers((TP_DEFAULT,))             # where the loop delivers the audio delayed by tp
+    payloads, frames = LINKS.frames()
     fsz = frames.shape[1]
-    direct = _audio(starts, TP_DEFAULT)
+    direct = LINKS.audio(starts, TP_DEFAULT)
     n = direct.shape[1]
     d_payloads = torch.from_numpy(payloads).cuda()
     d_audio = torch.zeros((S, n), dtype=torch.float64, device="cuda")
@@ -268,7 +236,7 @@ def test_three_links_end_to_end_through_the_channeliser_and_the_receive_loop():
     for c in range(n // step):
         sy.process(d_audio[:, c * step: (c + 1) * step], fmt="cf32", out=d_iq)          # the context's stream, as run_wideband's
         got += [(e[0], e[1] + c * HOPS_PER_CALL, e[3].tobytes()) for e in caps[0].run_wideband(ch, d_iq)]
-    want = [(e[0], e[1], e[3]) for e in _run(caps[1], direct, caps[1].run)]
+    want = [(e[0], e[1], e[3]) for e in LINKS.run_in_calls(direct, caps[1].run)]
     print("through the band: (capture, hop, own payload)", [(e[0], e[1], e[2] == payloads[e[0]].tobytes()) for e in got])
     print("the audio delayed by tp:                     ", [(e[0], e[1], e[2] == payloads[e[0]].tobytes()) for e in want])
     assert got == want

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import resampler_ref as rr
+from band_links import create_without_a_context
 from mercury_amd import MgpuError, host_resamp_count, host_resamp_design, host_resamp_process, load_library, resamp_config
 
 TABLED_IDS = ["%d-%d" % (fin, fout) for fin, fout, _, _ in rr.TABLED]
@@ -117,11 +118,8 @@ def test_counts_over_arbitrary_cuts_sum_to_the_whole(fin, fout):
 
 
 def _create(k):
-    """mgpu_resamp_create without a context: 1 for a refused configuration, 2 for a valid one"""
-    out = C.c_void_p()
-    rc = load_library().mgpu_resamp_create(None, C.byref(k), C.byref(out))
-    assert not out.value
-    return rc
+    """mgpu_resamp_create without a context: 1 for a refused configuration, 2 for a valid one, and a null handle"""
+    return create_without_a_context(load_library().mgpu_resamp_create, C.byref(k))
 
 
 def test_every_refusal_comes_before_any_device_work():

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import synth_ref as sr
+from band_links import create_without_a_context, refused as _refused
 from mercury_amd import (SYNTH_SYMBOLS, MgpuError, chan_channels, host_chan_design, host_chan_process, host_synth_process, host_synth_tables,
                          load_library, synth_config)
 from mercury_amd.physical_layer import SynthConfig, SynthState
@@ -129,12 +130,6 @@ def test_cutting_the_stream_at_a_seek():
     assert whole[cut * D:].tobytes() != host_synth_process(D, chs, audio[:, cut:], position=POSITION + cut, taps=h).tobytes()
 
 
-def _refused(fn):
-    with pytest.raises(MgpuError) as e:
-        fn()
-    assert e.value.code == 1
-
-
 def test_refusals_need_no_device():
     D = 4
     audio = np.random.default_rng(1).standard_normal((1, 16))
@@ -168,20 +163,23 @@ def test_refusals_need_no_device():
 def test_create_without_a_device_refuses_bad_arguments_and_reports_the_device():
     """without a context (no device could be opened) a bad configuration is still MGPU_ERR_ARG, a good one MGPU_ERR_DEVICE"""
     lib = load_library()
-    out = C.c_void_p()
+
+    def create(k, chs):
+        return create_without_a_context(lib.mgpu_synth_create, C.byref(k), chs)    # and the handle is null
+
     chs = chan_channels([(0, 0, 1.0), (3000, 1, 1.0)])
     k, _ = synth_config(4, 2)
-    assert lib.mgpu_synth_create(None, C.byref(k), chs, C.byref(out)) == 2 and not out.value      # MGPU_ERR_DEVICE
+    assert create(k, chs) == 2                                                                     # MGPU_ERR_DEVICE
     for change in (dict(struct_size=44), dict(D=0), dict(D=65), dict(S=0), dict(audio_centre_hz=0), dict(max_in=-1)):
         k, _ = synth_config(4, 2)
         for name, v in change.items():
             setattr(k, name, v)
-        assert lib.mgpu_synth_create(None, C.byref(k), chs, C.byref(out)) == 1, change             # MGPU_ERR_ARG
+        assert create(k, chs) == 1, change                                                         # MGPU_ERR_ARG
     k, keep = synth_config(4, 2, taps=np.ones(14))
-    assert lib.mgpu_synth_create(None, C.byref(k), chs, C.byref(out)) == 1
+    assert create(k, chs) == 1
     k, _ = synth_config(4, 2)
-    assert lib.mgpu_synth_create(None, C.byref(k), chan_channels([(0, 0, 1.0), (96000, 0, 1.0)]), C.byref(out)) == 1
-    assert lib.mgpu_synth_create(None, C.byref(k), None, C.byref(out)) == 1
+    assert create(k, chan_channels([(0, 0, 1.0), (96000, 0, 1.0)])) == 1
+    assert create(k, None) == 1
     assert lib.mgpu_synth_latency(None) < 0 and lib.mgpu_synth_destroy(None) == 1 and lib.mgpu_synth_seek(None, 0) == 1
     assert lib.mgpu_synth_status(None, None) == 1
 
