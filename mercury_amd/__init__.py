@@ -17,7 +17,9 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              EXCISOR_SYMBOLS, EXCISOR_MODES, EXCISOR_DEFAULT, EXCISOR_REPORT_DTYPE, ExcisorParams, host_excise, parse_excisor,
                              RESAMPLER_SYMBOLS, Resampler, ResampConfig, ResampStatus, resamp_config, resamp_ratio, host_resamp_design, host_resamp_process,
                              host_resamp_count,
-                             SYNTH_SYMBOLS, Synthesizer, SynthConfig, SynthState, synth_config, host_synth_process, host_synth_tables)
+                             SYNTH_SYMBOLS, Synthesizer, SynthConfig, SynthState, synth_config, host_synth_process, host_synth_tables,
+                             SCANNER_SYMBOLS, SCAN_MAX_RUNS, SCAN_DEFAULT_THRESHOLD, SCAN_REPORT_DTYPE, SCAN_RUN_DTYPE, BandScanner, ScanConfig, ScanState, scan_config,
+                             scan_reports, host_scan_process, host_scan_plan)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -32,4 +34,6 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "EXCISOR_SYMBOLS", "EXCISOR_MODES", "EXCISOR_DEFAULT", "EXCISOR_REPORT_DTYPE", "ExcisorParams", "host_excise", "parse_excisor",
            "RESAMPLER_SYMBOLS", "Resampler", "ResampConfig", "ResampStatus", "resamp_config", "resamp_ratio", "host_resamp_design", "host_resamp_process",
            "host_resamp_count",
-           "SYNTH_SYMBOLS", "Synthesizer", "SynthConfig", "SynthState", "synth_config", "host_synth_process", "host_synth_tables"]
+           "SYNTH_SYMBOLS", "Synthesizer", "SynthConfig", "SynthState", "synth_config", "host_synth_process", "host_synth_tables",
+           "SCANNER_SYMBOLS", "SCAN_MAX_RUNS", "SCAN_DEFAULT_THRESHOLD", "SCAN_REPORT_DTYPE", "SCAN_RUN_DTYPE", "BandScanner", "ScanConfig", "ScanState", "scan_config",
+           "scan_reports", "host_scan_process", "host_scan_plan"]

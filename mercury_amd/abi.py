@@ -131,6 +131,11 @@ EXTENSIONS = {
         "mgpu_synth_retune": "i:pip", "mgpu_synth_process": "i:ppziip", "mgpu_synth_process_dev": "i:ppziipp", "mgpu_synth_status": "i:pp",
         "mgpu_host_synth_tables": "i:pppppp", "mgpu_host_synth_process": "i:pppziuipp",
     },
+    "ext/mercury_scanner.h": {
+        "mgpu_scan_create": "i:ppp", "mgpu_scan_destroy": "i:p", "mgpu_scan_seek": "i:pu", "mgpu_scan_lines": "i:pi",
+        "mgpu_scan_process": "i:ppiippp", "mgpu_scan_process_dev": "i:ppiipppp", "mgpu_scan_status": "i:pp",
+        "mgpu_host_scan_process": "i:ppiiuppp", "mgpu_host_scan_plan": "i:ppiip",
+    },
 }
 
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of

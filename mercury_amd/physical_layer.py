@@ -2225,3 +2225,145 @@ class Synthesizer(_Handle):
             raise MgpuError("out: a contiguous array of n_in * D IQ samples in the format asked for")
         self.rx._ck(self.lib.mgpu_synth_process(self.h, ptr, stride, n_in, f, optr))
         return out
+
+
+# ---- band scanner (include/ext/mercury_scanner.h) --------------------------------------------------------------------------
+SCANNER_SYMBOLS = names("ext/mercury_scanner.h")
+SCAN_MAX_RUNS = 32
+SCAN_DEFAULT_THRESHOLD = 5.0            # MGPU_SCAN_DEFAULT_THRESHOLD: measured (profiles/scanner.md)
+SCAN_RUN_DTYPE = np.dtype([("first", np.int32), ("count", np.int32), ("peak", np.int32), ("pad", np.int32), ("power", np.float64)])
+SCAN_REPORT_DTYPE = np.dtype([("first_block", np.uint64), ("level", np.float64), ("n_runs", np.int32), ("reported", np.int32),
+                              ("nonfinite", np.int32), ("pad", np.int32), ("runs", SCAN_RUN_DTYPE, (SCAN_MAX_RUNS,))])       # mgpu_scan_report
+
+
+class ScanConfig(C.Structure):          # mgpu_scan_config
+    _fields_ = [("struct_size", C.c_int), ("D", C.c_int), ("log2n", C.c_int), ("blocks_per_line", C.c_int), ("threshold", C.c_double),
+                ("edge_bins", C.c_int), ("dc_bins", C.c_int), ("gap", C.c_int), ("min_bins", C.c_int), ("max_runs", C.c_int), ("max_in", C.c_int)]
+
+
+class ScanState(C.Structure):           # mgpu_scan_state
+    _fields_ = [("position", C.c_uint64), ("blocks", C.c_uint64), ("lines", C.c_uint64), ("D", C.c_int), ("log2n", C.c_int),
+                ("blocks_per_line", C.c_int), ("max_in", C.c_int)]
+
+
+def scan_config(D, log2n=12, blocks_per_line=16, threshold=SCAN_DEFAULT_THRESHOLD, edge_bins=None, dc_bins=2, gap=2, min_bins=2,
+                max_runs=SCAN_MAX_RUNS, max_in=0):
+    """-> mgpu_scan_config; edge_bins None: N / 32"""
+    if edge_bins is None:
+        edge_bins = (1 << int(log2n)) // 32 if 0 <= int(log2n) < 31 else 0
+    return ScanConfig(C.sizeof(ScanConfig), int(D), int(log2n), int(blocks_per_line), float(threshold), int(edge_bins), int(dc_bins), int(gap),
+                      int(min_bins), int(max_runs), int(max_in))
+
+
+def scan_reports(reports):
+    """a SCAN_REPORT_DTYPE array -> [{first_block, level, n_runs, reported, nonfinite, runs: [{first, count, peak, power}]}]"""
+    return [{"first_block": int(r["first_block"]), "level": float(r["level"]), "n_runs": int(r["n_runs"]), "reported": int(r["reported"]),
+             "nonfinite": int(r["nonfinite"]),
+             "runs": [{"first": int(q["first"]), "count": int(q["count"]), "peak": int(q["peak"]), "power": float(q["power"])}
+                      for q in r["runs"][: int(r["reported"])]]} for r in reports]
+
+
+def _scan_lines_host(config, position, n_in):
+    """the lines a fresh scanner at `position` completes from n_in samples; 1 where the arguments are refused (room for nothing)"""
+    H = (1 << config.log2n) // 2 if 8 <= config.log2n <= 12 else 0
+    A = config.blocks_per_line
+    if H == 0 or A < 1 or n_in < H or n_in % H or position < 0 or position % (H * A):
+        return 1
+    return (position // H + n_in // H) // A - position // H // A
+
+
+def host_scan_process(iq, D, position=0, struct_size=None, fmt=None, **config):
+    """the twin (mgpu_host_scan_process): a fresh scanner (scan_config(D, **config)) seeked to `position` and fed `iq` whole ->
+    (lines float64 [n, N], reports SCAN_REPORT_DTYPE [n])"""
+    k = scan_config(D, **config)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    ptr, f, n_in, _x = _iq(iq)
+    room = max(_scan_lines_host(k, int(position), n_in), 1)
+    lines = np.zeros((room, 1 << min(max(k.log2n, 0), 12)))
+    reports = np.zeros(room, SCAN_REPORT_DTYPE)
+    n = C.c_int()
+    _twin(load_library().mgpu_host_scan_process, C.byref(k), ptr, f if fmt is None else fmt, n_in, int(position), _ptr(lines), _ptr(reports),
+          C.byref(n), code=1)
+    return lines[: n.value], reports[: n.value]
+
+
+def host_scan_plan(run, D, log2n=12, sideband=0, audio_centre_hz=1472):
+    """one run ({first, count, ..}) as a channel tuple (offset_hz, sideband, 1.0) (mgpu_host_scan_plan)"""
+    k = scan_config(D, log2n=log2n)
+    r = np.zeros(1, SCAN_RUN_DTYPE)
+    r["first"], r["count"] = int(run["first"]), int(run["count"])
+    ch = ChanChannel()
+    _twin(load_library().mgpu_host_scan_plan, C.byref(k), _ptr(r), int(sideband), int(audio_centre_hz), C.byref(ch), code=1)
+    return ch.offset_hz, ch.sideband, ch.gain
+
+
+class BandScanner(_Handle):
+    """One wideband IQ stream at 48000 * D into spectrum lines of N = 2^log2n bins, one per blocks_per_line blocks of N / 2 samples, and per
+    line a report of the occupied runs, on an RxPhy context (include/ext/mercury_scanner.h). The other arguments are scan_config's.
+    process() takes complex64 / complex128 / int16 [..., 2] samples (numpy, or a torch tensor on the context's device), a multiple of
+    N / 2 of them."""
+    _destroy = "mgpu_scan_destroy"
+
+    def __init__(self, rx, D, **config):
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
+        self.config = scan_config(D, **config)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_scan_create(rx.h, C.byref(self.config), C.byref(self.h)))
+        self.log2n, self.N, self.H, self.A = self.config.log2n, 1 << self.config.log2n, (1 << self.config.log2n) // 2, self.config.blocks_per_line
+        self.max_in = self.status().max_in
+
+    def status(self):
+        """mgpu_scan_state: position, blocks, lines, D, log2n, blocks_per_line, max_in"""
+        st = ScanState()
+        self.rx._ck(self.lib.mgpu_scan_status(self.h, C.byref(st)))
+        return st
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_scan_seek(self.h, int(position)))
+
+    def lines(self, n_in):
+        """the lines the next call of n_in samples completes; < 0: that n_in is refused"""
+        return int(self.lib.mgpu_scan_lines(self.h, int(n_in)))
+
+    def process_raw(self, iq, lines=None, reports=None, stream=None):
+        """-> (lines float64 [n, N], reports SCAN_REPORT_DTYPE [n]) as numpy arrays (a blocking call). With lines a float64 torch tensor
+        [>= n, N] and reports a uint8 torch tensor [>= n, 800] on the device, and `iq` one too: mgpu_scan_process_dev, asynchronous on
+        `stream` (None: the context's stream); returns n."""
+        ptr, fmt, n_in, _keep = _iq(iq)
+        room = max(self.lines(n_in), 0)
+        n = C.c_int()
+        if lines is not None and hasattr(lines, "data_ptr"):
+            import torch
+            if (not hasattr(iq, "data_ptr") or not hasattr(reports, "data_ptr") or lines.dtype != torch.float64 or reports.dtype != torch.uint8
+                    or not lines.is_contiguous() or not reports.is_contiguous() or lines.numel() < room * self.N
+                    or reports.numel() < room * SCAN_REPORT_DTYPE.itemsize):
+                raise MgpuError("device output: device input, a contiguous float64 tensor [n, N] and a contiguous uint8 tensor [n, %d]"
+                                % SCAN_REPORT_DTYPE.itemsize)
+            self.rx._ck(self.lib.mgpu_scan_process_dev(self.h, ptr, fmt, n_in, lines.data_ptr(), reports.data_ptr(), C.byref(n), stream))
+            return n.value
+        out, rep = np.zeros((max(room, 1), self.N)), np.zeros(max(room, 1), SCAN_REPORT_DTYPE)
+        self.rx._ck(self.lib.mgpu_scan_process(self.h, ptr, fmt, n_in, _ptr(out), _ptr(rep), C.byref(n)))
+        return out[: n.value], rep[: n.value]
+
+    def process(self, iq):
+        """-> (lines float64 [n, N], [one dict per line, as scan_reports makes them])"""
+        lines, reports = self.process_raw(iq)
+        return lines, scan_reports(reports)
+
+    def bin_hz(self, f):
+        """the frequency of bin f (fractions allowed) relative to the stream's centre"""
+        return (f - self.N / 2) * 48000.0 * self.D / self.N
+
+    def plan(self, report, sideband=0, min_hz=1800, max_hz=3200, audio_centre_hz=1472):
+        """the channels [(offset_hz, sideband, 1.0), ...] of the report's runs whose width count * R / N lies in [min_hz, max_hz], what a
+        Mercury signal's 2.4 kHz may look like; a run whose band would leave (-R/2, R/2) is left out"""
+        out = []
+        for run in report["runs"]:
+            if not min_hz <= run["count"] * 48000.0 * self.D / self.N <= max_hz:
+                continue
+            try:
+                out.append(host_scan_plan(run, self.D, self.log2n, sideband, audio_centre_hz))
+            except MgpuError:
+                pass
+        return out
