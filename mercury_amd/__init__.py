@@ -19,7 +19,9 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              host_resamp_count,
                              SYNTH_SYMBOLS, Synthesizer, SynthConfig, SynthState, synth_config, host_synth_process, host_synth_tables,
                              SCANNER_SYMBOLS, SCAN_MAX_RUNS, SCAN_DEFAULT_THRESHOLD, SCAN_REPORT_DTYPE, SCAN_RUN_DTYPE, BandScanner, ScanConfig, ScanState, scan_config,
-                             scan_reports, host_scan_process, host_scan_plan)
+                             scan_reports, host_scan_process, host_scan_plan,
+                             TUNER_SYMBOLS, TUNE_DEFAULT_MIN_METRIC, TUNE_DEFAULT_CARRIER_HZ, TUNE_REPORT_DTYPE, Tuner, TuneConfig, tune_config, tune_samples,
+                             tune_reports, host_tune_process, host_tune_plan)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -36,4 +38,6 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "host_resamp_count",
            "SYNTH_SYMBOLS", "Synthesizer", "SynthConfig", "SynthState", "synth_config", "host_synth_process", "host_synth_tables",
            "SCANNER_SYMBOLS", "SCAN_MAX_RUNS", "SCAN_DEFAULT_THRESHOLD", "SCAN_REPORT_DTYPE", "SCAN_RUN_DTYPE", "BandScanner", "ScanConfig", "ScanState", "scan_config",
-           "scan_reports", "host_scan_process", "host_scan_plan"]
+           "scan_reports", "host_scan_process", "host_scan_plan",
+           "TUNER_SYMBOLS", "TUNE_DEFAULT_MIN_METRIC", "TUNE_DEFAULT_CARRIER_HZ", "TUNE_REPORT_DTYPE", "Tuner", "TuneConfig", "tune_config", "tune_samples",
+           "tune_reports", "host_tune_process", "host_tune_plan"]

@@ -136,6 +136,11 @@ EXTENSIONS = {
         "mgpu_scan_process": "i:ppiippp", "mgpu_scan_process_dev": "i:ppiipppp", "mgpu_scan_status": "i:pp",
         "mgpu_host_scan_process": "i:ppiiuppp", "mgpu_host_scan_plan": "i:ppiip",
     },
+    "ext/mercury_tuner.h": {
+        "mgpu_tune_create": "i:pppp", "mgpu_tune_destroy": "i:p", "mgpu_tune_retune": "i:pip", "mgpu_tune_samples": "i:p",
+        "mgpu_tune_process": "i:ppiip", "mgpu_tune_arrays": "i:pppp", "mgpu_host_tune_process": "i:pppiipppp",
+        "mgpu_host_tune_plan": "i:ppp",
+    },
 }
 
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of

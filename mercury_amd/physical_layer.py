@@ -2367,3 +2367,119 @@ class BandScanner(_Handle):
             except MgpuError:
                 pass
         return out
+
+
+# ---- carrier tuner (include/ext/mercury_tuner.h) ---------------------------------------------------------------------------
+TUNER_SYMBOLS = names("ext/mercury_tuner.h")
+TUNE_DEFAULT_MIN_METRIC = 0.44          # MGPU_TUNE_DEFAULT_MIN_METRIC: measured (profiles/tuner.md)
+TUNE_DEFAULT_CARRIER_HZ = 1471.875
+TUNE_REPORT_DTYPE = np.dtype([("metric", np.float64), ("frac_hz", np.float64), ("delta_hz", np.float64), ("contrast", np.float64),
+                              ("phase", np.int32), ("shift", np.int32), ("offset_hz", np.int32), ("valid", np.int32),
+                              ("nonfinite", np.int32), ("pad", np.int32)])              # mgpu_tune_report
+
+
+class TuneConfig(C.Structure):          # mgpu_tune_config
+    _fields_ = [("struct_size", C.c_int), ("D", C.c_int), ("S", C.c_int), ("audio_centre_hz", C.c_int), ("ntaps", C.c_int),
+                ("symbols", C.c_int), ("taps", C.c_void_p), ("carrier_hz", C.c_double), ("min_metric", C.c_double), ("search", C.c_int),
+                ("pad", C.c_int)]
+
+
+def tune_config(D, S, symbols=32, search=8, taps=None, audio_centre_hz=1472, carrier_hz=TUNE_DEFAULT_CARRIER_HZ,
+                min_metric=TUNE_DEFAULT_MIN_METRIC):
+    """-> (mgpu_tune_config, keep-alive of its taps)"""
+    h, ntaps, address = _taps_arg(taps)
+    return TuneConfig(C.sizeof(TuneConfig), int(D), int(S), int(audio_centre_hz), ntaps, int(symbols), address, float(carrier_hz),
+                      float(min_metric), int(search), 0), h
+
+
+def tune_samples(D, symbols=32):
+    """n_in of one call: 4 D 272 (symbols + 1)"""
+    return 4 * int(D) * 272 * (int(symbols) + 1)
+
+
+def tune_reports(reports):
+    """a TUNE_REPORT_DTYPE array -> [{metric, phase, frac_hz, shift, delta_hz, contrast, offset_hz, valid, nonfinite}]"""
+    return [{"metric": float(r["metric"]), "phase": int(r["phase"]), "frac_hz": float(r["frac_hz"]), "shift": int(r["shift"]),
+             "delta_hz": float(r["delta_hz"]), "contrast": float(r["contrast"]), "offset_hz": int(r["offset_hz"]), "valid": int(r["valid"]),
+             "nonfinite": int(r["nonfinite"])} for r in reports]
+
+
+def host_tune_process(iq, D, channels, struct_size=None, fmt=None, want_arrays=False, **config):
+    """the twin (mgpu_host_tune_process) on one block of tune_samples(D, symbols) IQ samples -> reports TUNE_REPORT_DTYPE [S]; with
+    want_arrays also G complex128 [S, 272], E float64 [S, 272], Q float64 [S, 256]"""
+    chs = chan_channels(channels)
+    k, _keep = tune_config(D, len(chs), **config)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    ptr, f, n_in, _x = _iq(iq)
+    S = max(len(chs), 1)
+    reports = np.zeros(S, TUNE_REPORT_DTYPE)
+    G, E, Q = np.zeros((S, 272), np.complex128), np.zeros((S, 272)), np.zeros((S, 256))
+    _twin(load_library().mgpu_host_tune_process, C.byref(k), chs, ptr, f if fmt is None else fmt, n_in, _ptr(reports), _ptr(G), _ptr(E),
+          _ptr(Q), code=1)
+    return (reports, G, E, Q) if want_arrays else reports
+
+
+def host_tune_plan(reports, channels):
+    """the refined plan [(offset_hz, sideband, gain), ...] (mgpu_host_tune_plan): a report's offset where it is valid, the channel's own
+    where not; sideband and gain are kept. reports: a TUNE_REPORT_DTYPE array or the dicts tune_reports makes"""
+    chs = chan_channels(channels)
+    if len(reports) != len(chs):
+        raise MgpuError("one report per channel")
+    out = []
+    for r, ch in zip(reports, chs):
+        rep = np.zeros(1, TUNE_REPORT_DTYPE)
+        rep["offset_hz"], rep["valid"] = int(r["offset_hz"]), int(r["valid"])
+        refined = ChanChannel()
+        _twin(load_library().mgpu_host_tune_plan, _ptr(rep), C.byref(ch), C.byref(refined), code=1)
+        out.append((refined.offset_hz, refined.sideband, refined.gain))
+    return out
+
+
+class Tuner(_Handle):
+    """The channels of a plan (as chan_channels takes them) onto their stations to the hertz, on an RxPhy context
+    (include/ext/mercury_tuner.h). process() takes one block of exactly `samples` IQ samples, complex64 / complex128 / int16 [..., 2]
+    (numpy, or a torch tensor on the context's device), and returns one dict per channel; plan() turns them into the refined plan. A
+    call is one measurement and stands alone."""
+    _destroy = "mgpu_tune_destroy"
+
+    def __init__(self, rx, D, channels, symbols=32, search=8, taps=None, audio_centre_hz=1472, carrier_hz=TUNE_DEFAULT_CARRIER_HZ,
+                 min_metric=TUNE_DEFAULT_MIN_METRIC):
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
+        self._chs = chan_channels(channels)
+        self.S = len(self._chs)
+        self.config, self._taps = tune_config(D, self.S, symbols, search, taps, audio_centre_hz, carrier_hz, min_metric)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_tune_create(rx.h, C.byref(self.config), self._chs, C.byref(self.h)))
+        self.samples = int(self.lib.mgpu_tune_samples(self.h))
+
+    @property
+    def channels(self):
+        """the plan being refined"""
+        return [(ch.offset_hz, ch.sideband, ch.gain) for ch in self._chs]
+
+    def retune(self, s, channel):
+        ch = chan_channels([channel])
+        self.rx._ck(self.lib.mgpu_tune_retune(self.h, int(s), ch))
+        self._chs[int(s)] = ch[0]
+
+    def process_raw(self, iq):
+        """-> reports TUNE_REPORT_DTYPE [S] (a blocking call)"""
+        ptr, fmt, n_in, _keep = _iq(iq)
+        reports = np.zeros(self.S, TUNE_REPORT_DTYPE)
+        self.rx._ck(self.lib.mgpu_tune_process(self.h, ptr, fmt, n_in, _ptr(reports)))
+        return reports
+
+    def process(self, iq):
+        """-> [one dict per channel, as tune_reports makes them]"""
+        return tune_reports(self.process_raw(iq))
+
+    def arrays(self):
+        """the last call's G complex128 [S, 272], E float64 [S, 272], Q float64 [S, 256]"""
+        G, E, Q = np.zeros((self.S, 272), np.complex128), np.zeros((self.S, 272)), np.zeros((self.S, 256))
+        self.rx._ck(self.lib.mgpu_tune_arrays(self.h, _ptr(G), _ptr(E), _ptr(Q)))
+        return G, E, Q
+
+    def plan(self, reports):
+        """the refined plan [(offset_hz, sideband, gain), ...]: what Channelizer takes"""
+        return host_tune_plan(reports, self.channels)

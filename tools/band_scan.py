@@ -4,13 +4,17 @@ IQ and reports the occupied runs; BandScanner.plan turns them into a channel pla
 the one the links were placed with, and RxCapture.run_wideband receives through it.
 
     python tools/band_scan.py [--links 3] [--D 4] [--raster 9000] [--frames 2] [--noise-db -40] [--mode 8] [--seed 1] [--log2n 12]
-                              [--blocks-per-line 16]
+                              [--blocks-per-line 16] [--tune]
 
 Every link is USB (the scanner finds a band, not its sideband: the plan is made for the sideband the user names). One JSON line per
 link: the true offset, the found offset (of the found channel nearest to it), their difference, the run's width in bins, and the frames
 sent, delivered through the found plan and, as the control, delivered from the same IQ through the plan the links were placed with. Whether receive_byte tolerates the planning error of up to a bin is what this tool reports; nothing is asserted. Then a
 summary line. A link is silent between its frames and a line in such a pause does not show it (the detection is static per line): the
-plan is made from the line with the most power."""
+plan is made from the line with the most power.
+
+--tune adds a third pass: the found plan goes through the Tuner on the block of IQ that begins at the judged line's first sample (the
+last block that fits, should the line lie too near the end), and the links are received once more through the tuned plan. Every link's
+line gains tuned_offset_hz, tuned_error_hz, metric and delivered_through_the_tuned_plan. Without --tune the output is unchanged."""
 import argparse
 import json
 import os
@@ -20,7 +24,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mercury_amd import BandScanner, Channelizer, RxCapture, RxPhy, Synthesizer  # noqa: E402
+from mercury_amd import BandScanner, Channelizer, RxCapture, RxPhy, Synthesizer, Tuner  # noqa: E402
 
 P = 1088
 CARRIER = 1471.875
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--log2n", type=int, default=12)
     ap.add_argument("--blocks-per-line", type=int, default=16)
+    ap.add_argument("--tune", action="store_true")
     a = ap.parse_args()
     import torch
     S, D = a.links, a.D
@@ -114,19 +119,37 @@ def main():
     links = [s for s in range(S) if nearest[s] is not None]
     delivered = receive([nearest[s] for s in links], links)
     control = receive(plan, list(range(S)))                             # the same band through the plan the links were placed with
+    tuned, tuned_reports, through_tuned = {}, {}, [0] * S
+    if a.tune and links:
+        tn = Tuner(rx, D, [nearest[s] for s in links])
+        at = min(best * per_line, n * D - tn.samples)
+        reports_t = tn.process(d_iq[at: at + tn.samples])
+        for s, ch, r in zip(links, tn.plan(reports_t), reports_t):
+            tuned[s], tuned_reports[s] = ch, r
+        tn.close()
+        through_tuned = receive([tuned[s] for s in links], links)
     widths = {}                                                         # a planned channel's offset -> its run's bins
     for r in report["runs"]:
         for ch in sc.plan({"runs": [r]}, sideband=0):
             widths[ch[0]] = r["count"]
     for s in range(S):
-        print(json.dumps({"link": s, "true_offset_hz": offs[s], "found_offset_hz": nearest[s][0] if nearest[s] else None,
-                          "error_hz": nearest[s][0] - offs[s] if nearest[s] else None,
-                          "run_bins": widths.get(nearest[s][0]) if nearest[s] else None, "sent": a.frames, "delivered": delivered[s],
-                          "delivered_through_the_true_plan": control[s]}), flush=True)
-    print(json.dumps({"links": S, "D": D, "mode": a.mode, "noise_db": a.noise_db, "N": sc.N, "blocks_per_line": sc.A,
-                      "bin_hz": 48000.0 * D / sc.N, "lines": len(reports), "line_judged": best, "runs_in_it": report["n_runs"],
-                      "channels_planned": len(found), "sent": S * a.frames, "delivered": sum(delivered),
-                      "delivered_through_the_true_plan": sum(control)}), flush=True)
+        row = {"link": s, "true_offset_hz": offs[s], "found_offset_hz": nearest[s][0] if nearest[s] else None,
+               "error_hz": nearest[s][0] - offs[s] if nearest[s] else None,
+               "run_bins": widths.get(nearest[s][0]) if nearest[s] else None, "sent": a.frames, "delivered": delivered[s],
+               "delivered_through_the_true_plan": control[s]}
+        if a.tune:
+            row.update({"tuned_offset_hz": tuned[s][0] if s in tuned else None,
+                        "tuned_error_hz": tuned[s][0] - offs[s] if s in tuned else None,
+                        "metric": tuned_reports[s]["metric"] if s in tuned else None,
+                        "delivered_through_the_tuned_plan": through_tuned[s]})
+        print(json.dumps(row), flush=True)
+    summary = {"links": S, "D": D, "mode": a.mode, "noise_db": a.noise_db, "N": sc.N, "blocks_per_line": sc.A,
+               "bin_hz": 48000.0 * D / sc.N, "lines": len(reports), "line_judged": best, "runs_in_it": report["n_runs"],
+               "channels_planned": len(found), "sent": S * a.frames, "delivered": sum(delivered),
+               "delivered_through_the_true_plan": sum(control)}
+    if a.tune:
+        summary["delivered_through_the_tuned_plan"] = sum(through_tuned)
+    print(json.dumps(summary), flush=True)
     for o in (sy, sc, rx):
         o.close()
 
