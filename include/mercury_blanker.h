@@ -41,6 +41,7 @@
  * Limits: the synchroniser and the passband filter of mgpu_receive_byte_batch still see the unblanked samples (only the decode phase is
  * behind the blanker); there is no blanking at 48 kHz; there is no clipping mode (a marked sample becomes zero, never a limited value); the
  * device self-simulations have no impulse source. (Narrowband carriers are removed ahead of the synchroniser: ext/mercury_excisor.h.)
+ * On the wideband path clicks are blanked in the IQ at 48000 * D, ahead of the channeliser and every filter: ext/mercury_wideband_blanker.h.
  * Off by default (MGPU_BLANK_OFF): every entry point computes what it computed before, with the same kernels.
  */
 #ifndef MERCURY_BLANKER_H

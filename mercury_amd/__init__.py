@@ -21,7 +21,9 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              SCANNER_SYMBOLS, SCAN_MAX_RUNS, SCAN_DEFAULT_THRESHOLD, SCAN_REPORT_DTYPE, SCAN_RUN_DTYPE, BandScanner, ScanConfig, ScanState, scan_config,
                              scan_reports, host_scan_process, host_scan_plan,
                              TUNER_SYMBOLS, TUNE_DEFAULT_MIN_METRIC, TUNE_DEFAULT_CARRIER_HZ, TUNE_REPORT_DTYPE, Tuner, TuneConfig, tune_config, tune_samples,
-                             tune_reports, host_tune_process, host_tune_plan)
+                             tune_reports, host_tune_process, host_tune_plan,
+                             WBLANK_SYMBOLS, WBLANK_DEFAULT_THRESHOLD, WBLANK_DEFAULT_GUARD, WBLANK_DEFAULT_MAX_SHARE, WBLANK_REPORT_DTYPE, WidebandBlanker,
+                             WblankConfig, WblankState, wblank_config, wblank_block, wblank_reports, host_wblank_process)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -40,4 +42,6 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "SCANNER_SYMBOLS", "SCAN_MAX_RUNS", "SCAN_DEFAULT_THRESHOLD", "SCAN_REPORT_DTYPE", "SCAN_RUN_DTYPE", "BandScanner", "ScanConfig", "ScanState", "scan_config",
            "scan_reports", "host_scan_process", "host_scan_plan",
            "TUNER_SYMBOLS", "TUNE_DEFAULT_MIN_METRIC", "TUNE_DEFAULT_CARRIER_HZ", "TUNE_REPORT_DTYPE", "Tuner", "TuneConfig", "tune_config", "tune_samples",
-           "tune_reports", "host_tune_process", "host_tune_plan"]
+           "tune_reports", "host_tune_process", "host_tune_plan",
+           "WBLANK_SYMBOLS", "WBLANK_DEFAULT_THRESHOLD", "WBLANK_DEFAULT_GUARD", "WBLANK_DEFAULT_MAX_SHARE", "WBLANK_REPORT_DTYPE", "WidebandBlanker",
+           "WblankConfig", "WblankState", "wblank_config", "wblank_block", "wblank_reports", "host_wblank_process"]

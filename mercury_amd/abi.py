@@ -141,6 +141,10 @@ EXTENSIONS = {
         "mgpu_tune_process": "i:ppiip", "mgpu_tune_arrays": "i:pppp", "mgpu_host_tune_process": "i:pppiipppp",
         "mgpu_host_tune_plan": "i:ppp",
     },
+    "ext/mercury_wideband_blanker.h": {
+        "mgpu_wblank_create": "i:ppp", "mgpu_wblank_destroy": "i:p", "mgpu_wblank_seek": "i:pu", "mgpu_wblank_status": "i:pp",
+        "mgpu_wblank_process": "i:ppippp", "mgpu_wblank_process_dev": "i:ppipppp", "mgpu_host_wblank_process": "i:ppiuppp",
+    },
 }
 
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of

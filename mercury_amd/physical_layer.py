@@ -2483,3 +2483,114 @@ class Tuner(_Handle):
     def plan(self, reports):
         """the refined plan [(offset_hz, sideband, gain), ...]: what Channelizer takes"""
         return host_tune_plan(reports, self.channels)
+
+
+# ---- wideband impulse blanker (include/ext/mercury_wideband_blanker.h, DESIGN.md §3i) --------------------------------------------------
+WBLANK_SYMBOLS = names("ext/mercury_wideband_blanker.h")
+WBLANK_DEFAULT_THRESHOLD = 38.0         # MGPU_WBLANK_DEFAULT_THRESHOLD: measured (profiles/wideband_blanker.md)
+WBLANK_DEFAULT_GUARD = 4
+WBLANK_DEFAULT_MAX_SHARE = 0.125
+WBLANK_REPORT_DTYPE = np.dtype([("block", np.int64), ("level", np.float64), ("exceeding", np.int32), ("blanked", np.int32),
+                                ("capped", np.int32), ("pad", np.int32)])                # mgpu_wblank_report
+
+
+class WblankConfig(C.Structure):        # mgpu_wblank_config
+    _fields_ = [("struct_size", C.c_int), ("D", C.c_int), ("format", C.c_int), ("block", C.c_int), ("threshold", C.c_double),
+                ("max_share", C.c_double), ("guard", C.c_int), ("max_in", C.c_int)]
+
+
+class WblankState(C.Structure):         # mgpu_wblank_state
+    _fields_ = [("position", C.c_uint64), ("blocks", C.c_uint64), ("D", C.c_int), ("block", C.c_int), ("cap", C.c_int), ("max_in", C.c_int),
+                ("format", C.c_int), ("delay", C.c_int)]
+
+
+def wblank_config(D, fmt="cf64", block=0, threshold=WBLANK_DEFAULT_THRESHOLD, guard=WBLANK_DEFAULT_GUARD,
+                  max_share=WBLANK_DEFAULT_MAX_SHARE, max_in=0):
+    """-> mgpu_wblank_config; fmt 'cs16', 'cf32', 'cf64' or an MGPU_IQ_* number (an unknown number is the library's to refuse)"""
+    f = _IQ_FORMATS.get(fmt.lower(), -1) if isinstance(fmt, str) else int(fmt)
+    return WblankConfig(C.sizeof(WblankConfig), int(D), f, int(block), float(threshold), float(max_share), int(guard), int(max_in))
+
+
+def wblank_block(D, block=0):
+    """B: `block`, or the default of D, the least multiple of 64 D that is >= 256"""
+    return int(block) or -(-256 // (64 * int(D))) * 64 * int(D)
+
+
+def wblank_reports(reports):
+    """a WBLANK_REPORT_DTYPE array -> [{block, level, exceeding, blanked, capped}]"""
+    return [{"block": int(r["block"]), "level": float(r["level"]), "exceeding": int(r["exceeding"]), "blanked": int(r["blanked"]),
+             "capped": int(r["capped"])} for r in reports]
+
+
+def _iq_like(x, fmt, n):
+    """a numpy array for n IQ samples of MGPU_IQ_* fmt, shaped as the numpy input x where that holds n samples"""
+    out = _iq_empty(fmt, max(n, 1))
+    return out.reshape(x.shape) if isinstance(x, np.ndarray) and x.size == out.size and n else out
+
+
+def host_wblank_process(iq, D, position=0, struct_size=None, fmt=None, **config):
+    """the twin (mgpu_host_wblank_process): a fresh stage (wblank_config(D, the input's format, **config)) seeked to `position` and fed
+    `iq` whole -> (out, as the input; reports WBLANK_REPORT_DTYPE [n_in / B])"""
+    ptr, f, n_in, x = _iq(iq)
+    k = wblank_config(D, f if fmt is None else fmt, **config)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    B = max(wblank_block(D, k.block), 1) if 1 <= int(D) <= 64 else 1
+    out = _iq_like(x, f, n_in)
+    reports = np.zeros(max(n_in // B, 1), WBLANK_REPORT_DTYPE)
+    n = C.c_int()
+    _twin(load_library().mgpu_host_wblank_process, C.byref(k), ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n), code=1)
+    return out, reports[: n.value]
+
+
+class WidebandBlanker(_Handle):
+    """One wideband IQ stream at 48000 * D out again in its own format fmt ('cs16', 'cf32', 'cf64'), one block of B samples late, with
+    its clicks replaced by zero, on an RxPhy context (include/ext/mercury_wideband_blanker.h). The other arguments are wblank_config's.
+    process() takes complex64 / complex128 / int16 [..., 2] samples of that format (numpy, or a torch tensor on the context's device), a
+    multiple of B of them."""
+    _destroy = "mgpu_wblank_destroy"
+
+    def __init__(self, rx, D, fmt="cf64", **config):
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
+        self.config = wblank_config(D, fmt, **config)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_wblank_create(rx.h, C.byref(self.config), C.byref(self.h)))
+        st = self.status()
+        self.format, self.B, self.cap, self.max_in, self.delay = st.format, st.block, st.cap, st.max_in, st.delay
+
+    def status(self):
+        """mgpu_wblank_state: position, blocks, D, block, cap, max_in, format, delay"""
+        st = WblankState()
+        self.rx._ck(self.lib.mgpu_wblank_status(self.h, C.byref(st)))
+        return st
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_wblank_seek(self.h, int(position)))
+
+    def process_raw(self, iq, out=None, reports=None, stream=None):
+        """-> (out, as the input; reports WBLANK_REPORT_DTYPE [n_in / B]) as numpy arrays (a blocking call). With out a torch tensor of
+        the input's dtype and size on the device, and `iq` one too: mgpu_wblank_process_dev, asynchronous on `stream` (None: the
+        context's stream), the reports into `reports`, a uint8 torch tensor [>= n_in / B, 32] on the device or None; returns n_in / B."""
+        ptr, fmt, n_in, x = _iq(iq)
+        if fmt != self.format:
+            raise MgpuError("the blanker was made for IQ format %d, not %d" % (self.format, fmt))
+        n = C.c_int()
+        if out is not None and hasattr(out, "data_ptr"):
+            import torch
+            if (not hasattr(iq, "data_ptr") or out.dtype != iq.dtype or not out.is_contiguous() or out.numel() != iq.numel()
+                    or (reports is not None and (not hasattr(reports, "data_ptr") or reports.dtype != torch.uint8 or not reports.is_contiguous()
+                                                 or reports.numel() < n_in // self.B * WBLANK_REPORT_DTYPE.itemsize))):
+                raise MgpuError("device output: device input, a contiguous tensor like it and a contiguous uint8 tensor [n_in / B, %d] or None"
+                                % WBLANK_REPORT_DTYPE.itemsize)
+            self.rx._ck(self.lib.mgpu_wblank_process_dev(self.h, ptr, n_in, out.data_ptr(), reports.data_ptr() if reports is not None else None,
+                                                         C.byref(n), stream))
+            return n.value
+        host = _iq_like(x, fmt, n_in)
+        rep = np.zeros(max(n_in // self.B, 1), WBLANK_REPORT_DTYPE)
+        self.rx._ck(self.lib.mgpu_wblank_process(self.h, ptr, n_in, _ptr(host), _ptr(rep), C.byref(n)))
+        return host, rep[: n.value]
+
+    def process(self, iq):
+        """-> (out, [one dict per emitted block, as wblank_reports makes them])"""
+        out, reports = self.process_raw(iq)
+        return out, wblank_reports(reports)

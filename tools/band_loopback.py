@@ -4,7 +4,7 @@ RxCapture.run_wideband, and what each link sent and what arrived is printed. The
 with gains of their own, USB next to LSB.
 
     python tools/band_loopback.py [--links 3] [--D 4] [--raster 3000] [--gains-db 0,30,0] [--sidebands u,u,l] [--frames 4]
-                                  [--noise-db -40] [--fmt cf32] [--mode 8] [--seed 1]
+                                  [--noise-db -40] [--fmt cf32] [--mode 8] [--seed 1] [--impulses 100:60] [--wblank [thr=38,guard=4,block=256]]
     python tools/band_loopback.py --time [--shapes 16x4,256x16] [--hops 16] [--steps 20] [--warmup 3] [--window 0.3]
 
 Every link sends `--frames` frames, frame f of link s starting at hop 5 + f * (frame hops + 3) plus an offset of its own, in silence.
@@ -12,6 +12,11 @@ The audio never leaves the device. --noise-db adds white noise of that level (dB
 One JSON line per link, then a summary line. "delivered_without_the_band" is what the same receive loop delivers on the link's own audio
 delayed by tp samples, with no neighbour and no filter: the receive loop loses some noise-free frames by their position on its hop grid
 (tests/test_gpu_channelizer.py), and only what is delivered there and not through the band is the band's doing.
+
+--impulses RATE_HZ:DB adds one-sample clicks of random phase, RATE_HZ of them a second, DB above the strongest link's rms in the IQ (measured
+on that link's first frame synthesised alone), behind the noise. The band is then run click-free and clicked, and with --wblank a third
+time clicked with a WidebandBlanker (ext/mercury_wideband_blanker.h; thr, guard, block: its threshold, guard and block, each optional) in
+front of the channeliser; every link's line counts the frames delivered in each run ("delivered" is the click-free run's).
 
 --time: mgpu_synth_process_dev against mgpu_chan_process_dev at the same S, D and signal length in one run (profiles/synthesizer.md):
 per shape, `--hops` hops of 1088 samples per channel, CF32 IQ on the device, both alternating in `--rounds` rounds of at least `--steps`
@@ -27,7 +32,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mercury_amd import Channelizer, RxCapture, RxPhy, Synthesizer, device_props  # noqa: E402
+from mercury_amd import Channelizer, RxCapture, RxPhy, Synthesizer, WidebandBlanker, device_props  # noqa: E402
 
 P = 1088
 CARRIER = 1471.875
@@ -69,42 +74,98 @@ def loopback(a):
         for s in range(S):
             d_audio[s, starts[f][s]: starts[f][s] + fsz] = d_frames[s]
     sy = Synthesizer(rx, D, plan)
-    ch = Channelizer(rx, D, [(o, sb, 1.0 / g) for o, sb, g in plan])
-    cap = RxCapture(rx, S, CARRIER, max_hops=HOPS_PER_CALL)
     direct = RxCapture(rx, S, CARRIER, max_hops=HOPS_PER_CALL)          # the same loop on the audio itself, delayed as the band delays it
     d_delayed = torch.zeros_like(d_audio)
     d_delayed[:, sy.tp:] = d_audio[:, : n - sy.tp]
     step = HOPS_PER_CALL * P
     cdt = {"cf32": torch.complex64, "cf64": torch.complex128}[a.fmt]
     d_iq = torch.zeros(step * D, dtype=cdt, device="cuda")
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(a.seed)
     amp = 10 ** (a.noise_db / 20.0) if a.noise_db is not None else 0.0
-    events, alone = [], []
-    torch.cuda.synchronize()
-    for c in range(H // HOPS_PER_CALL):
-        sy.process(d_audio[:, c * step: (c + 1) * step], fmt=a.fmt, out=d_iq)
-        if amp:
+    period, click_amp, wblank = 0, 0.0, None
+    if a.impulses:
+        rate, db = (float(v) for v in a.impulses.split(":"))
+        period = int(48000.0 * D / rate)
+        strongest = int(np.argmax(gains))
+        alone_sy = Synthesizer(rx, D, [plan[strongest]])
+        power, first = 0.0, starts[0][strongest]
+        d_one = torch.zeros((1, n), dtype=torch.float64, device="cuda")
+        d_one[0, first: first + fsz] = d_audio[strongest, first: first + fsz]
+        torch.cuda.synchronize()
+        for c in range(first // step, (first + fsz + sy.tp) // step + 1):      # the strongest link's first frame, synthesised alone
+            alone_sy.process(d_one[:, c * step: (c + 1) * step], fmt=a.fmt, out=d_iq)
             rx.lib.mgpu_synchronize(rx.h, None)
-            d_iq += amp * torch.view_as_complex(torch.randn((step * D, 2), dtype=d_iq.real.dtype, device="cuda", generator=gen))
-            torch.cuda.synchronize()
-        events += [(e[0], e[1] + c * HOPS_PER_CALL, int(e[2]["crc"]), e[3].tobytes()) for e in cap.run_wideband(ch, d_iq)]
-        alone += [(e[0], e[3].tobytes()) for e in direct.run(d_delayed[:, c * step: (c + 1) * step].contiguous())]
+            power += float((d_iq.real ** 2 + d_iq.imag ** 2).sum())
+        alone_sy.close()
+        click_amp = float(np.sqrt(power / (fsz * D))) * 10 ** (db / 20.0)
+        if a.wblank is not None:
+            names = {"thr": "threshold", "guard": "guard", "block": "block"}
+            wblank = {names[k]: float(v) if k == "thr" else int(v) for k, v in (kv.split("=") for kv in a.wblank.split(",") if kv)}
+
+    def run(clicks, blank, want_alone=False):
+        """the whole signal through the band -> (events, what the loop delivers on the audio alone)"""
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(a.seed)
+        sy.seek(0)
+        ch = Channelizer(rx, D, [(o, sb, 1.0 / g) for o, sb, g in plan])
+        cap = RxCapture(rx, S, CARRIER, max_hops=HOPS_PER_CALL)
+        wb = WidebandBlanker(rx, D, a.fmt, **blank) if blank is not None else None
+        d_out = torch.zeros_like(d_iq)
+        events, alone = [], []
+        torch.cuda.synchronize()
+        for c in range(H // HOPS_PER_CALL):
+            sy.process(d_audio[:, c * step: (c + 1) * step], fmt=a.fmt, out=d_iq)
+            if amp or clicks:
+                rx.lib.mgpu_synchronize(rx.h, None)
+                if amp:
+                    d_iq.add_(amp * torch.view_as_complex(torch.randn((step * D, 2), dtype=d_iq.real.dtype, device="cuda", generator=gen)))
+                if clicks:
+                    at = torch.arange((period // 2 - c * step * D) % period, step * D, period, device="cuda")
+                    phase = 2.0 * np.pi * torch.rand(at.numel(), dtype=d_iq.real.dtype, device="cuda", generator=gen)
+                    d_iq[at] += click_amp * torch.complex(torch.cos(phase), torch.sin(phase))
+                torch.cuda.synchronize()
+            d_in = d_iq
+            if wb:
+                wb.process_raw(d_iq, d_out)                             # the context's stream, as run_wideband's
+                d_in = d_out
+            events += [(e[0], e[1] + c * HOPS_PER_CALL, int(e[2]["crc"]), e[3].tobytes()) for e in cap.run_wideband(ch, d_in)]
+            if want_alone:
+                alone += [(e[0], e[3].tobytes()) for e in direct.run(d_delayed[:, c * step: (c + 1) * step].contiguous())]
+        for o in (ch, cap, wb):
+            if o:
+                o.close()
+        return events, alone
+
+    def frames_delivered(ev, s):
+        return sum(1 for f in range(a.frames) if any(e[0] == s and e[3] == payloads[f, s].tobytes() for e in ev))
+
+    events, alone = run(False, None, True)
+    clicked = run(True, None)[0] if period else None
+    blanked = run(True, wblank)[0] if period and wblank is not None else None
     clamped = sy.status().clamped
-    total = 0
+    total, totals = 0, {"clicked": 0, "blanked": 0}
     for s in range(S):
         sent = [payloads[f, s].tobytes() for f in range(a.frames)]
         mine = [e for e in events if e[0] == s]
-        delivered = sum(1 for pl in sent if any(e[3] == pl for e in mine))
+        delivered = frames_delivered(events, s)
         without = sum(1 for pl in sent if any(e[0] == s and e[1] == pl for e in alone))
         foreign = sum(1 for e in mine if any(e[3] == payloads[f, t].tobytes() for f in range(a.frames) for t in range(S) if t != s))
         total += delivered
-        print(json.dumps({"link": s, "offset_hz": offs[s], "sideband": "lsb" if sbs[s] else "usb", "gain_db": gains_db[s % len(gains_db)],
-                          "sent": a.frames, "delivered": delivered, "delivered_without_the_band": without, "events": len(mine),
-                          "foreign_payloads": foreign}), flush=True)
-    print(json.dumps({"links": S, "D": D, "mode": a.mode, "hops": H, "fmt": a.fmt, "noise_db": a.noise_db, "sent": S * a.frames,
-                      "delivered": total, "cs16_clamped": int(clamped)}), flush=True)
-    for o in (sy, ch, cap, direct, rx):
+        line = {"link": s, "offset_hz": offs[s], "sideband": "lsb" if sbs[s] else "usb", "gain_db": gains_db[s % len(gains_db)],
+                "sent": a.frames, "delivered": delivered, "delivered_without_the_band": without, "events": len(mine),
+                "foreign_payloads": foreign}
+        for name, ev in (("clicked", clicked), ("blanked", blanked)):
+            if ev is not None:
+                line["delivered_" + name] = frames_delivered(ev, s)
+                totals[name] += line["delivered_" + name]
+        print(json.dumps(line), flush=True)
+    summary = {"links": S, "D": D, "mode": a.mode, "hops": H, "fmt": a.fmt, "noise_db": a.noise_db, "sent": S * a.frames,
+               "delivered": total, "cs16_clamped": int(clamped)}
+    if clicked is not None:
+        summary.update({"impulses": a.impulses, "click_amplitude": click_amp, "delivered_clicked": totals["clicked"]})
+    if blanked is not None:
+        summary.update({"wblank": wblank, "delivered_blanked": totals["blanked"]})
+    print(json.dumps(summary), flush=True)
+    for o in (sy, direct, rx):
         o.close()
 
 
@@ -172,6 +233,8 @@ def main():
     ap.add_argument("--mode", type=int, default=8)
     ap.add_argument("--max-iters", type=int, default=50)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--impulses", default=None, metavar="RATE_HZ:DB")
+    ap.add_argument("--wblank", nargs="?", const="", default=None, metavar="thr=..,guard=..,block=..")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--shapes", default="16x4,256x16")
     ap.add_argument("--hops", type=int, default=16)
