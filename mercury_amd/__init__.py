@@ -23,7 +23,9 @@ from .physical_layer import (CAPTURE_SYMBOLS, DEC_GBF, DEC_MINSUM, DEC_SPA, DEC_
                              TUNER_SYMBOLS, TUNE_DEFAULT_MIN_METRIC, TUNE_DEFAULT_CARRIER_HZ, TUNE_REPORT_DTYPE, Tuner, TuneConfig, tune_config, tune_samples,
                              tune_reports, host_tune_process, host_tune_plan,
                              WBLANK_SYMBOLS, WBLANK_DEFAULT_THRESHOLD, WBLANK_DEFAULT_GUARD, WBLANK_DEFAULT_MAX_SHARE, WBLANK_REPORT_DTYPE, WidebandBlanker,
-                             WblankConfig, WblankState, wblank_config, wblank_block, wblank_reports, host_wblank_process)
+                             WblankConfig, WblankState, wblank_config, wblank_block, wblank_reports, host_wblank_process,
+                             IQC_SYMBOLS, IQC_DEFAULT_MEMORY, IQC_DEFAULT_BLOCK, IQC_SKIPPED, IQC_NO_BALANCE, IQC_REPORT_DTYPE, IqCorrector, IqcConfig,
+                             IqcState, iqc_config, iqc_reports, iqc_image_db, host_iqc_process)
 
 from .shm import ShmRing  # noqa: E402
 
@@ -44,4 +46,6 @@ __all__ = ["ShmRing", "RxPhy", "RxCapture", "CAPTURE_SYMBOLS", "RxPool", "pool_s
            "TUNER_SYMBOLS", "TUNE_DEFAULT_MIN_METRIC", "TUNE_DEFAULT_CARRIER_HZ", "TUNE_REPORT_DTYPE", "Tuner", "TuneConfig", "tune_config", "tune_samples",
            "tune_reports", "host_tune_process", "host_tune_plan",
            "WBLANK_SYMBOLS", "WBLANK_DEFAULT_THRESHOLD", "WBLANK_DEFAULT_GUARD", "WBLANK_DEFAULT_MAX_SHARE", "WBLANK_REPORT_DTYPE", "WidebandBlanker",
-           "WblankConfig", "WblankState", "wblank_config", "wblank_block", "wblank_reports", "host_wblank_process"]
+           "WblankConfig", "WblankState", "wblank_config", "wblank_block", "wblank_reports", "host_wblank_process",
+           "IQC_SYMBOLS", "IQC_DEFAULT_MEMORY", "IQC_DEFAULT_BLOCK", "IQC_SKIPPED", "IQC_NO_BALANCE", "IQC_REPORT_DTYPE", "IqCorrector", "IqcConfig",
+           "IqcState", "iqc_config", "iqc_reports", "iqc_image_db", "host_iqc_process"]

@@ -145,6 +145,11 @@ EXTENSIONS = {
         "mgpu_wblank_create": "i:ppp", "mgpu_wblank_destroy": "i:p", "mgpu_wblank_seek": "i:pu", "mgpu_wblank_status": "i:pp",
         "mgpu_wblank_process": "i:ppippp", "mgpu_wblank_process_dev": "i:ppipppp", "mgpu_host_wblank_process": "i:ppiuppp",
     },
+    "ext/mercury_iq_corrector.h": {
+        "mgpu_iqc_create": "i:ppp", "mgpu_iqc_destroy": "i:p", "mgpu_iqc_seek": "i:pu", "mgpu_iqc_status": "i:pp",
+        "mgpu_iqc_process": "i:ppippp", "mgpu_iqc_process_dev": "i:ppipppp", "mgpu_host_iqc_process": "i:ppiuppp",
+        "mgpu_host_iqc_continue": "i:pppiuppp",
+    },
 }
 
 # NOT ABI: exports that no header declares and that only tests and tools call (csrc/ctx.hpp, csrc/ldpc.hip). The one letter of

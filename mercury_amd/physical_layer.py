@@ -2594,3 +2594,125 @@ class WidebandBlanker(_Handle):
         """-> (out, [one dict per emitted block, as wblank_reports makes them])"""
         out, reports = self.process_raw(iq)
         return out, wblank_reports(reports)
+
+
+# ---- IQ corrector (include/ext/mercury_iq_corrector.h, DESIGN.md §3j) -------------------------------------------------------------------
+IQC_SYMBOLS = names("ext/mercury_iq_corrector.h")
+IQC_DEFAULT_MEMORY = 1024               # MGPU_IQC_DEFAULT_MEMORY
+IQC_DEFAULT_BLOCK = 4096                # block = 0
+IQC_SKIPPED, IQC_NO_BALANCE = 1, 2      # MGPU_IQC_SKIPPED, MGPU_IQC_NO_BALANCE
+IQC_REPORT_DTYPE = np.dtype([("block", np.int64), ("dc_re", np.float64), ("dc_im", np.float64), ("skew", np.float64), ("gain", np.float64),
+                             ("flags", np.int32), ("clamped", np.int32)])                 # mgpu_iqc_report
+
+
+class IqcConfig(C.Structure):           # mgpu_iqc_config
+    _fields_ = [("struct_size", C.c_int), ("D", C.c_int), ("format", C.c_int), ("block", C.c_int), ("memory", C.c_int), ("dc", C.c_int),
+                ("balance", C.c_int), ("fixed", C.c_int), ("fixed_dc_re", C.c_double), ("fixed_dc_im", C.c_double), ("fixed_skew", C.c_double),
+                ("fixed_gain", C.c_double), ("max_in", C.c_int), ("pad", C.c_int)]
+
+
+class IqcState(C.Structure):            # mgpu_iqc_state
+    _fields_ = [("position", C.c_uint64), ("blocks", C.c_uint64), ("D", C.c_int), ("block", C.c_int), ("max_in", C.c_int), ("format", C.c_int),
+                ("lambda_", C.c_double), ("T", C.c_double * 6), ("dc_re", C.c_double), ("dc_im", C.c_double), ("skew", C.c_double),
+                ("gain", C.c_double), ("flags", C.c_int), ("pad", C.c_int)]
+
+
+def iqc_config(D, fmt="cf32", block=0, memory=IQC_DEFAULT_MEMORY, dc=1, balance=1, fixed=0, fixed_dc_re=0.0, fixed_dc_im=0.0, fixed_skew=0.0,
+               fixed_gain=1.0, max_in=0):
+    """-> mgpu_iqc_config; fmt 'cs16', 'cf32', 'cf64' or an MGPU_IQ_* number (an unknown number is the library's to refuse)"""
+    f = _IQ_FORMATS.get(fmt.lower(), -1) if isinstance(fmt, str) else int(fmt)
+    return IqcConfig(C.sizeof(IqcConfig), int(D), f, int(block), int(memory), int(dc), int(balance), int(fixed), float(fixed_dc_re),
+                     float(fixed_dc_im), float(fixed_skew), float(fixed_gain), int(max_in), 0)
+
+
+def iqc_reports(reports):
+    """an IQC_REPORT_DTYPE array -> [{block, dc_re, dc_im, skew, gain, skipped, no_balance, clamped}]"""
+    return [{"block": int(r["block"]), "dc_re": float(r["dc_re"]), "dc_im": float(r["dc_im"]), "skew": float(r["skew"]),
+             "gain": float(r["gain"]), "skipped": bool(r["flags"] & IQC_SKIPPED), "no_balance": bool(r["flags"] & IQC_NO_BALANCE),
+             "clamped": int(r["clamped"])} for r in reports]
+
+
+def iqc_image_db(skew, gain):
+    """The image ratio, in dB (station over image), of the uncorrected front end that the coefficients describe: Q' = g (Q cos(phi) +
+    I sin(phi)) with g sin(phi) = skew and g cos(phi) = 1 / gain. A station at +f comes out as K1 e^{+} + K2 e^{-} with
+    K1 = (1 + g e^{-j phi}) / 2 and K2 = (1 - g e^{+j phi}) / 2; the ratio is |K1|^2 / |K2|^2 =
+    ((1 + c)^2 + s^2) / ((1 - c)^2 + s^2), c = 1 / gain, s = skew. A perfect front end (skew 0, gain 1) gives +inf."""
+    c, s = 1.0 / float(gain), float(skew)
+    image = (1.0 - c) ** 2 + s ** 2
+    return float("inf") if image == 0.0 else 10.0 * float(np.log10(((1.0 + c) ** 2 + s ** 2) / image))
+
+
+def host_iqc_process(iq, D, position=0, struct_size=None, fmt=None, state=None, **config):
+    """the twin (mgpu_host_iqc_process): a fresh stage (iqc_config(D, the input's format, **config)) seeked to `position` and fed `iq`
+    whole -> (out, as the input; reports IQC_REPORT_DTYPE [n_in / B]). state: a float64 array [6], T before the first block, which
+    becomes T after the last (mgpu_host_iqc_continue)."""
+    ptr, f, n_in, x = _iq(iq)
+    k = iqc_config(D, f if fmt is None else fmt, **config)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    B = k.block if k.block > 0 else IQC_DEFAULT_BLOCK
+    out = _iq_like(x, f, n_in)
+    reports = np.zeros(max(n_in // B, 1), IQC_REPORT_DTYPE)
+    n = C.c_int()
+    if state is None:
+        _twin(load_library().mgpu_host_iqc_process, C.byref(k), ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n), code=1)
+    else:
+        if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.size == 6 and state.flags.c_contiguous):
+            raise MgpuError("state: a contiguous float64 array of 6", 1)
+        _twin(load_library().mgpu_host_iqc_continue, C.byref(k), _ptr(state), ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n),
+              code=1)
+    return out, reports[: n.value]
+
+
+class IqCorrector(_Handle):
+    """One wideband IQ stream at 48000 * D out again in its own format fmt ('cs16', 'cf32', 'cf64'), with no delay, less its DC offset and
+    its IQ imbalance, on an RxPhy context (include/ext/mercury_iq_corrector.h). The other arguments are iqc_config's. process() takes
+    complex64 / complex128 / int16 [..., 2] samples of that format (numpy, or a torch tensor on the context's device), a multiple of B of
+    them."""
+    _destroy = "mgpu_iqc_destroy"
+
+    def __init__(self, rx, D, fmt="cf32", **config):
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
+        self.config = iqc_config(D, fmt, **config)
+        self.h = C.c_void_p()
+        rx._ck(self.lib.mgpu_iqc_create(rx.h, C.byref(self.config), C.byref(self.h)))
+        st = self.status()
+        self.format, self.B, self.max_in, self.lambda_ = st.format, st.block, st.max_in, st.lambda_
+
+    def status(self):
+        """mgpu_iqc_state: position, blocks, D, block, max_in, format, lambda_, T [6], dc_re, dc_im, skew, gain, flags (waits for the
+        handle's earlier calls)"""
+        st = IqcState()
+        self.rx._ck(self.lib.mgpu_iqc_status(self.h, C.byref(st)))
+        return st
+
+    def seek(self, position):
+        self.rx._ck(self.lib.mgpu_iqc_seek(self.h, int(position)))
+
+    def process_raw(self, iq, out=None, reports=None, stream=None):
+        """-> (out, as the input; reports IQC_REPORT_DTYPE [n_in / B]) as numpy arrays (a blocking call). With out a torch tensor of the
+        input's dtype and size on the device, and `iq` one too: mgpu_iqc_process_dev, asynchronous on `stream` (None: the context's
+        stream), the reports into `reports`, a uint8 torch tensor [>= n_in / B, 48] on the device or None; returns n_in / B."""
+        ptr, fmt, n_in, x = _iq(iq)
+        if fmt != self.format:
+            raise MgpuError("the corrector was made for IQ format %d, not %d" % (self.format, fmt))
+        n = C.c_int()
+        if out is not None and hasattr(out, "data_ptr"):
+            import torch
+            if (not hasattr(iq, "data_ptr") or out.dtype != iq.dtype or not out.is_contiguous() or out.numel() != iq.numel()
+                    or (reports is not None and (not hasattr(reports, "data_ptr") or reports.dtype != torch.uint8 or not reports.is_contiguous()
+                                                 or reports.numel() < n_in // self.B * IQC_REPORT_DTYPE.itemsize))):
+                raise MgpuError("device output: device input, a contiguous tensor like it and a contiguous uint8 tensor [n_in / B, %d] or None"
+                                % IQC_REPORT_DTYPE.itemsize)
+            self.rx._ck(self.lib.mgpu_iqc_process_dev(self.h, ptr, n_in, out.data_ptr(), reports.data_ptr() if reports is not None else None,
+                                                      C.byref(n), stream))
+            return n.value
+        host = _iq_like(x, fmt, n_in)
+        rep = np.zeros(max(n_in // self.B, 1), IQC_REPORT_DTYPE)
+        self.rx._ck(self.lib.mgpu_iqc_process(self.h, ptr, n_in, _ptr(host), _ptr(rep), C.byref(n)))
+        return host, rep[: n.value]
+
+    def process(self, iq):
+        """-> (out, [one dict per block, as iqc_reports makes them])"""
+        out, reports = self.process_raw(iq)
+        return out, iqc_reports(reports)

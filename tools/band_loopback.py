@@ -3,8 +3,9 @@
 RxCapture.run_wideband, and what each link sent and what arrived is printed. The adjacent-channel experiment: links on a 3 kHz raster
 with gains of their own, USB next to LSB.
 
-    python tools/band_loopback.py [--links 3] [--D 4] [--raster 3000] [--gains-db 0,30,0] [--sidebands u,u,l] [--frames 4]
+    python tools/band_loopback.py [--links 3] [--D 4] [--raster 3000 | --offsets HZ,HZ,..] [--gains-db 0,30,0] [--sidebands u,u,l] [--frames 4]
                                   [--noise-db -40] [--fmt cf32] [--mode 8] [--seed 1] [--impulses 100:60] [--wblank [thr=38,guard=4,block=256]]
+                                  [--imbalance 0.83,5[,0.01,-0.01]] [--iqfix [memory=1024,block=4096]]
     python tools/band_loopback.py --time [--shapes 16x4,256x16] [--hops 16] [--steps 20] [--warmup 3] [--window 0.3]
 
 Every link sends `--frames` frames, frame f of link s starting at hop 5 + f * (frame hops + 3) plus an offset of its own, in silence.
@@ -17,6 +18,13 @@ delayed by tp samples, with no neighbour and no filter: the receive loop loses s
 on that link's first frame synthesised alone), behind the noise. The band is then run click-free and clicked, and with --wblank a third
 time clicked with a WidebandBlanker (ext/mercury_wideband_blanker.h; thr, guard, block: its threshold, guard and block, each optional) in
 front of the channeliser; every link's line counts the frames delivered in each run ("delivered" is the click-free run's).
+
+--imbalance GAIN_DB,PHASE_DEG[,DC_RE,DC_IM] impairs the synthesised IQ (behind the noise and the clicks) in numpy as a quadrature front end
+does: I' = I + DC_RE, Q' = g (Q cos(phi) + I sin(phi)) + DC_IM with g = 10^(GAIN_DB / 20); 0.83,5 is gain 1.1 and 5 degrees, an image 23.8 dB
+down. The band is then run once more, impaired (with the clicks and the blanker where those are asked for), and with --iqfix a further time
+with an IqCorrector (ext/mercury_iq_corrector.h; memory, block: each optional; the default block is the greatest of 4096, 2048 and 1024
+that divides a call) ahead of the blanker; every link's line counts the frames of those runs too, and the summary carries the corrector's
+last report.
 
 --time: mgpu_synth_process_dev against mgpu_chan_process_dev at the same S, D and signal length in one run (profiles/synthesizer.md):
 per shape, `--hops` hops of 1088 samples per channel, CF32 IQ on the device, both alternating in `--rounds` rounds of at least `--steps`
@@ -32,7 +40,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mercury_amd import Channelizer, RxCapture, RxPhy, Synthesizer, WidebandBlanker, device_props  # noqa: E402
+from mercury_amd import (Channelizer, IQC_REPORT_DTYPE, IqCorrector, RxCapture, RxPhy, Synthesizer, WidebandBlanker, device_props,  # noqa: E402
+                         iqc_image_db, iqc_reports)
 
 P = 1088
 CARRIER = 1471.875
@@ -55,6 +64,9 @@ def loopback(a):
     sbs = [sbs[s % len(sbs)] for s in range(S)]
     offs = raster(S, D, a.raster)
     offs = [o + 2944 if sb else o for o, sb in zip(offs, sbs)]           # an LSB channel's band lies below its dial frequency
+    if a.offsets:                                                       # dial offsets of the caller's in place of the raster
+        offs = [int(v) for v in a.offsets.split(",")]
+        assert len(offs) == S, "--offsets wants one offset per link"
     plan = [(offs[s], sbs[s], gains[s]) for s in range(S)]
     rx = RxPhy(a.mode, max_iters=a.max_iters, max_batch=max(8, S))
     fsz = rx.transmit_frame_samples()
@@ -101,7 +113,15 @@ def loopback(a):
             names = {"thr": "threshold", "guard": "guard", "block": "block"}
             wblank = {names[k]: float(v) if k == "thr" else int(v) for k, v in (kv.split("=") for kv in a.wblank.split(",") if kv)}
 
-    def run(clicks, blank, want_alone=False):
+    front_end, iqfix, last_report = None, None, []
+    if a.imbalance:
+        v = [float(t) for t in a.imbalance.split(",")]
+        front_end = (10 ** (v[0] / 20.0), np.radians(v[1]), v[2] if len(v) > 2 else 0.0, v[3] if len(v) > 3 else 0.0)
+        if a.iqfix is not None:
+            iqfix = {k: int(t) for k, t in (kv.split("=") for kv in a.iqfix.split(",") if kv)}
+            iqfix.setdefault("block", 4096 if D % 4 == 0 else 2048 if D % 2 == 0 else 1024)
+
+    def run(clicks, blank, want_alone=False, impaired=False, fix=None):
         """the whole signal through the band -> (events, what the loop delivers on the audio alone)"""
         gen = torch.Generator(device="cuda")
         gen.manual_seed(a.seed)
@@ -109,7 +129,9 @@ def loopback(a):
         ch = Channelizer(rx, D, [(o, sb, 1.0 / g) for o, sb, g in plan])
         cap = RxCapture(rx, S, CARRIER, max_hops=HOPS_PER_CALL)
         wb = WidebandBlanker(rx, D, a.fmt, **blank) if blank is not None else None
-        d_out = torch.zeros_like(d_iq)
+        qc = IqCorrector(rx, D, a.fmt, **fix) if fix is not None else None
+        d_out, d_fixed = torch.zeros_like(d_iq), torch.zeros_like(d_iq)
+        d_rep = torch.zeros((step * D // qc.B, IQC_REPORT_DTYPE.itemsize), dtype=torch.uint8, device="cuda") if qc else None
         events, alone = [], []
         torch.cuda.synchronize()
         for c in range(H // HOPS_PER_CALL):
@@ -123,14 +145,27 @@ def loopback(a):
                     phase = 2.0 * np.pi * torch.rand(at.numel(), dtype=d_iq.real.dtype, device="cuda", generator=gen)
                     d_iq[at] += click_amp * torch.complex(torch.cos(phase), torch.sin(phase))
                 torch.cuda.synchronize()
+            if impaired:
+                rx.lib.mgpu_synchronize(rx.h, None)
+                x = d_iq.cpu().numpy()
+                g, phi, dc_re, dc_im = front_end
+                x = ((x.real + dc_re) + 1j * (g * (x.imag * np.cos(phi) + x.real * np.sin(phi)) + dc_im)).astype(x.dtype)
+                d_iq.copy_(torch.from_numpy(x))
+                torch.cuda.synchronize()
             d_in = d_iq
+            if qc:
+                qc.process_raw(d_in, d_fixed, d_rep)                    # the context's stream, as the blanker's and run_wideband's
+                d_in = d_fixed
             if wb:
-                wb.process_raw(d_iq, d_out)                             # the context's stream, as run_wideband's
+                wb.process_raw(d_in, d_out)                             # the context's stream, as run_wideband's
                 d_in = d_out
             events += [(e[0], e[1] + c * HOPS_PER_CALL, int(e[2]["crc"]), e[3].tobytes()) for e in cap.run_wideband(ch, d_in)]
             if want_alone:
                 alone += [(e[0], e[3].tobytes()) for e in direct.run(d_delayed[:, c * step: (c + 1) * step].contiguous())]
-        for o in (ch, cap, wb):
+        if qc:
+            rx.lib.mgpu_synchronize(rx.h, None)
+            last_report[:] = iqc_reports(d_rep.cpu().numpy().reshape(-1).view(IQC_REPORT_DTYPE))[-1:]
+        for o in (ch, cap, wb, qc):
             if o:
                 o.close()
         return events, alone
@@ -141,8 +176,11 @@ def loopback(a):
     events, alone = run(False, None, True)
     clicked = run(True, None)[0] if period else None
     blanked = run(True, wblank)[0] if period and wblank is not None else None
+    fullest = wblank if period and wblank is not None else None
+    impaired = run(bool(period), fullest, impaired=True)[0] if front_end else None
+    corrected = run(bool(period), fullest, impaired=True, fix=iqfix)[0] if front_end and iqfix is not None else None
     clamped = sy.status().clamped
-    total, totals = 0, {"clicked": 0, "blanked": 0}
+    total, totals = 0, {"clicked": 0, "blanked": 0, "impaired": 0, "corrected": 0}
     for s in range(S):
         sent = [payloads[f, s].tobytes() for f in range(a.frames)]
         mine = [e for e in events if e[0] == s]
@@ -153,7 +191,7 @@ def loopback(a):
         line = {"link": s, "offset_hz": offs[s], "sideband": "lsb" if sbs[s] else "usb", "gain_db": gains_db[s % len(gains_db)],
                 "sent": a.frames, "delivered": delivered, "delivered_without_the_band": without, "events": len(mine),
                 "foreign_payloads": foreign}
-        for name, ev in (("clicked", clicked), ("blanked", blanked)):
+        for name, ev in (("clicked", clicked), ("blanked", blanked), ("impaired", impaired), ("corrected", corrected)):
             if ev is not None:
                 line["delivered_" + name] = frames_delivered(ev, s)
                 totals[name] += line["delivered_" + name]
@@ -164,6 +202,12 @@ def loopback(a):
         summary.update({"impulses": a.impulses, "click_amplitude": click_amp, "delivered_clicked": totals["clicked"]})
     if blanked is not None:
         summary.update({"wblank": wblank, "delivered_blanked": totals["blanked"]})
+    if impaired is not None:
+        g, phi = front_end[0], front_end[1]
+        summary.update({"imbalance": a.imbalance, "image_db": round(iqc_image_db(g * np.sin(phi), 1.0 / (g * np.cos(phi))), 2),
+                        "delivered_impaired": totals["impaired"]})
+    if corrected is not None:
+        summary.update({"iqfix": iqfix, "delivered_corrected": totals["corrected"], "iqfix_last_report": last_report[0]})
     print(json.dumps(summary), flush=True)
     for o in (sy, direct, rx):
         o.close()
@@ -225,6 +269,7 @@ def main():
     ap.add_argument("--links", type=int, default=3)
     ap.add_argument("--D", type=int, default=4)
     ap.add_argument("--raster", type=int, default=3000)
+    ap.add_argument("--offsets", default=None, metavar="HZ,HZ,..")
     ap.add_argument("--gains-db", default="0,30,0")
     ap.add_argument("--sidebands", default="u,u,l")
     ap.add_argument("--frames", type=int, default=4)
@@ -235,6 +280,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--impulses", default=None, metavar="RATE_HZ:DB")
     ap.add_argument("--wblank", nargs="?", const="", default=None, metavar="thr=..,guard=..,block=..")
+    ap.add_argument("--imbalance", default=None, metavar="GAIN_DB,PHASE_DEG[,DC_RE,DC_IM]")
+    ap.add_argument("--iqfix", nargs="?", const="", default=None, metavar="memory=..,block=..")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--shapes", default="16x4,256x16")
     ap.add_argument("--hops", type=int, default=16)
