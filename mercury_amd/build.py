@@ -18,7 +18,7 @@ TABLES = os.path.join(HERE, "data", "mercury_ldpc_tables.bin")
 
 HIP_SOURCES = ["create.hip", "launch.hip", "rx_batch.hip", "sync_api.hip", "selfsim.hip", "rxloop.hip", "stages_api.hip", "stages.hip", "frontend.hip", "mfsk.hip", "ldpc.hip", "txgen.hip", "tx.hip", "stats.hip", "sync.hip", "hfchannel.hip", "capture.hip", "linksim.hip", "ladder.hip", "combine.hip", "demapper.hip", "cfo.hip", "blanker.hip", "channelizer.hip", "excisor.hip", "resampler.hip", "synth.hip", "scanner.hip", "tuner.hip", "wideband_blanker.hip", "iq_corrector.hip"]
 CXX_SOURCES = ["tables.cpp", "shm_transport.cpp", "pool.cpp", "numa.cpp", "libm_check.cpp", "cfo_rule.cpp", "wiener_tables.cpp", "chan_tables.cpp", "resamp_tables.cpp", "synth_tables.cpp"]
-HEADERS = ["device_tables.h", "tables.hpp", "numa.hpp", "spa_math.h", "fft256.h", "fe_math.h", "glibc_trig.h", "glibc_trig_tables.h", "ctx.hpp", "geometry_cache.hpp", "stream_stage.hpp", "sample_formats.h", "philox.h", "ls_rect.h", "chan_tables.hpp", "resamp_tables.hpp", "synth_tables.hpp", "scan_rule.hpp", "scan_fft.h", "tune_rule.hpp", "wblank_rule.hpp", "iqc_rule.hpp", os.path.join(ROOT, "include", "ext", "mercury_iq_corrector.h"), os.path.join(ROOT, "include", "ext", "mercury_wideband_blanker.h"), os.path.join(ROOT, "include", "ext", "mercury_tuner.h"), os.path.join(ROOT, "include", "ext", "mercury_scanner.h"), os.path.join(ROOT, "include", "ext", "mercury_synth.h"), os.path.join(ROOT, "include", "ext", "mercury_resampler.h"), os.path.join(ROOT, "include", "mercury_channelizer.h"), os.path.join(ROOT, "include", "mercury_estimator.h"), os.path.join(ROOT, "include", "mercury_wiener_bank.h"), os.path.join(ROOT, "include", "mercury_diversity.h"), os.path.join(ROOT, "include", "mercury_demapper.h"), os.path.join(ROOT, "include", "mercury_cfo.h"), os.path.join(ROOT, "include", "mercury_blanker.h"), os.path.join(ROOT, "include", "ext", "mercury_excisor.h"), os.path.join(ROOT, "include", "mercury_gpu.h"),
+HEADERS = ["device_tables.h", "tables.hpp", "numa.hpp", "spa_math.h", "fft256.h", "fe_math.h", "glibc_trig.h", "glibc_trig_tables.h", "ctx.hpp", "geometry_cache.hpp", "stream_stage.hpp", "sample_formats.h", "iq_stream_rule.hpp", "philox.h", "ls_rect.h", "chan_tables.hpp", "resamp_tables.hpp", "synth_tables.hpp", "scan_rule.hpp", "scan_fft.h", "tune_rule.hpp", "wblank_rule.hpp", "iqc_rule.hpp", os.path.join(ROOT, "include", "ext", "mercury_iq_corrector.h"), os.path.join(ROOT, "include", "ext", "mercury_wideband_blanker.h"), os.path.join(ROOT, "include", "ext", "mercury_tuner.h"), os.path.join(ROOT, "include", "ext", "mercury_scanner.h"), os.path.join(ROOT, "include", "ext", "mercury_synth.h"), os.path.join(ROOT, "include", "ext", "mercury_resampler.h"), os.path.join(ROOT, "include", "mercury_channelizer.h"), os.path.join(ROOT, "include", "mercury_estimator.h"), os.path.join(ROOT, "include", "mercury_wiener_bank.h"), os.path.join(ROOT, "include", "mercury_diversity.h"), os.path.join(ROOT, "include", "mercury_demapper.h"), os.path.join(ROOT, "include", "mercury_cfo.h"), os.path.join(ROOT, "include", "mercury_blanker.h"), os.path.join(ROOT, "include", "ext", "mercury_excisor.h"), os.path.join(ROOT, "include", "mercury_gpu.h"),
            os.path.join(ROOT, "include", "mercury_shm.h"), os.path.join(ROOT, "include", "mercury_rxloop.h"), os.path.join(ROOT, "include", "mercury_stages.h"),
            os.path.join(ROOT, "include", "mercury_tx.h"), os.path.join(ROOT, "include", "mercury_pool.h"),
            os.path.join(ROOT, "include", "mercury_channel.h"), os.path.join(ROOT, "include", "mercury_capture.h"), os.path.join(ROOT, "include", "mercury_linksim.h"),

@@ -186,7 +186,7 @@ struct mgpu_chan {
 
     void check_n_in(const void* iq, int format, int n_in, const void* out) const {
         need(iq && out, "null pointer");
-        need(mgpu_fmt::element(2, format) != mgpu_fmt::kNone, "unknown IQ format");
+        need_iq_format(format);
         need(n_in >= D && n_in % D == 0, "n_in must be a positive multiple of D");
         need(n_in / D <= max_out, "more outputs than max_out in one call");
         need(pos + uint64_t(n_in / D) <= (1ULL << 62), "position beyond 2^62");
@@ -220,7 +220,7 @@ struct mgpu_chan {
     }
 
     const void* on_device(const void* iq, int format, int n_in, hipStream_t st) {
-        return staged_on_device(d_stage, iq, size_t(n_in) * 2 * mgpu_fmt::element_bytes(mgpu_fmt::element(2, format)), st);
+        return staged_iq(d_stage, iq, format, n_in, st);
     }
     void need_out() {
         if (!d_out.p) d_out = DevArray<double>(size_t(S) * max_out * 8);

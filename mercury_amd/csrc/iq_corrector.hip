@@ -44,19 +44,6 @@ struct ApplyArgs {
 
 }  // namespace
 
-__device__ inline void iqc_load(const void* iq, int format, size_t g, double* I, double* Q) {
-    if (format == MGPU_IQ_CS16) {
-        const short2 v = static_cast<const short2*>(iq)[g];
-        *I = mgpu_fmt::widen(v.x, 32768.0), *Q = mgpu_fmt::widen(v.y, 32768.0);
-    } else if (format == MGPU_IQ_CF32) {
-        const float2 v = static_cast<const float2*>(iq)[g];
-        *I = mgpu_fmt::widen(v.x, 1.0), *Q = mgpu_fmt::widen(v.y, 1.0);
-    } else {
-        const double2 v = static_cast<const double2*>(iq)[g];
-        *I = v.x, *Q = v.y;
-    }
-}
-
 // grid: the call's blocks. sums [m][5]
 extern "C" __global__ __launch_bounds__(kThreads) void mgpu_iqc_sums_kernel(const void* __restrict__ iq, double* __restrict__ sums, int format,
                                                                             int B) {
@@ -65,13 +52,13 @@ extern "C" __global__ __launch_bounds__(kThreads) void mgpu_iqc_sums_kernel(cons
     const size_t first = size_t(blockIdx.x) * size_t(B);
     double p[kTerms];
     {
-        double I, Q;
-        iqc_load(iq, format, first + size_t(t), &I, &Q);             // B >= 256: every thread has a first term
+        const double2 v = mgpu_fmt::load_iq(iq, format, first + size_t(t));      // B >= 256: every thread has a first term
+        const double I = v.x, Q = v.y;
         p[0] = I, p[1] = Q, p[2] = I * I, p[3] = I * Q, p[4] = Q * Q;
     }
     for (int f = t + kThreads; f < B; f += kThreads) {
-        double I, Q;
-        iqc_load(iq, format, first + size_t(f), &I, &Q);
+        const double2 v = mgpu_fmt::load_iq(iq, format, first + size_t(f));
+        const double I = v.x, Q = v.y;
         p[0] += I, p[1] += Q, p[2] += I * I, p[3] += I * Q, p[4] += Q * Q;
     }
 #pragma unroll
@@ -162,10 +149,10 @@ extern "C" __global__ __launch_bounds__(kThreads) void mgpu_iqc_apply_kernel(App
     const size_t first = size_t(blockIdx.x) * size_t(B);
     int mine = 0;
     for (int f = t; f < B; f += kThreads) {                          // B is a multiple of 256: no lane is idle in a ballot
-        double I, Q, yI, yQ;
-        iqc_load(a.iq, a.format, first + size_t(f), &I, &Q);
-        correct(e, I, Q, &yI, &yQ);
-        const unsigned c = mgpu_synth_detail::store_iq(a.out, a.format, first + size_t(f), yI, yQ);
+        const double2 v = mgpu_fmt::load_iq(a.iq, a.format, first + size_t(f));
+        double yI, yQ;
+        correct(e, v.x, v.y, &yI, &yQ);
+        const unsigned c = mgpu_fmt::store_iq(a.out, a.format, first + size_t(f), yI, yQ);
         mine += __popcll(__ballot(c >= 1)) + __popcll(__ballot(c == 2));
     }
     if (!a.reports) return;
@@ -181,26 +168,13 @@ extern "C" __global__ __launch_bounds__(kThreads) void mgpu_iqc_apply_kernel(App
     }
 }
 
-struct mgpu_iqc {
-    mgpu_ctx* c = nullptr;
+struct mgpu_iqc : BlockStage<mgpu_iqc_report> {
     mgpu_iqc_config cfg{};
-    int B = 0, max_in = 0, max_blocks = 0;
     double lambda = 1.0;
-    size_t bytes = 0;                             // of one IQ sample
-    uint64_t pos = 0;
     bool fresh = true;                            // the state is zero: d_state is not read
     DevArray<double> d_state;                     // [6]
     DevArray<double> d_sums;                      // [max_blocks][5]
     DevArray<BlockEstimate> d_est;                // [max_blocks]
-    DevArray<char> d_stage;                       // host input's landing area (ctx.hpp staged_on_device)
-    DevArray<char> d_out;                         // process()'s output and reports (grown to the call)
-    DevArray<mgpu_iqc_report> d_reports;
-
-    int check_in(const void* iq, int n_in, const void* out) const {
-        need(iq != nullptr && out != nullptr, "null pointer");
-        need(call_ok(B, max_in, pos, n_in), "n_in must be a positive multiple of B, max_in at most, and the position stay below 2^62");
-        return n_in / B;
-    }
 
     // one call on device memory: m = n_in / B blocks into d_o [n_in] and d_r [m] (null: no reports)
     void run(const void* d_iq, int m, void* d_o, mgpu_iqc_report* d_r, hipStream_t st) {
@@ -229,11 +203,8 @@ extern "C" {
 int mgpu_iqc_create(mgpu_ctx* c, const mgpu_iqc_config* kc, mgpu_iqc** out) {
     return create_stage(c, out, "mgpu_iqc_create", config_error(kc), [&](mgpu_iqc* k) {
         k->cfg = *kc;
-        const int B = k->B = k->cfg.block = block_of(*kc);
+        block_shape(k, block_of(*kc), kDefaultBlocksIn);
         k->lambda = lambda_of(*kc);
-        k->max_in = k->cfg.max_in = kc->max_in ? kc->max_in : kDefaultBlocksIn * B;
-        k->max_blocks = k->max_in / B;
-        k->bytes = 2 * mgpu_fmt::element_bytes(mgpu_fmt::element(2, kc->format));
         k->d_state = DevArray<double>(6 * sizeof(double));
         k->d_sums = DevArray<double>(size_t(k->max_blocks) * kTerms * sizeof(double));
         k->d_est = DevArray<BlockEstimate>(size_t(k->max_blocks) * sizeof(BlockEstimate));
@@ -243,10 +214,7 @@ int mgpu_iqc_create(mgpu_ctx* c, const mgpu_iqc_config* kc, mgpu_iqc** out) {
 int mgpu_iqc_destroy(mgpu_iqc* k) { return destroy_stage(k); }
 
 int mgpu_iqc_seek(mgpu_iqc* k, uint64_t position) {
-    if (!k || position > kMaxPosition || position % uint64_t(k->B)) return MGPU_ERR_ARG;
-    k->pos = position;
-    k->fresh = true;
-    return MGPU_OK;
+    return block_seek(k, position, [&] { k->fresh = true; });
 }
 
 int mgpu_iqc_status(mgpu_iqc* k, mgpu_iqc_state* state) {
@@ -268,34 +236,11 @@ int mgpu_iqc_status(mgpu_iqc* k, mgpu_iqc_state* state) {
 }
 
 int mgpu_iqc_process_dev(mgpu_iqc* k, const void* d_iq, int n_in, void* d_out, mgpu_iqc_report* d_reports, int* n_reports, void* stream) {
-    if (!k) return MGPU_ERR_ARG;
-    return guard(k->c, [&] {
-        const int m = k->check_in(d_iq, n_in, d_out);
-        const char* const i0 = static_cast<const char*>(d_iq);
-        const char* const o0 = static_cast<const char*>(d_out);
-        const size_t len = size_t(n_in) * k->bytes;
-        need(o0 + len <= i0 || i0 + len <= o0, "d_out must not overlap d_iq");
-        k->run(d_iq, m, d_out, d_reports, stream_or_own(k->c, stream));
-        if (n_reports) *n_reports = m;
-    });
+    return block_process_dev(k, d_iq, n_in, d_out, d_reports, n_reports, stream);
 }
 
 int mgpu_iqc_process(mgpu_iqc* k, const void* iq, int n_in, void* out, mgpu_iqc_report* reports, int* n_reports) {
-    if (!k) return MGPU_ERR_ARG;
-    return guard(k->c, [&] {
-        const int m = k->check_in(iq, n_in, out);
-        hipStream_t st = k->c->stream;
-        const size_t len = size_t(n_in) * k->bytes;
-        HIPCK(hipStreamSynchronize(st));          // the buffers below grow only when nothing reads them
-        k->d_out.grow(len);
-        k->d_reports.grow(size_t(m) * sizeof(mgpu_iqc_report));
-        const void* d_iq = staged_on_device(k->d_stage, iq, len, st);
-        k->run(d_iq, m, k->d_out.p, k->d_reports, st);
-        HIPCK(hipMemcpyAsync(out, k->d_out.p, len, hipMemcpyDeviceToHost, st));
-        if (reports) HIPCK(hipMemcpyAsync(reports, k->d_reports.p, size_t(m) * sizeof(mgpu_iqc_report), hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        if (n_reports) *n_reports = m;
-    });
+    return block_process(k, iq, n_in, out, reports, n_reports);
 }
 
 int mgpu_host_iqc_process(const mgpu_iqc_config* kc, const void* iq, int n_in, uint64_t position, void* out, mgpu_iqc_report* reports,

@@ -8,14 +8,13 @@
 #include <vector>
 
 #include "../../include/ext/mercury_iq_corrector.h"
-#include "sample_formats.h"
-#include "synth_tables.hpp"
+#include "iq_stream_rule.hpp"
 
 namespace mgpu_iqc_detail {
 
+using namespace mgpu_iq_rule;
+
 constexpr int kDefaultBlocksIn = 1024;                          // max_in = 0: this many blocks
-constexpr int kMaxIn = 1 << 26;
-constexpr uint64_t kMaxPosition = 1ULL << 62;
 constexpr int kPartials = 256;                                  // partial sums per term and block
 constexpr int kTerms = 5;                                       // I, Q, I I, I Q, Q Q
 
@@ -28,8 +27,8 @@ MGPU_FMT_FN bool is_finite(double x) { return x - x == 0.0; }      // false for 
 inline const char* config_error(const mgpu_iqc_config* k) {
     if (!k) return "null configuration";
     if (k->struct_size != int(sizeof(mgpu_iqc_config))) return "struct_size is not this library's sizeof(mgpu_iqc_config)";
-    if (k->D < 1 || k->D > MGPU_CHAN_MAX_D) return "D must be 1..64";
-    if (mgpu_fmt::element(2, k->format) == mgpu_fmt::kNone) return "unknown IQ format";
+    if (const char* e = d_error(k->D)) return e;
+    if (const char* e = format_error(k->format)) return e;
     if (k->block != 0 && (k->block < MGPU_IQC_MIN_BLOCK || k->block > MGPU_IQC_MAX_BLOCK || k->block % kPartials))
         return "block must be a multiple of 256, 256..4096, or 0";
     if (k->memory != 0 && (k->memory < 2 || k->memory > MGPU_IQC_MAX_MEMORY)) return "memory must be 0 or 2..2^20 blocks";
@@ -41,12 +40,6 @@ inline const char* config_error(const mgpu_iqc_config* k) {
     }
     if (k->max_in < 0 || k->max_in > kMaxIn || k->max_in % block_of(*k)) return "max_in must be a multiple of B, 2^26 at most";
     return nullptr;
-}
-
-// a call of n_in samples at `position` on a stage of block B and max_in (0: no such limit)
-inline bool call_ok(int B, int max_in, uint64_t position, int n_in) {
-    return n_in >= B && n_in % B == 0 && (max_in == 0 || n_in <= max_in) && position <= kMaxPosition && position % uint64_t(B) == 0 &&
-           position + uint64_t(n_in) <= kMaxPosition;
 }
 
 // the four values a block's samples are corrected with, and MGPU_IQC_NO_BALANCE or 0
@@ -140,7 +133,7 @@ inline int host_process(const mgpu_iqc_config* kc, double* state, const void* iq
             const size_t g = size_t(b) * size_t(B) + size_t(i);
             double yI, yQ;
             correct(est, mgpu_fmt::widen_at(e, iq, 2 * g), mgpu_fmt::widen_at(e, iq, 2 * g + 1), &yI, &yQ);
-            clamped += mgpu_synth_detail::store_iq(out, k.format, g, yI, yQ);
+            clamped += mgpu_fmt::store_iq(out, k.format, g, yI, yQ);
         }
         if (reports) {
             mgpu_iqc_report r;

@@ -7,10 +7,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "../../include/mercury_channelizer.h"
 #include "../../include/mercury_rxloop.h"
 
 #ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #define MGPU_FMT_FN __host__ __device__ inline
 #else
 #define MGPU_FMT_FN inline
@@ -44,6 +47,52 @@ template <typename Fn> MGPU_FMT_FN auto with_elements(int e, const void* samples
 // element i of the samples, widened
 MGPU_FMT_FN double widen_at(int e, const void* samples, size_t i) {
     return with_elements(e, samples, [i](auto* in, double divisor) { return widen(in[i], divisor); });
+}
+
+// The IQ formats in both directions. The bytes of one IQ sample; 0: no such format
+MGPU_FMT_FN size_t iq_bytes(int format) { return format == MGPU_IQ_CS16 ? 4 : format == MGPU_IQ_CF32 ? 8 : format == MGPU_IQ_CF64 ? 16 : 0; }
+
+#ifdef __HIPCC__
+// IQ sample g of a buffer in `format`, widened: one 4-, 8- or 16-byte load. A chain on the format itself: going through element() and
+// with_elements() made the channeliser's assemble kernel longer and slower (profiles/stage_plumbing.md)
+__device__ inline double2 load_iq(const void* iq, int format, size_t g) {
+    if (format == MGPU_IQ_CS16) {
+        const short2 v = static_cast<const short2*>(iq)[g];
+        return make_double2(widen(v.x, 32768.0), widen(v.y, 32768.0));
+    }
+    if (format == MGPU_IQ_CF32) {
+        const float2 v = static_cast<const float2*>(iq)[g];
+        return make_double2(widen(v.x, 1.0), widen(v.y, 1.0));
+    }
+    return static_cast<const double2*>(iq)[g];
+}
+#endif
+
+// one component as CS16: clamp(nearbyint(x * 32768), -32768, 32767); *clamped += 1 where it was clamped (a NaN becomes 0 and counts)
+MGPU_FMT_FN int16_t to_cs16(double x, unsigned* clamped) {
+    const double y = rint(x * 32768.0);
+    if (y > 32767.0) { ++*clamped; return 32767; }
+    if (y < -32768.0) { ++*clamped; return -32768; }
+    if (y != y) { ++*clamped; return 0; }
+    return int16_t(int(y));
+}
+// IQ sample m of `out` in `format`; returns the components clamped
+MGPU_FMT_FN unsigned store_iq(void* out, int format, size_t m, double re, double im) {
+    unsigned clamped = 0;
+    if (format == MGPU_IQ_CS16) {
+        int16_t* o = static_cast<int16_t*>(out) + 2 * m;
+        o[0] = to_cs16(re, &clamped);
+        o[1] = to_cs16(im, &clamped);
+    } else if (format == MGPU_IQ_CF32) {
+        float* o = static_cast<float*>(out) + 2 * m;
+        o[0] = float(re);
+        o[1] = float(im);
+    } else {
+        double* o = static_cast<double*>(out) + 2 * m;
+        o[0] = re;
+        o[1] = im;
+    }
+    return clamped;
 }
 
 }  // namespace mgpu_fmt

@@ -8,19 +8,20 @@
 #include <vector>
 
 #include "../../include/ext/mercury_scanner.h"
-#include "sample_formats.h"
+#include "iq_stream_rule.hpp"
 
 namespace mgpu_scan_detail {
 
+using namespace mgpu_iq_rule;
+
 constexpr int kDefaultBlocksIn = 256;                           // max_in = 0: this many blocks
-constexpr uint64_t kMaxPosition = 1ULL << 62;
 constexpr unsigned long long kScanKeyMask = 0x7fffffffffffffffull, kScanKeyInf = 0x7ff0000000000000ull;
 
 // why the configuration is refused, or null
 inline const char* config_error(const mgpu_scan_config* k) {
     if (!k) return "null configuration";
     if (k->struct_size != int(sizeof(mgpu_scan_config))) return "struct_size is not this library's sizeof(mgpu_scan_config)";
-    if (k->D < 1 || k->D > MGPU_CHAN_MAX_D) return "D must be 1..64";
+    if (const char* e = d_error(k->D)) return e;
     if (k->log2n < MGPU_SCAN_MIN_LOG2N || k->log2n > MGPU_SCAN_MAX_LOG2N) return "log2n must be 8..12";
     const int N = 1 << k->log2n;
     if (k->blocks_per_line < 1 || k->blocks_per_line > 4096) return "blocks_per_line must be 1..4096";
@@ -142,7 +143,7 @@ inline int host_process(const mgpu_scan_config* kc, const void* iq, int format, 
     if (config_error(kc) || !iq) return 1;
     const mgpu_scan_config& k = *kc;
     const int N = 1 << k.log2n, H = N / 2, A = k.blocks_per_line, e = mgpu_fmt::element(2, format);
-    if (e == mgpu_fmt::kNone || n_in < H || n_in % H || position % (uint64_t(H) * A) || position > kMaxPosition ||
+    if (format_error(format) || n_in < H || n_in % H || position % (uint64_t(H) * A) || position > kMaxPosition ||
         position + uint64_t(n_in) > kMaxPosition)
         return 1;
     const uint64_t j = position / uint64_t(H);

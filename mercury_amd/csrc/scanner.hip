@@ -39,19 +39,6 @@ constexpr int kFar = 1 << 20;                // no such bin within reach
 
 }  // namespace
 
-__device__ inline sc2 scan_widen(const void* iq, int format, size_t g) {
-    if (format == MGPU_IQ_CS16) {
-        const short2 v = static_cast<const short2*>(iq)[g];
-        return {double(v.x) / 32768.0, double(v.y) / 32768.0};
-    }
-    if (format == MGPU_IQ_CF32) {
-        const float2 v = static_cast<const float2*>(iq)[g];
-        return {double(v.x), double(v.y)};
-    }
-    const double2 v = static_cast<const double2*>(iq)[g];
-    return {v.x, v.y};
-}
-
 template <int L>
 __device__ inline void scan_block(const BlockArgs& a) {
     using F = ScanFft<L>;
@@ -63,8 +50,10 @@ __device__ inline void scan_block(const BlockArgs& a) {
     auto fetch = [&](int i) {
         const long long g = (long long)(b - 1) * H + i;
         sc2 x = {0.0, 0.0};
-        if (g >= 0) x = scan_widen(a.iq, a.format, size_t(g));
-        else if (a.hist_old) x = a.hist_old[i];
+        if (g >= 0) {
+            const double2 v = mgpu_fmt::load_iq(a.iq, a.format, size_t(g));
+            x = {v.x, v.y};
+        } else if (a.hist_old) x = a.hist_old[i];
         if (keeps_history && i >= H) a.hist_new[i - H] = x;
         const double w = a.win[i];
         return sc2{x.re * w, x.im * w};
@@ -291,7 +280,7 @@ struct mgpu_scan {
 
     int check_in(const void* iq, int format, int n_in, const void* lines, const void* reports) const {
         need(iq != nullptr, "null pointer");
-        need(mgpu_fmt::element(2, format) != mgpu_fmt::kNone, "unknown IQ format");
+        need_iq_format(format);
         const int n = lines_of(n_in);
         need(n >= 0, "n_in must be a positive multiple of H, max_in at most, and the position stay below 2^62");
         need(n == 0 || (lines && reports), "null pointer");
@@ -340,7 +329,7 @@ int mgpu_scan_create(mgpu_ctx* c, const mgpu_scan_config* kc, mgpu_scan** out) {
         const int N = k->N = 1 << kc->log2n, H = k->H = N / 2;
         k->A = kc->blocks_per_line;
         k->max_in = k->cfg.max_in = kc->max_in ? kc->max_in : kDefaultBlocksIn * H;
-        need(k->max_in <= (1 << 26), "max_in must be at most 2^26");
+        need(k->max_in <= kMaxIn, "max_in must be at most 2^26");
         k->max_blocks = k->max_in / H;
         k->max_lines = (k->max_blocks + k->A - 1) / k->A;
         need(k->max_blocks <= 65535 * k->A, "max_in / H must be at most 65535 blocks_per_line");      // the line kernel's grid y
@@ -386,7 +375,7 @@ int mgpu_scan_process(mgpu_scan* k, const void* iq, int format, int n_in, double
             k->d_lines = DevArray<double>(size_t(k->max_lines) * k->N * 8);
             k->d_reports = DevArray<mgpu_scan_report>(size_t(k->max_lines) * sizeof(mgpu_scan_report));
         }
-        const void* d_iq = staged_on_device(k->d_stage, iq, size_t(n_in) * 2 * mgpu_fmt::element_bytes(mgpu_fmt::element(2, format)), st);
+        const void* d_iq = staged_iq(k->d_stage, iq, format, n_in, st);
         k->run(d_iq, format, n_in, n, k->d_lines, k->d_reports, st);
         if (n > 0) {
             HIPCK(hipMemcpyAsync(lines, k->d_lines.p, size_t(n) * k->N * 8, hipMemcpyDeviceToHost, st));

@@ -146,7 +146,7 @@ __device__ inline void synth_tile(const SynthArgs& a, const double2* __restrict_
         const int n = n0 + int(threadIdx.x) / PH, r = r0 + int(threadIdx.x) % PH;
         if (n < a.n_in && r < a.D) {
             const double2 t = zx[threadIdx.x];
-            const unsigned c = store_iq(a.out, a.format, size_t(n) * a.D + r, t.x, t.y);
+            const unsigned c = mgpu_fmt::store_iq(a.out, a.format, size_t(n) * a.D + r, t.x, t.y);
             if (c) atomicAdd(a.clamped, (unsigned long long)c);
         }
     }
@@ -192,7 +192,7 @@ struct mgpu_synth {
 
     void check_in(const void* audio, size_t in_stride, int n_in, int format, const void* out) const {
         need(audio && out, "null pointer");
-        need(iq_sample_bytes(format) != 0, "unknown IQ format");
+        need_iq_format(format);
         need(n_in >= 1 && n_in <= max_in, "n_in must be 1..max_in");
         need(in_stride >= size_t(n_in), "in_stride is smaller than n_in");
         need(pos + uint64_t(n_in) <= kMaxPosition, "position beyond 2^62");
@@ -292,7 +292,7 @@ int mgpu_synth_process(mgpu_synth* k, const double* audio, size_t in_stride, int
             in_stride = size_t(n_in);
         }
         k->run(d_in, in_stride, n_in, format, k->d_out.p, st);
-        HIPCK(hipMemcpyAsync(out, k->d_out.p, size_t(n_in) * k->D * iq_sample_bytes(format), hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(out, k->d_out.p, size_t(n_in) * k->D * mgpu_fmt::iq_bytes(format), hipMemcpyDeviceToHost, st));
         HIPCK(hipStreamSynchronize(st));
     });
 }

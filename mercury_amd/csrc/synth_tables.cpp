@@ -83,7 +83,7 @@ int mgpu_host_synth_tables(const mgpu_synth_config* k, const mgpu_chan_channel* 
 int mgpu_host_synth_process(const mgpu_synth_config* k, const mgpu_chan_channel* channels, const double* audio, size_t in_stride, int n_in,
                             uint64_t position, int format, void* out, uint64_t* clamped) {
     if (config_error(k, true) || mgpu_chan_detail::plan_error(k->D, k->audio_centre_hz, k->S, channels) || !audio || !out) return MGPU_ERR_ARG;
-    if (n_in < 1 || (long long)n_in * k->D > (1LL << 30) || in_stride < size_t(n_in) || !iq_sample_bytes(format)) return MGPU_ERR_ARG;
+    if (n_in < 1 || (long long)n_in * k->D > (1LL << 30) || in_stride < size_t(n_in) || !mgpu_fmt::iq_bytes(format)) return MGPU_ERR_ARG;
     if (position > kMaxPosition || position + uint64_t(n_in) > kMaxPosition) return MGPU_ERR_ARG;
     const int D = k->D, S = k->S;
     const std::vector<double> h = prototype(k);
@@ -115,7 +115,7 @@ int mgpu_host_synth_process(const mgpu_synth_config* k, const mgpu_chan_channel*
                 re += G * std::fma(-vi, Ei, vr * Er);
                 im += G * std::fma(vi, Er, vr * Ei);
             }
-            count += store_iq(out, format, size_t(n) * D + r, re, im);
+            count += mgpu_fmt::store_iq(out, format, size_t(n) * D + r, re, im);
         }
     }
     if (clamped) *clamped = count;

@@ -6,17 +6,12 @@
 
 #include "../../include/ext/mercury_synth.h"
 #include "chan_tables.hpp"
-
-#ifdef __HIPCC__
-#define MGPU_SYNTH_FN __host__ __device__ inline
-#else
-#define MGPU_SYNTH_FN inline
-#endif
+#include "iq_stream_rule.hpp"
 
 namespace mgpu_synth_detail {
 
 constexpr int kDefaultMaxIn = 16 * 1088;
-constexpr uint64_t kMaxPosition = 1ULL << 62;
+using mgpu_iq_rule::kMaxPosition;
 
 // why the configuration is refused, or null. need_s: S is read (the tables of one channel do not read it)
 const char* config_error(const mgpu_synth_config* k, bool need_s);
@@ -32,34 +27,6 @@ inline double channel_gain(int D, double gain) { return (2.0 * double(D)) * gain
 inline int carrier_index(int offset_hz, uint64_t n) {
     const long long a = mgpu_chan_detail::floor_mod(offset_hz, MGPU_CHAN_PHASOR_LEN);
     return int((a * (long long)(n % MGPU_CHAN_PHASOR_LEN)) % MGPU_CHAN_PHASOR_LEN);
-}
-inline size_t iq_sample_bytes(int format) { return format == MGPU_IQ_CS16 ? 4 : format == MGPU_IQ_CF32 ? 8 : format == MGPU_IQ_CF64 ? 16 : 0; }
-
-// one component as CS16: clamp(nearbyint(x * 32768), -32768, 32767); *clamped += 1 where it was clamped (a NaN becomes 0 and counts)
-MGPU_SYNTH_FN int16_t to_cs16(double x, unsigned* clamped) {
-    const double y = rint(x * 32768.0);
-    if (y > 32767.0) { ++*clamped; return 32767; }
-    if (y < -32768.0) { ++*clamped; return -32768; }
-    if (y != y) { ++*clamped; return 0; }
-    return int16_t(int(y));
-}
-// IQ sample m of `out` in `format`; returns the components clamped
-MGPU_SYNTH_FN unsigned store_iq(void* out, int format, size_t m, double re, double im) {
-    unsigned clamped = 0;
-    if (format == MGPU_IQ_CS16) {
-        int16_t* o = static_cast<int16_t*>(out) + 2 * m;
-        o[0] = to_cs16(re, &clamped);
-        o[1] = to_cs16(im, &clamped);
-    } else if (format == MGPU_IQ_CF32) {
-        float* o = static_cast<float*>(out) + 2 * m;
-        o[0] = float(re);
-        o[1] = float(im);
-    } else {
-        double* o = static_cast<double*>(out) + 2 * m;
-        o[0] = re;
-        o[1] = im;
-    }
-    return clamped;
 }
 
 }  // namespace mgpu_synth_detail

@@ -39,18 +39,6 @@ struct MixArgs {
 
 }  // namespace
 
-__device__ inline double2 tune_widen(const void* iq, int format, size_t u) {
-    if (format == MGPU_IQ_CS16) {
-        const short2 v = static_cast<const short2*>(iq)[u];
-        return make_double2(double(v.x) / 32768.0, double(v.y) / 32768.0);
-    }
-    if (format == MGPU_IQ_CF32) {
-        const float2 v = static_cast<const float2*>(iq)[u];
-        return make_double2(double(v.x), double(v.y));
-    }
-    return static_cast<const double2*>(iq)[u];
-}
-
 // the channeliser's step (channelizer.hip chan_step), one output: the rule's four fused multiply-adds of tap g on sample v
 __device__ inline void tune_step(const double2 g, const double2 v, double& re, double& im) {
     re = fma(g.x, v.x, re);
@@ -81,7 +69,7 @@ extern "C" __global__ __launch_bounds__(kMixThreads) void mgpu_tune_mix_kernel(M
         if (b) __syncthreads();                              // the previous block's reads are done
         for (int w = threadIdx.x; w < wn; w += blockDim.x) {
             const int u = lo + w;
-            const double2 v = (u >= 0 && u < a.n_in) ? tune_widen(a.iq, a.format, size_t(u)) : make_double2(0.0, 0.0);
+            const double2 v = (u >= 0 && u < a.n_in) ? mgpu_fmt::load_iq(a.iq, a.format, size_t(u)) : make_double2(0.0, 0.0);
             tune_lds[(w % Dm) * ncols + w / Dm] = v;
         }
         __syncthreads();
@@ -287,10 +275,10 @@ int mgpu_tune_process(mgpu_tune* k, const void* iq, int format, int n_in, mgpu_t
     if (!k) return MGPU_ERR_ARG;
     return guard(k->c, [&] {
         need(iq && reports, "null pointer");
-        need(mgpu_fmt::element(2, format) != mgpu_fmt::kNone, "unknown IQ format");
+        need_iq_format(format);
         need(n_in == k->n_in, "n_in must be 4 * D * 272 * (symbols + 1)");
         hipStream_t st = k->c->stream;
-        const void* d_iq = staged_on_device(k->d_stage, iq, size_t(n_in) * 2 * mgpu_fmt::element_bytes(mgpu_fmt::element(2, format)), st);
+        const void* d_iq = staged_iq(k->d_stage, iq, format, n_in, st);
         k->run(d_iq, format, reports, st);
     });
 }

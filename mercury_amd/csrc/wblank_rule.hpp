@@ -7,13 +7,13 @@
 #include <vector>
 
 #include "../../include/ext/mercury_wideband_blanker.h"
-#include "sample_formats.h"
+#include "iq_stream_rule.hpp"
 
 namespace mgpu_wblank_detail {
 
+using namespace mgpu_iq_rule;
+
 constexpr int kDefaultBlocksIn = 1024;                          // max_in = 0: this many blocks
-constexpr int kMaxIn = 1 << 26;
-constexpr uint64_t kMaxPosition = 1ULL << 62;
 constexpr unsigned long long kWblankKeyMask = 0x7fffffffffffffffull;
 
 // B of a configuration whose D is in range
@@ -27,8 +27,8 @@ inline int block_of(const mgpu_wblank_config& k) {
 inline const char* config_error(const mgpu_wblank_config* k) {
     if (!k) return "null configuration";
     if (k->struct_size != int(sizeof(mgpu_wblank_config))) return "struct_size is not this library's sizeof(mgpu_wblank_config)";
-    if (k->D < 1 || k->D > MGPU_CHAN_MAX_D) return "D must be 1..64";
-    if (mgpu_fmt::element(2, k->format) == mgpu_fmt::kNone) return "unknown IQ format";
+    if (const char* e = d_error(k->D)) return e;
+    if (const char* e = format_error(k->format)) return e;
     if (k->block != 0 && (k->block < MGPU_WBLANK_MIN_BLOCK || k->block > MGPU_WBLANK_MAX_BLOCK || k->block % 64))
         return "block must be a multiple of 64, 64..4096, or 0";
     if (!(k->threshold >= 2.0) || !(k->threshold <= 1.7976931348623157e308)) return "threshold must be finite and at least 2";
@@ -40,12 +40,6 @@ inline const char* config_error(const mgpu_wblank_config* k) {
 
 // cap = floor(max_share * B) in double; the product is non-negative and below 2^31, so the conversion is the floor
 inline int cap_of(const mgpu_wblank_config& k) { return int(k.max_share * double(block_of(k))); }
-
-// a call of n_in samples at `position` on a stage of block B and max_in (0: no such limit)
-inline bool call_ok(int B, int max_in, uint64_t position, int n_in) {
-    return n_in >= B && n_in % B == 0 && (max_in == 0 || n_in <= max_in) && position <= kMaxPosition && position % uint64_t(B) == 0 &&
-           position + uint64_t(n_in) <= kMaxPosition;
-}
 
 inline unsigned long long key_of(double p) {
     unsigned long long key;
@@ -78,7 +72,7 @@ inline int host_process(const mgpu_wblank_config* kc, const void* iq, int n_in, 
     const int B = block_of(k), cap = cap_of(k), e = mgpu_fmt::element(2, k.format), guard = k.guard;
     if (!call_ok(B, k.max_in, position, n_in)) return 1;
     const int m = n_in / B;
-    const size_t bytes = 2 * mgpu_fmt::element_bytes(e);         // of one IQ sample
+    const size_t bytes = mgpu_fmt::iq_bytes(k.format);
     if (n_reports) *n_reports = m;
     std::vector<char> exceeds(static_cast<size_t>(n_in), 0);
     std::vector<mgpu_wblank_report> rep(static_cast<size_t>(m));

@@ -55,20 +55,7 @@ struct EmitArgs {
 
 }  // namespace
 
-__device__ inline double wblank_power(const void* iq, int format, size_t g) {
-    double re, im;
-    if (format == MGPU_IQ_CS16) {
-        const short2 v = static_cast<const short2*>(iq)[g];
-        re = mgpu_fmt::widen(v.x, 32768.0), im = mgpu_fmt::widen(v.y, 32768.0);
-    } else if (format == MGPU_IQ_CF32) {
-        const float2 v = static_cast<const float2*>(iq)[g];
-        re = mgpu_fmt::widen(v.x, 1.0), im = mgpu_fmt::widen(v.y, 1.0);
-    } else {
-        const double2 v = static_cast<const double2*>(iq)[g];
-        re = v.x, im = v.y;
-    }
-    return re * re + im * im;
-}
+__device__ inline double wblank_power(const double2 v) { return v.x * v.x + v.y * v.y; }
 
 // Thread t has the samples 256 i + t of the block, i < K: bit `lane` of flag word 4 i + wave. The selection costs one barrier per bit: a
 // wavefront's count of the bit goes to cnt[bit & 1][wave], and a wavefront can be at most one bit ahead of another, which writes the
@@ -82,7 +69,7 @@ __device__ inline void wblank_analyse(const AnalyseArgs& a) {
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         const int f = kThreads * i + t;
-        p[i] = f < B ? wblank_power(a.iq, a.format, first + size_t(f)) : 0.0;
+        p[i] = f < B ? wblank_power(mgpu_fmt::load_iq(a.iq, a.format, first + size_t(f))) : 0.0;
     }
     auto key = [&](int i) { return static_cast<unsigned long long>(__double_as_longlong(p[i])) & kWblankKeyMask; };
     int rank = B / 2;
@@ -188,25 +175,13 @@ extern "C" __global__ __launch_bounds__(kThreads) void mgpu_wblank_emit_4_kernel
 extern "C" __global__ __launch_bounds__(kThreads) void mgpu_wblank_emit_8_kernel(EmitArgs a) { wblank_emit<unsigned long long>(a); }
 extern "C" __global__ __launch_bounds__(kThreads) void mgpu_wblank_emit_16_kernel(EmitArgs a) { wblank_emit<ulonglong2>(a); }
 
-struct mgpu_wblank {
-    mgpu_ctx* c = nullptr;
+struct mgpu_wblank : BlockStage<mgpu_wblank_report> {
     mgpu_wblank_config cfg{};
-    int B = 0, W = 0, cap = 0, max_in = 0, max_blocks = 0;
-    size_t bytes = 0;                             // of one IQ sample
-    uint64_t pos = 0;
+    int W = 0, cap = 0;
     History<char> held;                           // [B] samples: the block that waits for its successor
     History<unsigned long long> words;            // [W + 3]: its flag words and figures (EmitArgs)
     DevArray<unsigned long long> d_flags;         // [max_blocks][W]
     DevArray<BlockInfo> d_info;                   // [max_blocks]
-    DevArray<char> d_stage;                       // host input's landing area (ctx.hpp staged_on_device)
-    DevArray<char> d_out;                         // process()'s output and reports (grown to the call)
-    DevArray<mgpu_wblank_report> d_reports;
-
-    int check_in(const void* iq, int n_in, const void* out) const {
-        need(iq != nullptr && out != nullptr, "null pointer");
-        need(call_ok(B, max_in, pos, n_in), "n_in must be a positive multiple of B, max_in at most, and the position stay below 2^62");
-        return n_in / B;
-    }
 
     // one call on device memory: m = n_in / B blocks into d_o [n_in] and d_r [m] (null: no reports)
     void run(const void* d_iq, int m, void* d_o, mgpu_wblank_report* d_r, hipStream_t st) {
@@ -234,12 +209,10 @@ extern "C" {
 int mgpu_wblank_create(mgpu_ctx* c, const mgpu_wblank_config* kc, mgpu_wblank** out) {
     return create_stage(c, out, "mgpu_wblank_create", config_error(kc), [&](mgpu_wblank* k) {
         k->cfg = *kc;
-        const int B = k->B = k->cfg.block = block_of(*kc);
+        const int B = block_of(*kc);
+        block_shape(k, B, kDefaultBlocksIn);
         k->W = B / 64;
         k->cap = cap_of(*kc);
-        k->max_in = k->cfg.max_in = kc->max_in ? kc->max_in : kDefaultBlocksIn * B;
-        k->max_blocks = k->max_in / B;
-        k->bytes = 2 * mgpu_fmt::element_bytes(mgpu_fmt::element(2, kc->format));
         k->held.make(size_t(B) * k->bytes);
         k->words.make(size_t(k->W + 3) * 8);
         k->d_flags = DevArray<unsigned long long>(size_t(k->max_blocks) * size_t(k->W) * 8);
@@ -250,11 +223,10 @@ int mgpu_wblank_create(mgpu_ctx* c, const mgpu_wblank_config* kc, mgpu_wblank** 
 int mgpu_wblank_destroy(mgpu_wblank* k) { return destroy_stage(k); }
 
 int mgpu_wblank_seek(mgpu_wblank* k, uint64_t position) {
-    if (!k || position > kMaxPosition || position % uint64_t(k->B)) return MGPU_ERR_ARG;
-    k->pos = position;
-    k->held.restart();
-    k->words.restart();
-    return MGPU_OK;
+    return block_seek(k, position, [&] {
+        k->held.restart();
+        k->words.restart();
+    });
 }
 
 int mgpu_wblank_status(mgpu_wblank* k, mgpu_wblank_state* state) {
@@ -269,34 +241,11 @@ int mgpu_wblank_status(mgpu_wblank* k, mgpu_wblank_state* state) {
 
 int mgpu_wblank_process_dev(mgpu_wblank* k, const void* d_iq, int n_in, void* d_out, mgpu_wblank_report* d_reports, int* n_reports,
                             void* stream) {
-    if (!k) return MGPU_ERR_ARG;
-    return guard(k->c, [&] {
-        const int m = k->check_in(d_iq, n_in, d_out);
-        const char* const i0 = static_cast<const char*>(d_iq);
-        const char* const o0 = static_cast<const char*>(d_out);
-        const size_t len = size_t(n_in) * k->bytes;
-        need(o0 + len <= i0 || i0 + len <= o0, "d_out must not overlap d_iq");
-        k->run(d_iq, m, d_out, d_reports, stream_or_own(k->c, stream));
-        if (n_reports) *n_reports = m;
-    });
+    return block_process_dev(k, d_iq, n_in, d_out, d_reports, n_reports, stream);
 }
 
 int mgpu_wblank_process(mgpu_wblank* k, const void* iq, int n_in, void* out, mgpu_wblank_report* reports, int* n_reports) {
-    if (!k) return MGPU_ERR_ARG;
-    return guard(k->c, [&] {
-        const int m = k->check_in(iq, n_in, out);
-        hipStream_t st = k->c->stream;
-        const size_t len = size_t(n_in) * k->bytes;
-        HIPCK(hipStreamSynchronize(st));          // the buffers below grow only when nothing reads them
-        k->d_out.grow(len);
-        k->d_reports.grow(size_t(m) * sizeof(mgpu_wblank_report));
-        const void* d_iq = staged_on_device(k->d_stage, iq, len, st);
-        k->run(d_iq, m, k->d_out.p, k->d_reports, st);
-        HIPCK(hipMemcpyAsync(out, k->d_out.p, len, hipMemcpyDeviceToHost, st));
-        if (reports) HIPCK(hipMemcpyAsync(reports, k->d_reports.p, size_t(m) * sizeof(mgpu_wblank_report), hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        if (n_reports) *n_reports = m;
-    });
+    return block_process(k, iq, n_in, out, reports, n_reports);
 }
 
 int mgpu_host_wblank_process(const mgpu_wblank_config* kc, const void* iq, int n_in, uint64_t position, void* out,

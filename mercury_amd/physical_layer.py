@@ -2135,6 +2135,101 @@ def _iq_empty(fmt, n):
     return np.zeros((n, 2), np.int16) if fmt == IQ_CS16 else np.zeros(n, np.complex64 if fmt == IQ_CF32 else np.complex128)
 
 
+def _iq_format_number(fmt):
+    """'cs16', 'cf32', 'cf64' or an MGPU_IQ_* number as a configuration takes it (an unknown name is -1 and an unknown number stays: both are
+    the library's to refuse)"""
+    return _IQ_FORMATS.get(fmt.lower(), -1) if isinstance(fmt, str) else int(fmt)
+
+
+def _iq_like(x, fmt, n):
+    """a numpy array for n IQ samples of MGPU_IQ_* fmt, shaped as the numpy input x where that holds n samples"""
+    out = _iq_empty(fmt, max(n, 1))
+    return out.reshape(x.shape) if isinstance(x, np.ndarray) and x.size == out.size and n else out
+
+
+def _device_tensor(t, dtype, numel, exact=False):
+    """t is a contiguous torch tensor of `dtype` with at least (exact: just) `numel` elements"""
+    return hasattr(t, "data_ptr") and t.dtype == dtype and t.is_contiguous() and (t.numel() == numel if exact else t.numel() >= numel)
+
+
+def _host_block_process(stage, make_config, block_of, report_dtype, iq, D, position, struct_size, fmt, config, state=None):
+    """the twin mgpu_host_<stage>_process of a block stage: a fresh stage (make_config(D, the input's format, **config), whose block is
+    block_of(it)) seeked to `position` and fed `iq` whole -> (out, as the input; reports [n_in / B]). state: a float64 array [6] that
+    the twin's _continue form reads and leaves"""
+    ptr, f, n_in, x = _iq(iq)
+    k = make_config(D, f if fmt is None else fmt, **config)
+    if struct_size is not None:
+        k.struct_size = struct_size
+    out = _iq_like(x, f, n_in)
+    reports = np.zeros(max(n_in // block_of(k), 1), report_dtype)
+    n = C.c_int()
+    ahead = ()
+    if state is not None:
+        if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.size == 6 and state.flags.c_contiguous):
+            raise MgpuError("state: a contiguous float64 array of 6", 1)
+        ahead = (_ptr(state),)
+    twin = getattr(load_library(), "mgpu_host_%s_%s" % (stage, "process" if state is None else "continue"))
+    _twin(twin, C.byref(k), *ahead, ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n), code=1)
+    return out, reports[: n.value]
+
+
+class _BlockStage(_Handle):
+    """What WidebandBlanker and IqCorrector are alike in: a stage mgpu_<_prefix> that takes blocks of B IQ samples of one format and gives as
+    many samples back, with one report (_REPORT_DTYPE, decoded by _decode) per block. _make_config: the configuration maker, _State: the
+    status struct, _noun: what the stage is called where a call's format is not the stage's."""
+    _prefix = _make_config = _State = _REPORT_DTYPE = _decode = _noun = None
+
+    def _fn(self, name):
+        return getattr(self.lib, "mgpu_%s_%s" % (self._prefix, name))
+
+    def _create(self, rx, D, fmt, config):
+        """the handle; -> its status"""
+        self.rx, self.lib, self.D = rx, rx.lib, int(D)
+        self.config = type(self)._make_config(D, fmt, **config)
+        self.h = C.c_void_p()
+        rx._ck(self._fn("create")(rx.h, C.byref(self.config), C.byref(self.h)))
+        st = self.status()
+        self.format, self.B, self.max_in = st.format, st.block, st.max_in
+        return st
+
+    def status(self):
+        """the stage's state struct (the class names its fields)"""
+        st = self._State()
+        self.rx._ck(self._fn("status")(self.h, C.byref(st)))
+        return st
+
+    def seek(self, position):
+        self.rx._ck(self._fn("seek")(self.h, int(position)))
+
+    def process_raw(self, iq, out=None, reports=None, stream=None):
+        """-> (out, as the input; reports _REPORT_DTYPE [n_in / B]) as numpy arrays (a blocking call). With out a torch tensor of the
+        input's dtype and size on the device, and `iq` one too: mgpu_<stage>_process_dev, asynchronous on `stream` (None: the context's
+        stream), the reports into `reports`, a uint8 torch tensor [>= n_in / B, the report's bytes] on the device or None; returns
+        n_in / B."""
+        ptr, fmt, n_in, x = _iq(iq)
+        if fmt != self.format:
+            raise MgpuError("the %s was made for IQ format %d, not %d" % (self._noun, self.format, fmt))
+        n = C.c_int()
+        row = self._REPORT_DTYPE.itemsize
+        if out is not None and hasattr(out, "data_ptr"):
+            import torch
+            if not (hasattr(iq, "data_ptr") and _device_tensor(out, iq.dtype, iq.numel(), exact=True)
+                    and (reports is None or _device_tensor(reports, torch.uint8, n_in // self.B * row))):
+                raise MgpuError("device output: device input, a contiguous tensor like it and a contiguous uint8 tensor [n_in / B, %d] or None" % row)
+            self.rx._ck(self._fn("process_dev")(self.h, ptr, n_in, out.data_ptr(), reports.data_ptr() if reports is not None else None,
+                                                C.byref(n), stream))
+            return n.value
+        host = _iq_like(x, fmt, n_in)
+        rep = np.zeros(max(n_in // self.B, 1), self._REPORT_DTYPE)
+        self.rx._ck(self._fn("process")(self.h, ptr, n_in, _ptr(host), _ptr(rep), C.byref(n)))
+        return host, rep[: n.value]
+
+    def process(self, iq):
+        """-> (out, [one dict per block of the call, as the stage's *_reports function makes them])"""
+        out, reports = self.process_raw(iq)
+        return out, type(self)._decode(reports)
+
+
 def _synth_audio(audio, S):
     """-> (pointer, row stride in samples, samples per channel, keep-alive): float64 audio [S, n_in] (or [n_in] for one channel), a numpy
     array or a torch tensor (read in place; its rows may be further apart than n_in)"""
@@ -2335,9 +2430,8 @@ class BandScanner(_Handle):
         n = C.c_int()
         if lines is not None and hasattr(lines, "data_ptr"):
             import torch
-            if (not hasattr(iq, "data_ptr") or not hasattr(reports, "data_ptr") or lines.dtype != torch.float64 or reports.dtype != torch.uint8
-                    or not lines.is_contiguous() or not reports.is_contiguous() or lines.numel() < room * self.N
-                    or reports.numel() < room * SCAN_REPORT_DTYPE.itemsize):
+            if not (hasattr(iq, "data_ptr") and _device_tensor(lines, torch.float64, room * self.N)
+                    and _device_tensor(reports, torch.uint8, room * SCAN_REPORT_DTYPE.itemsize)):
                 raise MgpuError("device output: device input, a contiguous float64 tensor [n, N] and a contiguous uint8 tensor [n, %d]"
                                 % SCAN_REPORT_DTYPE.itemsize)
             self.rx._ck(self.lib.mgpu_scan_process_dev(self.h, ptr, fmt, n_in, lines.data_ptr(), reports.data_ptr(), C.byref(n), stream))
@@ -2507,8 +2601,7 @@ class WblankState(C.Structure):         # mgpu_wblank_state
 def wblank_config(D, fmt="cf64", block=0, threshold=WBLANK_DEFAULT_THRESHOLD, guard=WBLANK_DEFAULT_GUARD,
                   max_share=WBLANK_DEFAULT_MAX_SHARE, max_in=0):
     """-> mgpu_wblank_config; fmt 'cs16', 'cf32', 'cf64' or an MGPU_IQ_* number (an unknown number is the library's to refuse)"""
-    f = _IQ_FORMATS.get(fmt.lower(), -1) if isinstance(fmt, str) else int(fmt)
-    return WblankConfig(C.sizeof(WblankConfig), int(D), f, int(block), float(threshold), float(max_share), int(guard), int(max_in))
+    return WblankConfig(C.sizeof(WblankConfig), int(D), _iq_format_number(fmt), int(block), float(threshold), float(max_share), int(guard), int(max_in))
 
 
 def wblank_block(D, block=0):
@@ -2522,78 +2615,25 @@ def wblank_reports(reports):
              "capped": int(r["capped"])} for r in reports]
 
 
-def _iq_like(x, fmt, n):
-    """a numpy array for n IQ samples of MGPU_IQ_* fmt, shaped as the numpy input x where that holds n samples"""
-    out = _iq_empty(fmt, max(n, 1))
-    return out.reshape(x.shape) if isinstance(x, np.ndarray) and x.size == out.size and n else out
-
-
 def host_wblank_process(iq, D, position=0, struct_size=None, fmt=None, **config):
     """the twin (mgpu_host_wblank_process): a fresh stage (wblank_config(D, the input's format, **config)) seeked to `position` and fed
     `iq` whole -> (out, as the input; reports WBLANK_REPORT_DTYPE [n_in / B])"""
-    ptr, f, n_in, x = _iq(iq)
-    k = wblank_config(D, f if fmt is None else fmt, **config)
-    if struct_size is not None:
-        k.struct_size = struct_size
-    B = max(wblank_block(D, k.block), 1) if 1 <= int(D) <= 64 else 1
-    out = _iq_like(x, f, n_in)
-    reports = np.zeros(max(n_in // B, 1), WBLANK_REPORT_DTYPE)
-    n = C.c_int()
-    _twin(load_library().mgpu_host_wblank_process, C.byref(k), ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n), code=1)
-    return out, reports[: n.value]
+    return _host_block_process("wblank", wblank_config, lambda k: max(wblank_block(D, k.block), 1) if 1 <= int(D) <= 64 else 1,
+                               WBLANK_REPORT_DTYPE, iq, D, position, struct_size, fmt, config)
 
 
-class WidebandBlanker(_Handle):
+class WidebandBlanker(_BlockStage):
     """One wideband IQ stream at 48000 * D out again in its own format fmt ('cs16', 'cf32', 'cf64'), one block of B samples late, with
     its clicks replaced by zero, on an RxPhy context (include/ext/mercury_wideband_blanker.h). The other arguments are wblank_config's.
     process() takes complex64 / complex128 / int16 [..., 2] samples of that format (numpy, or a torch tensor on the context's device), a
-    multiple of B of them."""
-    _destroy = "mgpu_wblank_destroy"
+    multiple of B of them, and gives one report per emitted block (32 bytes each on the device). status() is mgpu_wblank_state:
+    position, blocks, D, block, cap, max_in, format, delay."""
+    _destroy, _prefix, _make_config, _State, _noun = "mgpu_wblank_destroy", "wblank", wblank_config, WblankState, "blanker"
+    _REPORT_DTYPE, _decode = WBLANK_REPORT_DTYPE, wblank_reports
 
     def __init__(self, rx, D, fmt="cf64", **config):
-        self.rx, self.lib, self.D = rx, rx.lib, int(D)
-        self.config = wblank_config(D, fmt, **config)
-        self.h = C.c_void_p()
-        rx._ck(self.lib.mgpu_wblank_create(rx.h, C.byref(self.config), C.byref(self.h)))
-        st = self.status()
-        self.format, self.B, self.cap, self.max_in, self.delay = st.format, st.block, st.cap, st.max_in, st.delay
-
-    def status(self):
-        """mgpu_wblank_state: position, blocks, D, block, cap, max_in, format, delay"""
-        st = WblankState()
-        self.rx._ck(self.lib.mgpu_wblank_status(self.h, C.byref(st)))
-        return st
-
-    def seek(self, position):
-        self.rx._ck(self.lib.mgpu_wblank_seek(self.h, int(position)))
-
-    def process_raw(self, iq, out=None, reports=None, stream=None):
-        """-> (out, as the input; reports WBLANK_REPORT_DTYPE [n_in / B]) as numpy arrays (a blocking call). With out a torch tensor of
-        the input's dtype and size on the device, and `iq` one too: mgpu_wblank_process_dev, asynchronous on `stream` (None: the
-        context's stream), the reports into `reports`, a uint8 torch tensor [>= n_in / B, 32] on the device or None; returns n_in / B."""
-        ptr, fmt, n_in, x = _iq(iq)
-        if fmt != self.format:
-            raise MgpuError("the blanker was made for IQ format %d, not %d" % (self.format, fmt))
-        n = C.c_int()
-        if out is not None and hasattr(out, "data_ptr"):
-            import torch
-            if (not hasattr(iq, "data_ptr") or out.dtype != iq.dtype or not out.is_contiguous() or out.numel() != iq.numel()
-                    or (reports is not None and (not hasattr(reports, "data_ptr") or reports.dtype != torch.uint8 or not reports.is_contiguous()
-                                                 or reports.numel() < n_in // self.B * WBLANK_REPORT_DTYPE.itemsize))):
-                raise MgpuError("device output: device input, a contiguous tensor like it and a contiguous uint8 tensor [n_in / B, %d] or None"
-                                % WBLANK_REPORT_DTYPE.itemsize)
-            self.rx._ck(self.lib.mgpu_wblank_process_dev(self.h, ptr, n_in, out.data_ptr(), reports.data_ptr() if reports is not None else None,
-                                                         C.byref(n), stream))
-            return n.value
-        host = _iq_like(x, fmt, n_in)
-        rep = np.zeros(max(n_in // self.B, 1), WBLANK_REPORT_DTYPE)
-        self.rx._ck(self.lib.mgpu_wblank_process(self.h, ptr, n_in, _ptr(host), _ptr(rep), C.byref(n)))
-        return host, rep[: n.value]
-
-    def process(self, iq):
-        """-> (out, [one dict per emitted block, as wblank_reports makes them])"""
-        out, reports = self.process_raw(iq)
-        return out, wblank_reports(reports)
+        st = self._create(rx, D, fmt, config)
+        self.cap, self.delay = st.cap, st.delay
 
 
 # ---- IQ corrector (include/ext/mercury_iq_corrector.h, DESIGN.md §3j) -------------------------------------------------------------------
@@ -2620,8 +2660,7 @@ class IqcState(C.Structure):            # mgpu_iqc_state
 def iqc_config(D, fmt="cf32", block=0, memory=IQC_DEFAULT_MEMORY, dc=1, balance=1, fixed=0, fixed_dc_re=0.0, fixed_dc_im=0.0, fixed_skew=0.0,
                fixed_gain=1.0, max_in=0):
     """-> mgpu_iqc_config; fmt 'cs16', 'cf32', 'cf64' or an MGPU_IQ_* number (an unknown number is the library's to refuse)"""
-    f = _IQ_FORMATS.get(fmt.lower(), -1) if isinstance(fmt, str) else int(fmt)
-    return IqcConfig(C.sizeof(IqcConfig), int(D), f, int(block), int(memory), int(dc), int(balance), int(fixed), float(fixed_dc_re),
+    return IqcConfig(C.sizeof(IqcConfig), int(D), _iq_format_number(fmt), int(block), int(memory), int(dc), int(balance), int(fixed), float(fixed_dc_re),
                      float(fixed_dc_im), float(fixed_skew), float(fixed_gain), int(max_in), 0)
 
 
@@ -2646,73 +2685,18 @@ def host_iqc_process(iq, D, position=0, struct_size=None, fmt=None, state=None, 
     """the twin (mgpu_host_iqc_process): a fresh stage (iqc_config(D, the input's format, **config)) seeked to `position` and fed `iq`
     whole -> (out, as the input; reports IQC_REPORT_DTYPE [n_in / B]). state: a float64 array [6], T before the first block, which
     becomes T after the last (mgpu_host_iqc_continue)."""
-    ptr, f, n_in, x = _iq(iq)
-    k = iqc_config(D, f if fmt is None else fmt, **config)
-    if struct_size is not None:
-        k.struct_size = struct_size
-    B = k.block if k.block > 0 else IQC_DEFAULT_BLOCK
-    out = _iq_like(x, f, n_in)
-    reports = np.zeros(max(n_in // B, 1), IQC_REPORT_DTYPE)
-    n = C.c_int()
-    if state is None:
-        _twin(load_library().mgpu_host_iqc_process, C.byref(k), ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n), code=1)
-    else:
-        if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.size == 6 and state.flags.c_contiguous):
-            raise MgpuError("state: a contiguous float64 array of 6", 1)
-        _twin(load_library().mgpu_host_iqc_continue, C.byref(k), _ptr(state), ptr, n_in, int(position), _ptr(out), _ptr(reports), C.byref(n),
-              code=1)
-    return out, reports[: n.value]
+    return _host_block_process("iqc", iqc_config, lambda k: k.block if k.block > 0 else IQC_DEFAULT_BLOCK, IQC_REPORT_DTYPE, iq, D, position,
+                               struct_size, fmt, config, state)
 
 
-class IqCorrector(_Handle):
+class IqCorrector(_BlockStage):
     """One wideband IQ stream at 48000 * D out again in its own format fmt ('cs16', 'cf32', 'cf64'), with no delay, less its DC offset and
     its IQ imbalance, on an RxPhy context (include/ext/mercury_iq_corrector.h). The other arguments are iqc_config's. process() takes
     complex64 / complex128 / int16 [..., 2] samples of that format (numpy, or a torch tensor on the context's device), a multiple of B of
-    them."""
-    _destroy = "mgpu_iqc_destroy"
+    them, and gives one report per block (48 bytes each on the device). status() is mgpu_iqc_state: position, blocks, D, block, max_in,
+    format, lambda_, T [6], dc_re, dc_im, skew, gain, flags (it waits for the handle's earlier calls)."""
+    _destroy, _prefix, _make_config, _State, _noun = "mgpu_iqc_destroy", "iqc", iqc_config, IqcState, "corrector"
+    _REPORT_DTYPE, _decode = IQC_REPORT_DTYPE, iqc_reports
 
     def __init__(self, rx, D, fmt="cf32", **config):
-        self.rx, self.lib, self.D = rx, rx.lib, int(D)
-        self.config = iqc_config(D, fmt, **config)
-        self.h = C.c_void_p()
-        rx._ck(self.lib.mgpu_iqc_create(rx.h, C.byref(self.config), C.byref(self.h)))
-        st = self.status()
-        self.format, self.B, self.max_in, self.lambda_ = st.format, st.block, st.max_in, st.lambda_
-
-    def status(self):
-        """mgpu_iqc_state: position, blocks, D, block, max_in, format, lambda_, T [6], dc_re, dc_im, skew, gain, flags (waits for the
-        handle's earlier calls)"""
-        st = IqcState()
-        self.rx._ck(self.lib.mgpu_iqc_status(self.h, C.byref(st)))
-        return st
-
-    def seek(self, position):
-        self.rx._ck(self.lib.mgpu_iqc_seek(self.h, int(position)))
-
-    def process_raw(self, iq, out=None, reports=None, stream=None):
-        """-> (out, as the input; reports IQC_REPORT_DTYPE [n_in / B]) as numpy arrays (a blocking call). With out a torch tensor of the
-        input's dtype and size on the device, and `iq` one too: mgpu_iqc_process_dev, asynchronous on `stream` (None: the context's
-        stream), the reports into `reports`, a uint8 torch tensor [>= n_in / B, 48] on the device or None; returns n_in / B."""
-        ptr, fmt, n_in, x = _iq(iq)
-        if fmt != self.format:
-            raise MgpuError("the corrector was made for IQ format %d, not %d" % (self.format, fmt))
-        n = C.c_int()
-        if out is not None and hasattr(out, "data_ptr"):
-            import torch
-            if (not hasattr(iq, "data_ptr") or out.dtype != iq.dtype or not out.is_contiguous() or out.numel() != iq.numel()
-                    or (reports is not None and (not hasattr(reports, "data_ptr") or reports.dtype != torch.uint8 or not reports.is_contiguous()
-                                                 or reports.numel() < n_in // self.B * IQC_REPORT_DTYPE.itemsize))):
-                raise MgpuError("device output: device input, a contiguous tensor like it and a contiguous uint8 tensor [n_in / B, %d] or None"
-                                % IQC_REPORT_DTYPE.itemsize)
-            self.rx._ck(self.lib.mgpu_iqc_process_dev(self.h, ptr, n_in, out.data_ptr(), reports.data_ptr() if reports is not None else None,
-                                                      C.byref(n), stream))
-            return n.value
-        host = _iq_like(x, fmt, n_in)
-        rep = np.zeros(max(n_in // self.B, 1), IQC_REPORT_DTYPE)
-        self.rx._ck(self.lib.mgpu_iqc_process(self.h, ptr, n_in, _ptr(host), _ptr(rep), C.byref(n)))
-        return host, rep[: n.value]
-
-    def process(self, iq):
-        """-> (out, [one dict per block, as iqc_reports makes them])"""
-        out, reports = self.process_raw(iq)
-        return out, iqc_reports(reports)
+        self.lambda_ = self._create(rx, D, fmt, config).lambda_

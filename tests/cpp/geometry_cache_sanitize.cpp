@@ -8,6 +8,7 @@
 #include <thread>
 #include <vector>
 
+#include "check.hpp"
 #include "geometry_cache.hpp"
 
 namespace {
@@ -29,14 +30,6 @@ bool is_geometry(const Toy& g, int cfg, const mgpu::ExplicitParams& xp) {
 }
 
 }  // namespace
-
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                      \
-        }                                                                  \
-    } while (0)
 
 int main() {
     const int cfg = 13;
@@ -70,6 +63,7 @@ int main() {
         });
     for (auto& th : threads) th.join();
     CHECK(bad[0] + bad[1] + bad[2] + bad[3] == 0);
+    if (failures) return 1;
     std::printf("geometry cache: clean\n");
     return 0;
 }

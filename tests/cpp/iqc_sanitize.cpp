@@ -10,18 +10,10 @@
 #include <random>
 #include <vector>
 
+#include "check.hpp"
 #include "iqc_rule.hpp"
 
 using namespace mgpu_iqc_detail;
-
-static int failures = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            ++failures;                                                    \
-        }                                                                  \
-    } while (0)
 
 static mgpu_iqc_config config(int format, int B, int memory) {
     mgpu_iqc_config k{};

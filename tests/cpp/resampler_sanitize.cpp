@@ -9,15 +9,8 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "ext/mercury_resampler.h"
-
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                      \
-        }                                                                  \
-    } while (0)
 
 static int one(int fin, int fout, int components, int format, int tp, uint64_t position) {
     int ntaps = 0;
@@ -74,7 +67,7 @@ static int one(int fin, int fout, int components, int format, int tp, uint64_t p
     CHECK(mgpu_host_resamp_process(&k, in, format, n_in, position, out_taps.data(), size_t(whole), &n_out) == MGPU_ERR_ARG);
     std::printf("%d -> %d, C = %d: %d taps, %d inputs at %llu -> %d outputs, peak %.6f\n", fin, fout, components, ntaps, n_in,
                 (unsigned long long)position, whole, peak);
-    return 0;
+    return failures;
 }
 
 int main() {

@@ -9,19 +9,11 @@
 #include <random>
 #include <vector>
 
+#include "check.hpp"
 #include "scan_fft.h"
 #include "scan_rule.hpp"
 
 using namespace mgpu_scan_detail;
-
-static int failures = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            ++failures;                                                    \
-        }                                                                  \
-    } while (0)
 
 static mgpu_scan_config config(int log2n, int A) {
     mgpu_scan_config k{};

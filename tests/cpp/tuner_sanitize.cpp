@@ -9,19 +9,11 @@
 #include <random>
 #include <vector>
 
+#include "check.hpp"
 #include "scan_fft.h"
 #include "tune_rule.hpp"
 
 using namespace mgpu_tune_detail;
-
-static int failures = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            ++failures;                                                    \
-        }                                                                  \
-    } while (0)
 
 static mgpu_tune_config config(int D, int S, int J, int K, const std::vector<double>& taps) {
     mgpu_tune_config k{};

@@ -9,18 +9,10 @@
 #include <random>
 #include <vector>
 
+#include "check.hpp"
 #include "wblank_rule.hpp"
 
 using namespace mgpu_wblank_detail;
-
-static int failures = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            ++failures;                                                    \
-        }                                                                  \
-    } while (0)
 
 static mgpu_wblank_config config(int format, int B, int guard) {
     mgpu_wblank_config k{};

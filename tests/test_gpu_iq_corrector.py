@@ -10,24 +10,12 @@ import pytest
 
 import iqc_ref as ref
 from band_links import ThreeLinks, last_error, other_rx, rx as _rx, torch as _torch
+from block_stage_cases import device_reports, in_calls as _in_calls, join as _join, memory_comes_back, same as _same
 from mercury_amd import (IQC_NO_BALANCE, IQC_REPORT_DTYPE, IQC_SKIPPED, Channelizer, IqCorrector, MgpuError, RxCapture, RxPhy, Synthesizer,
                          WidebandBlanker, host_chan_process, host_iqc_process, host_wblank_process, iqc_reports)
 from oraclelib import CARRIER
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(got, want):
-    return (got[0].shape == want[0].shape and got[0].dtype == want[0].dtype and got[0].tobytes() == want[0].tobytes()
-            and got[1].shape == want[1].shape and got[1].tobytes() == want[1].tobytes())
-
-
-def _device_reports(d_reports, n):
-    return d_reports.cpu().numpy().reshape(-1)[: n * IQC_REPORT_DTYPE.itemsize].view(IQC_REPORT_DTYPE)
-
-
-def _join(parts):
-    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
 
 @pytest.mark.parametrize("memory", [0, 2])
@@ -67,18 +55,6 @@ def test_a_call_that_crosses_a_round_of_the_scan():
     assert qc.max_in == 1024 * B
     assert _same(qc.process_raw(x), want)
     qc.close()
-
-
-def _in_calls(qc, x, blocks):
-    """x fed in calls of the given block counts -> (out, reports) of all calls"""
-    parts, at = [], 0
-    for m in blocks:
-        o, r = qc.process_raw(x[at * qc.B: (at + m) * qc.B])
-        assert len(o) == m * qc.B and len(r) == m
-        parts.append((o, r))
-        at += m
-    assert at * qc.B == len(x)
-    return _join(parts)
 
 
 @pytest.mark.parametrize("fmt,B", [("cf32", 256), ("cs16", 768), ("cf64", 4096)])
@@ -148,7 +124,7 @@ def test_process_dev_on_a_callers_stream_and_on_the_contexts():
             assert got == m
             assert d_out.cpu().numpy().tobytes() == want[0].tobytes()
             if with_reports:
-                assert _device_reports(d_reports, m).tobytes() == want[1].tobytes()
+                assert device_reports(d_reports, m, IQC_REPORT_DTYPE).tobytes() == want[1].tobytes()
             else:
                 assert (d_reports.cpu().numpy() == 0xA5).all()
     with pytest.raises(MgpuError):
@@ -340,7 +316,7 @@ def test_three_links_end_to_end_behind_an_impaired_front_end():
                 part = d_out
             events += [(e[0], e[1], None, e[3].tobytes()) for e in cap.run_wideband(ch, part)]
         if qc:
-            last_report[:] = iqc_reports(_device_reports(d_reports, step * D // 4096))[-1:]
+            last_report[:] = iqc_reports(device_reports(d_reports, step * D // 4096, IQC_REPORT_DTYPE))[-1:]
         for h in (ch, cap, qc):
             if h:
                 h.close()
@@ -371,30 +347,4 @@ def test_three_links_end_to_end_behind_an_impaired_front_end():
 def test_create_use_destroy_gives_the_memory_back():
     """50 create / process / destroy cycles (the state, the sums, the estimates, staging, the output buffers) leave the device's free
     memory where it was"""
-    import gc
-    torch = _torch()
-
-    def free_hbm():
-        gc.collect()
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
-        return torch.cuda.mem_get_info()[0]
-
-    rx = _rx()
-    x = ref.to_format(ref.white(64 * 4096, 6), "cf64")
-
-    def cycle():
-        qc = IqCorrector(rx, 64, "cf64")
-        qc.process_raw(x)
-        return qc
-
-    cycle().close()
-    first = free_hbm()
-    qc = cycle()
-    in_use = first - free_hbm()
-    qc.close()
-    assert in_use >= 2 * 64 * 4096 * 16, in_use                         # the staging area and the output of 64 blocks
-    for _ in range(50):
-        cycle().close()
-    after = free_hbm()
-    assert abs(after - first) < 64 << 20, (first, after)
+    memory_comes_back(lambda: IqCorrector(_rx(), 64, "cf64"), ref.to_format(ref.white(64 * 4096, 6), "cf64"))

@@ -11,20 +11,12 @@ import pytest
 
 import wblank_ref as ref
 from band_links import ThreeLinks, last_error, other_rx, rx as _rx, torch as _torch
+from block_stage_cases import device_reports, in_calls as _in_calls, join as _join, memory_comes_back, same as _same
 from mercury_amd import (WBLANK_REPORT_DTYPE, Channelizer, MgpuError, RxCapture, Synthesizer, WidebandBlanker, host_wblank_process,
                          wblank_reports)
 from oraclelib import CARRIER
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(got, want):
-    return (got[0].shape == want[0].shape and got[0].dtype == want[0].dtype and got[0].tobytes() == want[0].tobytes()
-            and got[1].shape == want[1].shape and got[1].tobytes() == want[1].tobytes())
-
-
-def _device_reports(d_reports, n):
-    return d_reports.cpu().numpy().reshape(-1)[: n * WBLANK_REPORT_DTYPE.itemsize].view(WBLANK_REPORT_DTYPE)
 
 
 @pytest.mark.parametrize("guard", [0, 64])
@@ -46,19 +38,6 @@ def test_output_and_reports_equal_the_twin(fmt, B, guard):
     assert _same(wb.process_raw(d_x), want)
     assert wb.status().position == len(x) and wb.status().blocks == ref.PLANTED_BLOCKS
     wb.close()
-
-
-def _in_calls(wb, x, blocks):
-    """x fed in calls of the given block counts -> (out, reports) of all calls"""
-    outs, reports, at = [], [], 0
-    for m in blocks:
-        o, r = wb.process_raw(x[at * wb.B: (at + m) * wb.B])
-        assert len(o) == m * wb.B and len(r) == m
-        outs.append(o)
-        reports.append(r)
-        at += m
-    assert at * wb.B == len(x)
-    return np.concatenate(outs), np.concatenate(reports)
 
 
 @pytest.mark.parametrize("fmt,B", [("cf32", 256), ("cs16", 64), ("cf64", 4096)])
@@ -83,7 +62,7 @@ def test_chunking_and_seeking_do_not_change_a_byte(fmt, B):
     assert "n_in must be a positive multiple of B" in last_error(_rx())
     assert wb.status().position == 4 * B
     rest = _in_calls(wb, x[4 * B:], [8, 8, 4])
-    assert _same((np.concatenate([first[0], rest[0]]), np.concatenate([first[1], rest[1]])), want)
+    assert _same(_join([first, rest]), want)
     for bad in (B // 2, B + 1, 2 ** 62 + B):
         with pytest.raises(MgpuError):
             wb.seek(bad)
@@ -123,7 +102,7 @@ def test_process_dev_on_a_callers_stream_and_on_the_contexts():
             assert got == m
             assert d_out.cpu().numpy().tobytes() == want[0].tobytes()
             if with_reports:
-                assert _device_reports(d_reports, m).tobytes() == want[1].tobytes()
+                assert device_reports(d_reports, m, WBLANK_REPORT_DTYPE).tobytes() == want[1].tobytes()
             else:
                 assert (d_reports.cpu().numpy() == 0xA5).all()
     with pytest.raises(MgpuError):
@@ -157,9 +136,8 @@ def test_two_handles_on_two_contexts_stay_independent():
     for i in range(4):
         got_a.append(a.process_raw(xa[i * 3 * B: (i + 1) * 3 * B]))
         got_b += [b.process_raw(xb[(3 * i + j) * B: (3 * i + j + 1) * B]) for j in range(3)]
-    join = lambda parts: (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
-    assert _same(join(got_a), host_wblank_process(xa, 4, guard=7))
-    assert _same(join(got_b), host_wblank_process(xb, 1, guard=0, threshold=30.0))
+    assert _same(_join(got_a), host_wblank_process(xa, 4, guard=7))
+    assert _same(_join(got_b), host_wblank_process(xb, 1, guard=0, threshold=30.0))
     a.close(), b.close()
 
 
@@ -208,7 +186,7 @@ def test_three_links_end_to_end_with_clicks():
                 part = d_out
             events += [(e[0], e[1], None, e[3].tobytes()) for e in cap.run_wideband(ch, part)]
             if wb:
-                zeroed += int(_device_reports(d_reports, step * D // B)["blanked"].sum())
+                zeroed += int(device_reports(d_reports, step * D // B, WBLANK_REPORT_DTYPE)["blanked"].sum())
         for h in (ch, cap, wb):
             if h:
                 h.close()
@@ -227,30 +205,4 @@ def test_three_links_end_to_end_with_clicks():
 def test_create_use_destroy_gives_the_memory_back():
     """50 create / process / destroy cycles (the held block, the flag words, staging, the output buffers) leave the device's free memory
     where it was"""
-    import gc
-    torch = _torch()
-
-    def free_hbm():
-        gc.collect()
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
-        return torch.cuda.mem_get_info()[0]
-
-    rx = _rx()
-    x = ref.noise(6, 64 * 4096, "cf64")
-
-    def cycle():
-        wb = WidebandBlanker(rx, 64)
-        wb.process_raw(x)
-        return wb
-
-    cycle().close()
-    first = free_hbm()
-    wb = cycle()
-    in_use = first - free_hbm()
-    wb.close()
-    assert in_use >= 2 * 64 * 4096 * 16, in_use                         # the staging area and the output of 64 blocks
-    for _ in range(50):
-        cycle().close()
-    after = free_hbm()
-    assert abs(after - first) < 64 << 20, (first, after)
+    memory_comes_back(lambda: WidebandBlanker(_rx(), 64), ref.noise(6, 64 * 4096, "cf64"))

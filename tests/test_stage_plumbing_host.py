@@ -1,6 +1,7 @@
 """CPU tests of the plumbing the optional stages share: the host twins' geometry cache (mercury_amd/csrc/geometry_cache.hpp) through every
-twin family and under the sanitizers, the one parser behind parse_demapper / parse_blanker / parse_excisor, and the binding's checked
-call. The parsers' results and every error text are literals recorded from the binding as it was before these pieces were shared."""
+twin family and under the sanitizers, the one parser behind parse_demapper / parse_blanker / parse_excisor, the binding's checked
+call, and what the wideband IQ stages' twins raise where they refuse a call. The parsers' results and every error text are literals
+recorded from the binding as it was before these pieces were shared."""
 import os
 import subprocess
 
@@ -194,3 +195,73 @@ def test_refused_host_calls_raise_what_they_raised(what, call, message, code):
         call()
     assert str(e.value) == message
     assert e.value.code == code
+
+
+# ---- 5. what a refused twin call of the wideband IQ stages raises ---------------------------------------------------------------------------
+# The smallest shapes: the blanker at B = 64, the corrector at B = 256, the scanner at N = 256 (H = 128) and two blocks per line, the tuner
+# at D = 1 and four symbols. Every text and code below was recorded from the binding and the library of the commit before the stages'
+# call checks and the two block twins' Python halves were shared.
+WB, QC, SC = np.zeros(128, np.complex64), np.zeros(512, np.complex64), np.zeros(512, np.complex64)
+TU = np.zeros(M.tune_samples(1, 4), np.complex128)
+T6 = np.zeros(6)
+
+
+def _wb(x=WB, D=4, **kw):
+    return M.host_wblank_process(x, D, block=64, **kw)
+
+
+def _qc(x=QC, D=4, **kw):
+    return M.host_iqc_process(x, D, block=256, **kw)
+
+
+def _sc(x=SC, D=4, **kw):
+    return M.host_scan_process(x, D, log2n=8, blocks_per_line=2, **kw)
+
+
+def _tu(x=TU, D=1, **kw):
+    return M.host_tune_process(x, D, [(0, 0, 1.0)], symbols=4, search=2, taps=M.host_chan_design(1, 8), **kw)
+
+
+def _twin_calls(name, twin, x, block, grid, **kw):
+    """the refusals every twin with a position has, for an input x of two grid steps: (what, call)"""
+    assert len(x) == 2 * grid
+    return [(name + ", unknown format number", lambda: twin(fmt=7, **kw)),
+            (name + ", n_in no multiple of the block", lambda: twin(x[: block + 1], **kw)),
+            (name + ", position off the block grid", lambda: twin(position=grid // 2, **kw)),
+            (name + ", position past 2^62", lambda: twin(position=2 ** 62 + grid, **kw)),
+            (name + ", the call ends past 2^62", lambda: twin(position=2 ** 62 - grid, **kw)),            # len(x) = 2 grid
+            (name + ", D = 0", lambda: twin(D=0, **kw)),
+            (name + ", D = 65", lambda: twin(D=65, **kw)),
+            (name + ", wrong struct_size", lambda: twin(struct_size=20, **kw))]
+
+
+TWIN_CALLS = (_twin_calls("wblank", _wb, WB, 64, 64) + _twin_calls("iqc", _qc, QC, 256, 256)
+              + _twin_calls("iqc with state", _qc, QC, 256, 256, state=T6) + _twin_calls("scan", _sc, SC, 128, 256)
+              + [("tune, unknown format number", lambda: _tu(fmt=7)), ("tune, n_in one too many", lambda: _tu(np.zeros(len(TU) + 1, np.complex128))),
+                 ("tune, D = 0", lambda: _tu(D=0)), ("tune, D = 65", lambda: _tu(D=65)), ("tune, wrong struct_size", lambda: _tu(struct_size=20))])
+TWIN_RAISES = {"wblank": "mgpu_host_wblank_process: bad argument", "iqc": "mgpu_host_iqc_process: bad argument",
+               "iqc with state": "mgpu_host_iqc_continue: bad argument", "scan": "mgpu_host_scan_process: bad argument",
+               "tune": "mgpu_host_tune_process: bad argument"}
+STATE_CALLS = [("state of 5", np.zeros(5)), ("state of float32", np.zeros(6, np.float32)), ("state a list", [0.0] * 6),
+               ("state not contiguous", np.zeros(12)[::2])]
+
+
+def test_the_twins_take_the_smallest_good_calls():
+    """what the refusals below change one argument of"""
+    assert len(_wb()[1]) == 2 and len(_qc()[1]) == 2 and len(_qc(state=T6.copy())[1]) == 2 and len(_sc()[0]) == 2 and len(_tu()) == 1
+
+
+@pytest.mark.parametrize("what,call", TWIN_CALLS, ids=[c[0] for c in TWIN_CALLS])
+def test_refused_twin_calls_raise_what_they_raised(what, call):
+    with pytest.raises(MgpuError) as e:
+        call()
+    assert str(e.value) == TWIN_RAISES[what.split(",")[0]]
+    assert e.value.code == 1
+
+
+@pytest.mark.parametrize("what,state", STATE_CALLS, ids=[c[0] for c in STATE_CALLS])
+def test_a_wrong_shaped_state_raises_what_it_raised(what, state):
+    with pytest.raises(MgpuError) as e:
+        _qc(state=state)
+    assert str(e.value) == "state: a contiguous float64 array of 6"
+    assert e.value.code == 1
